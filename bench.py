@@ -14,6 +14,13 @@ exits with its code (the parent never initialises HIP). On the GPU, untimed step
 ``--settle-ms`` (300 ms: the shader clock's ramp, ``extra.settle``); then W untimed warmup steps and EXACTLY K timed steps
 bracketed by barrier + torch.cuda.synchronize() on both sides; max time over ranks; rank 0 prints ONE JSON line.
 
+A plain run does only that: set up (world > 1: choose the schedule, below), settle, warm up, time the K steps, write
+``--dump-outputs DIR`` if given (the last timed step's loss rows and updated weights as ``.npy``, reproducible from run
+to run: the weights restart from their seeded values after the settle phase) and print the line with ``ms_per_step``.
+Everything else this file measures or checks runs only with ``--full``: the reference-batch cell (``extra.mb1792``),
+the traced pass (``extra.allreduce``), the extras after the headline, the exactness gate of a fixed schedule, the
+layout gate and the replica check (``extra.dist``); without ``--full`` those keys are null or absent.
+
 World > 1 (GPU): the run chooses its own schedule and checks it before timing anything (``--schedule auto``):
 * every available arm — the C++ engine's mesh over its own RCCL communicator, the direct-P2P mesh and the direct-P2P
   ring over the link-disjoint rings, each with persistent or tile-grid GEMMs while a request is in flight, and the
@@ -21,22 +28,22 @@ World > 1 (GPU): the run chooses its own schedule and checks it before timing an
   request vs the NumPy simulators, :mod:`fpga_ai_nic_amd.parallel.gate`) and is timed for a few steps;
   ``extra.schedule_ab`` lists every arm (ms/step, exactness, or the error that excluded it), ``extra.gates_failed``
   the arms whose all-reduce was not bit-exact (excluded; the run still records the fastest exact arm);
-* the headline runs on the fastest exact arm; ``extra.dist.allreduce_exact`` is its gate. Exit codes: an A/B arm
-  that fails the gate is excluded and listed in ``extra.gates_failed`` (the run still exits 0 with the fastest exact
-  arm); only a failed gate of ``--schedule fixed``'s own engine exits 3 (after printing the line), diverged replicas
-  exit 2, and no exact arm at all exits 3 without a line;
-* after the headline (bounded by ``--extra-budget`` seconds): ``extra.config4`` (256 MB all-reduce + fused SGD:
-  BFP mesh / ring, the uncompressed f32 all-reduce over the same transport and RCCL f32 + SGD kernel: algo- and
-  bus-BW; BASELINE configs 2/4) and ``extra.uncompressed`` (the same MLP step with an uncompressed all-reduce:
+* the headline runs on the fastest exact arm; ``extra.dist.allreduce_exact`` (``--full``) is its gate. Exit codes:
+  an A/B arm that fails the gate is excluded and listed in ``extra.gates_failed`` (the run still exits 0 with the
+  fastest exact arm); with ``--full`` only a failed gate of ``--schedule fixed``'s own engine exits 3 (after printing
+  the line) and diverged replicas exit 2; no exact arm at all exits 3 without a line;
+* ``--full``, after the headline (bounded by ``--extra-budget`` seconds): ``extra.config4`` (256 MB all-reduce +
+  fused SGD: BFP mesh / ring, the uncompressed f32 all-reduce over the same transport and RCCL f32 + SGD kernel:
+  algo- and bus-BW; BASELINE configs 2/4) and ``extra.uncompressed`` (the same MLP step with an uncompressed all-reduce:
   the analogue of the reference's smart-NIC vs MPI_Iallreduce comparison, sw/mlp_mpi_example_f32.cpp:615-643 vs
   :752-787).
-World 1 also reports ``extra.forced_dist_ms_per_step`` (the multi-rank path over a 1-rank group) and
+World 1 with ``--full`` also reports ``extra.forced_dist_ms_per_step`` (the multi-rank path over a 1-rank group) and
 ``extra.unfused_update_ms_per_step`` (decode + SGD as a separate pass instead of inside the bwd-weight GEMM), so a
 1 -> N curve splits into compute, update pass and exposed communication.
 
 Synthetic data (random bf16 inputs, random labels) and random-init weights of the named architecture.
 Reference workload shapes: sw/run.sh:16 (global MB 5376 over 3 ranks = 1792 per rank) — reported as
-``extra.mb1792`` next to the headline per-GPU batch.
+``extra.mb1792`` next to the headline per-GPU batch (``--full``).
 """
 from __future__ import annotations
 
@@ -53,6 +60,7 @@ SIZES = [1024, 4096, 4096, 1024]
 REF_MB_PER_RANK = 1792  # sw/run.sh:16: global MB 5376 / 3 ranks
 REF_STEPS = 100  # timed steps of the reference-batch measurement (extra.mb1792) at least
 CONFIG4_MB = 256  # BASELINE config 4: 256 MB synthetic gradient
+DUMP_SAMPLE = 1 << 21  # --dump-outputs: elements kept of a weight bucket larger than this (8 MB of float32 a layer)
 
 
 def parse_args(argv=None):
@@ -60,6 +68,17 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure and check everything else: the reference-batch cell "
+                         "(--ref-mb), the traced pass (extra.allreduce), the extras (--extra-budget), a fixed "
+                         "schedule's exactness gate, the layout gate and the replica check (extra.dist); without it "
+                         "the run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (rank 0) as DIR/<name>.npy: "
+                         "loss_rows (float32, every row) and fc<i>_master (float32; each layer's updated weight "
+                         "bucket, or a fixed, seeded sample of DUMP_SAMPLE of its elements). The weights are set "
+                         "back to their seeded initial values after the settle phase, so the last step is step "
+                         "W + K from the same start in every run")
     ap.add_argument("--settle-ms", type=float, default=300.0,
                     help="GPU: before the headline's W warmup steps, untimed steps of the same batch until this much "
                          "wall time has passed (the shader clock's ramp; extra.settle); 0 = off")
@@ -69,7 +88,7 @@ def parse_args(argv=None):
     # The reference's own per-rank batch (1792) is measured as well and reported in extra.mb1792.
     ap.add_argument("--mb-per-gpu", type=int, default=8192)
     ap.add_argument("--ref-mb", type=int, default=REF_MB_PER_RANK,
-                    help="also time K steps at this per-GPU batch (extra.mb<ref>); 0 disables")
+                    help="--full: also time K steps at this per-GPU batch (extra.mb<ref>); 0 disables")
     ap.add_argument("--compress", default="bfp", choices=["bfp", "raw", "raw_bf16", "rccl", "local"])
     ap.add_argument("--rounding", default="rne", choices=["rne", "trunc"])
     ap.add_argument("--schedule", default="auto", choices=["auto", "fixed"],
@@ -110,10 +129,10 @@ def parse_args(argv=None):
                          "decides)")
     ap.add_argument("--ab2-top", type=int, default=3, help="arms kept for stage 2 of the schedule A/B")
     ap.add_argument("--no-trace", action="store_true",
-                    help="skip the separate traced pass that measures the all-reduce phases (extra.allreduce)")
+                    help="--full: skip the separate traced pass that measures the all-reduce phases (extra.allreduce)")
     ap.add_argument("--extra-budget", type=float, default=240.0,
-                    help="seconds the extras after the headline may take in total (config 4, uncompressed step, the "
-                         "world-1 split); what does not fit is recorded as skipped; 0 disables them")
+                    help="--full: seconds the extras after the headline may take in total (config 4, uncompressed step, "
+                         "the world-1 split); what does not fit is recorded as skipped; 0 disables them")
     ap.add_argument("--arm-timeout", type=float, default=90.0,
                     help="world > 1 schedule A/B: bound of each arm's exactness gate and of its steps' waits; an arm "
                          "whose transport hangs fails at this bound, the transport is aborted on every rank and its "
@@ -369,6 +388,7 @@ def main(argv=None):
 
     stall_rank = int(os.environ.get("FAN_BENCH_STALL_RANK", "-1"))
     settle = {}  # the headline's untimed settle steps (extra.settle)
+    start_state = None  # --dump-outputs: the headline model's (master, lp) planes before its first step
 
     def run(setup, mb, seed, warmup, steps, tag, graph_ok=False, trace=False, wait_s=None):
         """W warmup + K timed steps of ``setup`` at per-GPU batch mb: (elapsed s max over ranks, host enqueue s,
@@ -424,6 +444,14 @@ def main(argv=None):
                 if D.max_over_ranks(time.perf_counter() - t_s) * 1e3 >= a.settle_ms:
                     break
             settle[tag] = {"steps": n_s, "ms": round((time.perf_counter() - t_s) * 1e3, 1)}
+            if tag == "timed" and start_state is not None:
+                # --dump-outputs: the settle phase ran as many steps as fit its time; back to the seeded weights, so
+                # the W + K steps that follow compute the same in every run
+                for l, (w0, lp0) in zip(model.layers, start_state):
+                    l.master.copy_(w0)
+                    if lp0 is not None:
+                        l.lp.copy_(lp0)
+                torch.cuda.synchronize()
         if stall_rank == rank and tag == "timed":  # test hook: this rank stops taking part (a hung peer)
             time.sleep(float(os.environ.get("FAN_BENCH_STALL_S", "600")))
         for _ in range(warmup):
@@ -655,12 +683,12 @@ def main(argv=None):
                            sdma=a.p2p_copy == "sdma" and transport == "p2p",
                            kflag=a.p2p_flags == "kernel" and transport == "p2p",
                            shard=None if a.shard_update < 0 else bool(a.shard_update))
-        if multi and main_setup.engine is not None:
+        if a.full and multi and main_setup.engine is not None:
             gate_rec = gate.allreduce_exactness(main_setup.engine)
             if not gate_rec["exact"]:
                 gates_failed.append({"arm": "main", **gate_rec})
     engine, model, trainer = main_setup.engine, main_setup.model, main_setup.trainer
-    if multi and engine is not None and gate_rec is not None and gate_rec.get("exact"):
+    if a.full and multi and engine is not None and gate_rec is not None and gate_rec.get("exact"):
         # the chosen schedule once more, on every bucket layout the model actually trains (each layer's size at this
         # world's arena slot: chunking and ring block geometry differ from the 1 Mi-element gate request)
         wd.arm("layout gate")
@@ -678,14 +706,23 @@ def main(argv=None):
     held["engine"] = engine
     held["comm"] = ctx["p2p"] if main_setup.info.get("transport") == "p2p" else None
     held["transport"] = ctx["native"] or ctrl
-    can_trace = (not a.no_trace and hasattr(engine, "trace") and not getattr(engine, "inline", True))
+    can_trace = (a.full and not a.no_trace and hasattr(engine, "trace") and not getattr(engine, "inline", True))
 
-    # ------------------------------------------------------------------ reference batch, headline, traced pass
+    # ------------------------------------------------------------------ headline, reference batch, traced pass
+    if a.dump_outputs:
+        start_state = [(l.master.clone(), l.lp.clone() if l.lp is not None else None) for l in model.layers]
     elapsed, t_enqueue, loss, _, graphed = run(main_setup, mb, 1234, a.warmup, a.steps, "timed", graph_ok=True)
     ms = elapsed / a.steps * 1e3
     log(f"headline: {ms:.4f} ms/step over {a.steps} steps")
+    if a.dump_outputs:
+        start_state = None
+        wd.arm("dump outputs")
+        if getattr(trainer, "shard", False):  # owner-sharded master: whole again before it is read (collective)
+            trainer.gather_state()
+        if rank == 0:
+            _dump_outputs(a.dump_outputs, model)
     ref = None
-    if a.ref_mb and a.ref_mb != mb:
+    if a.full and a.ref_mb and a.ref_mb != mb:
         # The reference-batch cell runs after the headline, with its own settle phase (both cells are measured alike);
         # a short step, so a longer window (a host hiccup is then a smaller share of it).
         ref_steps = max(a.steps, REF_STEPS) if cuda else a.steps
@@ -757,6 +794,7 @@ def main(argv=None):
                                   "mismatch_ranks": g.get("mismatch_ranks")} for g in gates_failed],
                 "dist": dist_rec,
                 **dict(extras),
+                "full": a.full,
                 "extras_s": round(extras_s, 2),
                 "run_s": round(time.perf_counter() - t_begin, 2),
                 "gemm_tuning": _tuning_report(),
@@ -795,7 +833,7 @@ def main(argv=None):
             log(f"extra {name} failed: {ex}")
 
     t_extra0 = time.perf_counter()
-    if a.extra_budget > 0:
+    if a.full and a.extra_budget > 0:
         if world == 1 and not a.force_dist and engine is not None:
             def split(fused, force, shard=None):
                 s = build("split", a.compress, transport="auto", fused=fused, force=force, shard=shard)
@@ -899,8 +937,10 @@ def main(argv=None):
     # replicas after every step of the run: bit-identical weights on every rank (the reference reads its NIC
     # registers back to stdout after programming them, sw/mlp_mpi_example_f32.cpp:65-98; here the run proves
     # what it ran on and that the replicas agree)
-    wd.arm("verify")
-    dist_rec = _dist_report(main_setup, world, rank, device, D, gate_rec)
+    dist_rec = None
+    if a.full:
+        wd.arm("verify")
+        dist_rec = _dist_report(main_setup, world, rank, device, D, gate_rec)
     wd.disarm()
 
     if rank == 0:
@@ -908,7 +948,7 @@ def main(argv=None):
     wd.arm("cleanup")
     D.cleanup()
     wd.close()
-    if not dist_rec["replicas_identical"]:
+    if dist_rec is not None and not dist_rec["replicas_identical"]:
         print(f"[bench] rank {rank}: replicas DIVERGED: {dist_rec['replica_digests']}", file=sys.stderr, flush=True)
         return 2
     if gates_failed:
@@ -1043,6 +1083,26 @@ def _config4(a, world, rank, device, ctx, native_transport, p2p_comm, make_engin
             torch.cuda.synchronize()
             torch.cuda.empty_cache()
     return out
+
+
+def _dump_outputs(out_dir, model):
+    """--dump-outputs: what the last timed step left its caller, as float32 ``.npy`` files: the per-row loss it
+    returned and every layer's updated fp32 weight bucket (W | b, without the padding). A bucket above DUMP_SAMPLE
+    elements is written as the elements at DUMP_SAMPLE seeded positions (seed = layer index; the same positions in
+    every run and every build), which keeps the whole dump under 64 MB."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"loss_rows": model.loss_rows}
+    for i, l in enumerate(model.layers):
+        w = l.master[: l.n]
+        if l.n > DUMP_SAMPLE:
+            idx = torch.randint(0, l.n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(i))
+            w = w.index_select(0, idx.to(w.device))
+        out[f"fc{i}_master"] = w
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
 
 
 def _tuning_report():

@@ -9,7 +9,8 @@
 #
 #   test[=<pytest args>]      pytest -m gpu (default: the whole GPU suite) with a per-test thread timeout
 #   smoke                     __graft_entry__.smoke()
-#   bench[=<bench.py args>]   one flagship bench run (JSON line -> bench.jsonl)
+#   bench[=<bench.py args>]   one flagship bench run (JSON line -> bench.jsonl); bench=--full adds the MB 1792 cell,
+#                             the traced all-reduce, the extras and the replica check to the headline
 #   prof[=<bench.py args>]    rocprofv3 --kernel-trace --stats of a bench run; per-kernel summary -> prof_stats.csv
 #   pmc=<c1,c2,...>[:<args>]  ONE rocprofv3 --pmc pass (counters within the per-block slot limits) over a bench run
 #   py=<script> [args]        any python tool / probe in the tree (e.g. py=bench/gemm_bench.py --shapes mlp)

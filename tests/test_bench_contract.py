@@ -28,7 +28,7 @@ def _json_lines(out):
 @pytest.mark.parametrize("world", [1, 2, 3, 4])  # 3: the reference's world size (sw/run.sh: mpirun -n 3)
 def test_bench_json_contract(world, tmp_path):
     args = [os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-            "--mb-per-gpu", "16"]
+            "--mb-per-gpu", "16", "--full"]
     if world > 1:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port())] + args
@@ -65,11 +65,44 @@ def test_bench_json_contract(world, tmp_path):
         assert cfg["schedule"] == ab[0]["arm"]
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the run times its K steps and prints the line, nothing else (no reference-batch cell, no
+    extras, no replica check); --dump-outputs writes the last timed step's loss rows and updated weights as float32
+    .npy files, the same from run to run."""
+    import numpy as np
+
+    def once(out):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+               "--mb-per-gpu", "16", "--dump-outputs", str(out)]
+        env = dict(os.environ, OMP_NUM_THREADS="2", CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
+        r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        recs = _json_lines(r.stdout)
+        assert len(recs) == 1, r.stdout
+        return recs[0]
+
+    rec = once(tmp_path / "a")
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["dtype"] == "bf16"
+    assert rec["value"] == pytest.approx(16 / (rec["ms_per_step"] / 1e3), rel=1e-2)
+    ex = rec["extra"]
+    assert ex["full"] is False and ex["dist"] is None and ex["mb1792"] is None and ex["allreduce"] is None
+    assert not {"unfused_update_ms_per_step", "forced_dist_ms_per_step", "config5", "ref_workload"} & set(ex)
+    once(tmp_path / "b")
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["fc0_master.npy", "fc1_master.npy", "fc2_master.npy", "loss_rows.npy"]
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype == np.float32 and np.isfinite(x).all() and np.array_equal(x, y), n
+        total += x.nbytes
+    assert np.load(tmp_path / "a" / "loss_rows.npy").shape == (16,) and total <= 64 << 20
+
+
 def test_bench_self_launches_ranks(tmp_path):
     """``python bench.py --gpus 2`` with no torch.distributed environment starts its 2 ranks itself (a
     torch.distributed.run child; the parent never touches the GPU) and still prints exactly one JSON line."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--mb-per-gpu", "16", "--ref-mb", "8"]
+           "--mb-per-gpu", "16", "--ref-mb", "8", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(OMP_NUM_THREADS="2", CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=300)
@@ -101,7 +134,7 @@ def test_bench_prints_the_headline_when_an_extra_hangs(tmp_path):
     until its watchdog fires — which prints the record of the headline measured before (one JSON line, the phase it
     was aborted in) before ending the run, instead of losing the measurement."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--mb-per-gpu", "16", "--ref-mb", "0", "--timeout", "20"]
+           "--mb-per-gpu", "16", "--ref-mb", "0", "--timeout", "20", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(OMP_NUM_THREADS="2", CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="",
                FAN_BENCH_STALL_EXTRA="uncompressed:1")

@@ -22,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _bench(tmp_path, *extra, timeout=420):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--transport", "p2p", "--steps", "3",
-           "--warmup", "1", "--mb-per-gpu", "512", "--ref-mb", "256", "--timeout", "150", *extra]
+           "--warmup", "1", "--mb-per-gpu", "512", "--ref-mb", "256", "--timeout", "150", "--full", *extra]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(FAN_CTRL_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=timeout)
