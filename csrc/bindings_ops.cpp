@@ -24,6 +24,48 @@ int64_t ld_of(const at::Tensor& t) {
   return t.stride(0);
 }
 
+// The kEpiWire fields of g (its M, N, ldc and colsum set): the wire buffer and, with upd_master, the fused local
+// update's bucket planes.
+void set_wire(GemmArgs& g, const c10::optional<at::Tensor>& wire, int64_t wire_shard, int64_t wire_own,
+              int64_t wire_codec, int64_t wire_period, int64_t wire_off, const c10::optional<at::Tensor>& upd_master,
+              const c10::optional<at::Tensor>& upd_lp, const c10::optional<at::Tensor>& upd_mom,
+              const SgdParams& upd) {
+  TORCH_CHECK(wire && wire->is_cuda() && wire->is_contiguous() && wire->scalar_type() == at::kByte,
+              "wire epilogue needs a contiguous uint8 GPU wire buffer");
+  TORCH_CHECK(wire_shard > 0 && wire_shard % 256 == 0, "wire_shard must be a positive multiple of 256");
+  // with colsum the encoded bias segment follows C: flat M*ldc .. M*ldc + N - 1
+  TORCH_CHECK(wire_off >= 0 && wire_off % 16 == 0, "wire_off must be a non-negative multiple of 16");
+  const int64_t last = wire_off + (g.colsum ? (int64_t)g.M * g.ldc + g.N - 1 : (int64_t)(g.M - 1) * g.ldc + g.N - 1);
+  const int64_t need = (last / wire_shard + 1) * (int64_t)wire_shard_bytes((int)wire_codec, (size_t)wire_shard);
+  TORCH_CHECK(wire->numel() >= need, "wire buffer too small: ", wire->numel(), " < ", need);
+  g.wire = wire->data_ptr<uint8_t>();
+  g.wire_shard = wire_shard;
+  g.wire_own = (int)wire_own;
+  g.wire_period = (int)wire_period;
+  g.wire_codec = (int)wire_codec;
+  g.wire_off = wire_off;
+  if (upd_master) {  // fused local update: the bucket planes cover every flat index the epilogue touches
+    auto plane = [&](const at::Tensor& t, at::ScalarType st, const char* what) {
+      TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == st && t.numel() > last &&
+                      t.data_ptr() != nullptr && (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0,
+                  "fused update: ", what, " must be a contiguous, 16-B aligned GPU plane covering the bucket");
+    };
+    TORCH_CHECK(wire_own == -1, "fused update: no owner shard (single-rank engine)");
+    TORCH_CHECK(wire_codec == kBfpRne, "fused update: rne codec only");
+    plane(*upd_master, at::kFloat, "master");
+    g.upd_master = upd_master->data_ptr<float>();
+    if (upd_lp) {
+      plane(*upd_lp, at::kBFloat16, "lp");
+      g.upd_lp = reinterpret_cast<bf16_t*>(upd_lp->data_ptr());
+    }
+    if (upd_mom) {
+      plane(*upd_mom, at::kFloat, "mom");
+      g.upd_mom = upd_mom->data_ptr<float>();
+    }
+    g.upd = upd;
+  }
+}
+
 // C = op(A) op(B) with fused epilogue.
 //   a_t: if true, A is given as a [K][M] tensor (MN-contiguous), else [M][K]
 //   b_t: if true, B is given as a [N][K] tensor (K-contiguous), else [K][N]
@@ -79,42 +121,10 @@ void gemm(const at::Tensor& A, bool a_t, const at::Tensor& B, bool b_t, at::Tens
   }
   if (workspace) g.workspace = workspace->data_ptr();
   if (epilogue == kEpiWire) {
-    TORCH_CHECK(wire && wire->is_cuda() && wire->is_contiguous() && wire->scalar_type() == at::kByte,
-                "wire epilogue needs a contiguous uint8 GPU wire buffer");
-    TORCH_CHECK(wire_shard > 0 && wire_shard % 256 == 0, "wire_shard must be a positive multiple of 256");
-    // with colsum the encoded bias segment follows C: flat M*ldc .. M*ldc + N - 1
-    TORCH_CHECK(wire_off >= 0 && wire_off % 16 == 0, "wire_off must be a non-negative multiple of 16");
-    const int64_t last = wire_off + (g.colsum ? (int64_t)g.M * g.ldc + g.N - 1 : (int64_t)(g.M - 1) * g.ldc + g.N - 1);
-    const int64_t need = (last / wire_shard + 1) * (int64_t)wire_shard_bytes((int)wire_codec, (size_t)wire_shard);
-    TORCH_CHECK(wire->numel() >= need, "wire buffer too small: ", wire->numel(), " < ", need);
-    g.wire = wire->data_ptr<uint8_t>();
-    g.wire_shard = wire_shard;
-    g.wire_own = (int)wire_own;
-    g.wire_period = (int)wire_period;
-    g.wire_codec = (int)wire_codec;
-    g.wire_off = wire_off;
-    if (upd_master) {  // fused local update: the bucket planes cover every flat index the epilogue touches
-      auto plane = [&](const at::Tensor& t, at::ScalarType st, const char* what) {
-        TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == st && t.numel() > last &&
-                        t.data_ptr() != nullptr && (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0,
-                    "fused update: ", what, " must be a contiguous, 16-B aligned GPU plane covering the bucket");
-      };
-      TORCH_CHECK(wire_own == -1, "fused update: no owner shard (single-rank engine)");
-      TORCH_CHECK(wire_codec == kBfpRne, "fused update: rne codec only");
-      plane(*upd_master, at::kFloat, "master");
-      g.upd_master = upd_master->data_ptr<float>();
-      if (upd_lp) {
-        plane(*upd_lp, at::kBFloat16, "lp");
-        g.upd_lp = reinterpret_cast<bf16_t*>(upd_lp->data_ptr());
-      }
-      if (upd_mom) {
-        plane(*upd_mom, at::kFloat, "mom");
-        g.upd_mom = upd_mom->data_ptr<float>();
-      }
-      g.upd = SgdParams{(float)upd_lr, (float)upd_grad_scale, (float)upd_weight_decay, (float)upd_momentum,
-                        upd_nesterov ? 1 : 0};
-      g.defer_colsum = defer_colsum && g.colsum != nullptr;
-    }
+    set_wire(g, wire, wire_shard, wire_own, wire_codec, wire_period, wire_off, upd_master, upd_lp, upd_mom,
+             SgdParams{(float)upd_lr, (float)upd_grad_scale, (float)upd_weight_decay, (float)upd_momentum,
+                       upd_nesterov ? 1 : 0});
+    g.defer_colsum = defer_colsum && g.upd_master != nullptr && g.colsum != nullptr;
   }
   if (A.scalar_type() == at::kBFloat16) {
     TORCH_CHECK(bias ? bias->scalar_type() == at::kBFloat16 : true, "bias must be bf16");
@@ -200,6 +210,88 @@ void gemm_wgrad_group(const std::vector<at::Tensor>& Xs, const std::vector<at::T
               "gemm_wgrad_group: unsupported (M % 256, N % 128, K % 64, aligned operands, at most ", 64 * kNumCU,
               " workgroups)");
   launch_gemm_wgrad_group(g.data(), (int)n, fan_stream());
+}
+
+// Up to kGroupMax bwd-weight GEMMs C_i = X_i^T . dY_i (+ colsum_i) on 256x256 tiles at one common split-K count in one
+// dispatch, then one slab reduce for all of them (gemm_group.h launch_gemm_wgrad_splitk_group). Each problem has its own
+// wire target (buffer, shard, owner, period, flat offset) and, with upd_masters, its own bucket planes of the fused
+// local update (every problem or none; one set of SGD hyper-parameters).
+void gemm_wgrad_splitk_group(const std::vector<at::Tensor>& Xs, const std::vector<at::Tensor>& dYs,
+                             const std::vector<at::Tensor>& Cs, const std::vector<at::Tensor>& colsums, int64_t split,
+                             at::Tensor& workspace, const std::vector<at::Tensor>& wires,
+                             const std::vector<int64_t>& wire_shards, const std::vector<int64_t>& wire_owns,
+                             const std::vector<int64_t>& wire_periods, const std::vector<int64_t>& wire_offs,
+                             int64_t wire_codec, const std::vector<c10::optional<at::Tensor>>& upd_masters,
+                             const std::vector<c10::optional<at::Tensor>>& upd_lps,
+                             const std::vector<c10::optional<at::Tensor>>& upd_moms, double upd_lr,
+                             double upd_grad_scale, double upd_weight_decay, double upd_momentum, bool upd_nesterov) {
+  const size_t n = Xs.size();
+  TORCH_CHECK(n >= 1 && n <= (size_t)kGroupMax, "gemm_wgrad_splitk_group: 1..", kGroupMax, " problems");
+  TORCH_CHECK(dYs.size() == n && Cs.size() == n && colsums.size() == n && wires.size() == n &&
+                  wire_shards.size() == n && wire_owns.size() == n && wire_periods.size() == n &&
+                  wire_offs.size() == n && upd_masters.size() == n && upd_lps.size() == n && upd_moms.size() == n,
+              "gemm_wgrad_splitk_group: one X, dY, C, colsum, wire target and update entry per problem");
+  TORCH_CHECK(split == 2 || split == 4, "gemm_wgrad_splitk_group: split 2 or 4");
+  TORCH_CHECK(workspace.is_cuda() && workspace.scalar_type() == at::kFloat && workspace.is_contiguous(),
+              "gemm_wgrad_splitk_group: f32 GPU workspace");
+  const SgdParams sgd{(float)upd_lr, (float)upd_grad_scale, (float)upd_weight_decay, (float)upd_momentum,
+                      upd_nesterov ? 1 : 0};
+  std::vector<GemmArgs> g(n);
+  int64_t ws_off = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const at::Tensor &X = Xs[i], &dY = dYs[i], &C = Cs[i], &cs = colsums[i];
+    TORCH_CHECK(X.is_cuda() && dY.is_cuda() && C.is_cuda() && cs.is_cuda(), "gemm_wgrad_splitk_group: GPU tensors");
+    TORCH_CHECK(X.scalar_type() == at::kBFloat16 && dY.scalar_type() == at::kBFloat16 &&
+                    C.scalar_type() == at::kFloat && cs.scalar_type() == at::kFloat && cs.is_contiguous(),
+                "gemm_wgrad_splitk_group: bf16 X / dY, f32 C / colsum");
+    TORCH_CHECK(X.dim() == 2 && dY.dim() == 2 && X.size(0) == dY.size(0) && C.dim() == 2 && C.size(0) == X.size(1) &&
+                    C.size(1) == dY.size(1) && cs.numel() >= dY.size(1),
+                "gemm_wgrad_splitk_group: shapes (X [K][M], dY [K][N], C [M][N], colsum [N])");
+    GemmArgs& a = g[i];
+    a.A = X.data_ptr(); a.lda = ld_of(X);
+    a.B = dY.data_ptr(); a.ldb = ld_of(dY);
+    a.C = C.data_ptr(); a.ldc = ld_of(C);
+    a.M = (int)X.size(1); a.N = (int)dY.size(1); a.K = (int)X.size(0);
+    a.a_kcontig = false; a.b_kcontig = false; a.c_bf16 = false;
+    a.colsum = cs.data_ptr<float>();
+    a.epilogue = kEpiWire;
+    a.split_k = (int)split;
+    a.tile_bm = a.tile_bn = 256;
+    a.workspace = workspace.data_ptr<float>() + ws_off;
+    ws_off += gemm_wgrad_splitk_group_ws(a, (int)split);
+    set_wire(a, wires[i], wire_shards[i], wire_owns[i], wire_codec, wire_periods[i], wire_offs[i], upd_masters[i],
+             upd_lps[i], upd_moms[i], sgd);
+  }
+  TORCH_CHECK(workspace.numel() >= ws_off, "gemm_wgrad_splitk_group: workspace of ", ws_off, " floats needed");
+  TORCH_CHECK(gemm_wgrad_splitk_group_supported(g.data(), (int)n, (int)split),
+              "gemm_wgrad_splitk_group: unsupported (M, N % 256, K % (64 * split), aligned operands, the fused update on "
+              "every problem or none)");
+  launch_gemm_wgrad_splitk_group(g.data(), (int)n, (int)split, fan_stream());
+}
+
+// The shape limits of gemm_wgrad_splitk_group for problems (M, N, K) at a common split (operands assumed aligned).
+bool gemm_wgrad_splitk_group_shapes_ok(const std::vector<std::tuple<int64_t, int64_t, int64_t>>& mnk, int64_t split) {
+  std::vector<GemmArgs> g(mnk.size());
+  for (size_t i = 0; i < mnk.size(); ++i) {
+    GemmArgs& a = g[i];
+    a.M = (int)std::get<0>(mnk[i]);
+    a.N = (int)std::get<1>(mnk[i]);
+    a.K = (int)std::get<2>(mnk[i]);
+    a.lda = a.M;
+    a.ldb = a.ldc = a.N;
+    a.epilogue = kEpiWire;
+    a.A = a.B = a.C = a.workspace = (void*)16;
+    a.colsum = (float*)16;
+    a.wire = (uint8_t*)16;
+    a.wire_shard = 256;
+  }
+  return gemm_wgrad_splitk_group_supported(g.data(), (int)g.size(), (int)split);
+}
+
+int64_t gemm_wgrad_splitk_group_ws_floats(const std::vector<std::pair<int64_t, int64_t>>& mn, int64_t split) {
+  int64_t w = 0;
+  for (const auto& p : mn) w += split * (p.first * p.second + p.second);
+  return w;
 }
 
 // The GEMMs of one MLP pass as ONE persistent launch (gemm_chain.h). kind 0 (forward): A0 = X [M][K0], Bs[i] = W_i
@@ -353,6 +445,25 @@ void register_gemm(pybind11::module_& m) {
         pybind11::arg("wire_shard") = 0, pybind11::arg("wire_own") = -1, pybind11::arg("wire_codec") = 1,
         pybind11::arg("wire_period") = 0);
   m.def("gemm_wgrad_group_ws", &gemm_wgrad_group_ws_floats, "f32 workspace elements for a group of (M, N) problems");
+  m.def("gemm_wgrad_splitk_group", &gemm_wgrad_splitk_group,
+        "up to 8 bwd-weight GEMMs (256x256 tiles, wire epilogue or fused update) at one split-K count in one "
+        "dispatch + one slab reduce",
+        pybind11::arg("Xs"), pybind11::arg("dYs"), pybind11::arg("Cs"), pybind11::arg("colsums"),
+        pybind11::arg("split"), pybind11::arg("workspace"), pybind11::arg("wires"), pybind11::arg("wire_shards"),
+        pybind11::arg("wire_owns"), pybind11::arg("wire_periods"), pybind11::arg("wire_offs"),
+        pybind11::arg("wire_codec"), pybind11::arg("upd_masters"), pybind11::arg("upd_lps"),
+        pybind11::arg("upd_moms"), pybind11::arg("upd_lr") = 0.0, pybind11::arg("upd_grad_scale") = 1.0,
+        pybind11::arg("upd_weight_decay") = 0.0, pybind11::arg("upd_momentum") = 0.0,
+        pybind11::arg("upd_nesterov") = false);
+  m.def("gemm_wgrad_splitk_group_supported", &gemm_wgrad_splitk_group_shapes_ok,
+        "shape limits of gemm_wgrad_splitk_group for (M, N, K) problems at a common split", pybind11::arg("mnk"),
+        pybind11::arg("split"));
+  m.def("gemm_wgrad_splitk_group_ws", &gemm_wgrad_splitk_group_ws_floats,
+        "f32 workspace elements for a split-K group of (M, N) problems", pybind11::arg("mn"), pybind11::arg("split"));
+  m.def("gemm_plan_overridden", [](int64_t M, int64_t N, int64_t K) {
+          return gemm_bf16_plan_overridden((int)M, (int)N, (int)K);
+        },
+        "the automatic plan of this shape comes from FAN_GEMM_PLAN or the measured table");
   m.def("gemm_chain", &gemm_chain, "the GEMMs of one MLP pass as one persistent launch (row-panel hand-offs)",
         pybind11::arg("kind"), pybind11::arg("A0"), pybind11::arg("Bs"), pybind11::arg("Cs"), pybind11::arg("biases"),
         pybind11::arg("auxes"), pybind11::arg("epis"), pybind11::arg("counters"), pybind11::arg("dry_run") = false);

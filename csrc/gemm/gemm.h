@@ -80,6 +80,8 @@ struct GemmPlan {
 
 // Tile / split-K choice for a shape (split_k <= 0: automatic).
 GemmPlan gemm_bf16_plan(int M, int N, int K, int split_k, int tile_bm = 0, int tile_bn = 0, int tile_waves = 0);
+// True when the automatic plan of this shape comes from a FAN_GEMM_PLAN entry or the measured table, not the rule.
+bool gemm_bf16_plan_overridden(int M, int N, int K);
 
 // Returns false if the shape is not supported by the MFMA path (caller must then error out).
 bool gemm_bf16_supported(const GemmArgs& a);

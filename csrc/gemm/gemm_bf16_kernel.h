@@ -1756,23 +1756,12 @@ __device__ __forceinline__ void local_update4(float v[4], uint32_t E, uint32_t f
 // grid's thread count too, so a quad's lanes are always all in or all out of range.)
 // QCS: the launch also runs bias-gradient reduces that earlier fused-update GEMMs of the stream queued (qcs, in its
 // first qcs.first[qcs.n] blocks: one launch less per queued reduce, GemmArgs::defer_colsum).
-template <bool UPD, int SK = 0, bool QCS = false>
-__global__ void __launch_bounds__(256)
-    splitk_reduce_wire4_kernel(const float* __restrict__ ws, int split_k, float* __restrict__ C, int64_t ldc, int M,
-                               int N, float* __restrict__ colsum, WireOut wo, ColsumGroup qcs) {
-  int bid = (int)blockIdx.x, nb = (int)gridDim.x;
-  if constexpr (QCS) {
-    const int nq = qcs.first[qcs.n];
-    if (bid < nq) {
-      int i = 0;
-      while (i + 1 < qcs.n && bid >= qcs.first[i + 1]) ++i;
-      colsum_reduce_block<true, true>(qcs.part[i], qcs.parts[i], qcs.colsum[i], qcs.N[i], qcs.wo[i],
-                                      bid - qcs.first[i]);
-      return;
-    }
-    bid -= nq;
-    nb -= nq;
-  }
+// (the body: blocks bid of nb reduce one GEMM's slabs; the kernels below give it their own or a problem's block range)
+template <bool UPD, int SK>
+__device__ __forceinline__ void splitk_reduce_wire4_run(const float* __restrict__ ws, int split_k,
+                                                        float* __restrict__ C, int64_t ldc, int M, int N,
+                                                        float* __restrict__ colsum, const WireOut& wo, int bid,
+                                                        int nb) {
   if constexpr (SK > 0) split_k = SK;
   const int64_t slab = (int64_t)M * N, quads = slab / 4;
   const int64_t t0 = bid * (int64_t)blockDim.x + threadIdx.x, step = (int64_t)nb * blockDim.x;
@@ -1832,6 +1821,58 @@ __global__ void __launch_bounds__(256)
       if (wo.bias_off > 0) wire_store16<UPD>(v, (uint32_t)wo.bias_off + (uint32_t)col, wo);
     }
   }
+}
+
+// the queued bias-gradient reduces of a launch's first qcs.first[qcs.n] blocks (QCS); false: bid is past them
+__device__ __forceinline__ bool queued_colsum_block(const ColsumGroup& qcs, int bid) {
+  if (bid >= qcs.first[qcs.n]) return false;
+  int i = 0;
+  while (i + 1 < qcs.n && bid >= qcs.first[i + 1]) ++i;
+  colsum_reduce_block<true, true>(qcs.part[i], qcs.parts[i], qcs.colsum[i], qcs.N[i], qcs.wo[i], bid - qcs.first[i]);
+  return true;
+}
+
+template <bool UPD, int SK = 0, bool QCS = false>
+__global__ void __launch_bounds__(256)
+    splitk_reduce_wire4_kernel(const float* __restrict__ ws, int split_k, float* __restrict__ C, int64_t ldc, int M,
+                               int N, float* __restrict__ colsum, WireOut wo, ColsumGroup qcs) {
+  int bid = (int)blockIdx.x, nb = (int)gridDim.x;
+  if constexpr (QCS) {
+    if (queued_colsum_block(qcs, bid)) return;
+    bid -= qcs.first[qcs.n];
+    nb -= qcs.first[qcs.n];
+  }
+  splitk_reduce_wire4_run<UPD, SK>(ws, split_k, C, ldc, M, N, colsum, wo, bid, nb);
+}
+
+// The slab reduces of a grouped split-K launch (gemm_group.hip launch_gemm_wgrad_splitk_group) in ONE launch: problem
+// i's blocks [first[i], first[i + 1]) run splitk_reduce_wire4_kernel's body on its slabs (each value summed, encoded,
+// rounded and updated as there: bit-identical to one launch per problem), after the queued bias-gradient reduces'
+// blocks (QCS).
+struct SlabGroup {
+  const float* ws[kMaxGroup];
+  float* C[kMaxGroup];
+  float* colsum[kMaxGroup];
+  int64_t ldc[kMaxGroup];
+  WireOut wo[kMaxGroup];
+  int M[kMaxGroup];
+  int N[kMaxGroup];
+  int first[kMaxGroup + 1];
+  int n;
+};
+
+template <bool UPD, int SK, bool QCS = false>
+__global__ void __launch_bounds__(256) splitk_reduce_wire4_group_kernel(SlabGroup g, ColsumGroup qcs) {
+  static_assert(SK > 0, "grouped slab reduce: compile-time split count");
+  int bid = (int)blockIdx.x;
+  if constexpr (QCS) {
+    if (queued_colsum_block(qcs, bid)) return;
+    bid -= qcs.first[qcs.n];
+  }
+  int i = 0;
+  while (i + 1 < g.n && bid >= g.first[i + 1]) ++i;  // workgroup-uniform
+  splitk_reduce_wire4_run<UPD, SK>(g.ws[i], SK, g.C[i], g.ldc[i], g.M[i], g.N[i], g.colsum[i], g.wo[i],
+                                   bid - g.first[i], g.first[i + 1] - g.first[i]);
 }
 
 // Ordered reduce of bias-gradient partial slabs part[p * N + n], p < parts, into colsum[n]; WIRE: also encodes the

@@ -303,6 +303,14 @@ GemmPlan gemm_bf16_plan(int M, int N, int K, int split_k, int tile_bm, int tile_
   return p;
 }
 
+bool gemm_bf16_plan_overridden(int M, int N, int K) {
+  for (const TunedPlan& t : env_plans().plans)
+    if (t.M == M && t.N == N && t.K == K) return true;
+  for (const TunedPlan& t : kTuned)
+    if (t.M == M && t.N == N && t.K == K) return true;
+  return false;
+}
+
 bool gemm_bf16_supported(const GemmArgs& a) {
   const GemmPlan p = gemm_bf16_plan(a.M, a.N, a.K, a.split_k, a.tile_bm, a.tile_bn, a.tile_waves);
   if (p.bm == 0) return false;

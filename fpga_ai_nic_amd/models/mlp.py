@@ -210,17 +210,18 @@ class MLP:
         if self._relu_at(self.L - 1):  # ReLU on the classifier output (reference fuse_type 2/3)
             self.dz[self.L].mul_(self.logits > 0)
 
-    def backward_weight(self, i: int, wire=None, update=None, defer_colsum=False):
+    def backward_weight(self, i: int, wire=None, update=None, defer_colsum=False, split_k=None, tile=None):
         """dW (+ db) of layer i into the gradient bucket. ``wire`` (GPU bf16 only): the all-reduce engine's
         prepack target — dW is BFP-encoded straight into the wire shards by the GEMM epilogue. ``update`` (with
         ``wire``, single-rank engine): a :class:`~fpga_ai_nic_amd.ops.gemm.LocalUpdate` — the epilogue applies the
         decoded gradient to this layer's weights in place instead of storing the wire (the layer's bwd-data GEMM,
         which reads the weights, must already be enqueued). ``defer_colsum`` (with ``update``): the bias part may be
-        queued on the stream (ops/gemm.py :func:`~fpga_ai_nic_amd.ops.gemm.flush_colsum` completes it)."""
+        queued on the stream (ops/gemm.py :func:`~fpga_ai_nic_amd.ops.gemm.flush_colsum` completes it).
+        ``split_k`` / ``tile`` (with ``wire``): an explicit plan."""
         l = self.layers[i]
         if wire is not None:
             G.linear_bwd_weight(self.act[i], self.dz[i + 1], l.gw, bias_grad=l.gb if self.bias else None, wire=wire,
-                                update=update, defer_colsum=defer_colsum)
+                                update=update, defer_colsum=defer_colsum, split_k=split_k, tile=tile)
         elif not self.bias:
             G.linear_bwd_weight(self.act[i], self.dz[i + 1], l.gw)
         elif l.gw.is_cuda and self.dtype == torch.bfloat16:  # bias gradient fused into the bwd-weight GEMM
@@ -228,6 +229,19 @@ class MLP:
         else:
             G.linear_bwd_weight(self.act[i], self.dz[i + 1], l.gw)
             NN.col_sum(self.dz[i + 1], l.gb)
+
+    def wgrad_problem(self, i: int):
+        """Layer i's bwd-weight operands (X, dY) for the grouped launch's planning (ops/gemm.py wgrad_group_split)."""
+        return self.act[i], self.dz[i + 1]
+
+    def backward_weight_group(self, items, split: int):
+        """The wire bwd-weight GEMMs of several layers, ``items`` = [(i, wire, update)], as ONE grouped launch at the
+        common split-K count ``split`` and one slab reduce (ops/gemm.py gemm_wgrad_splitk_group): what
+        :meth:`backward_weight` does per layer with ``tile=(256, 256), split_k=split``, bit-identical. Models with
+        bias only (the grouped kernel carries the fused bias gradient); every layer's bwd-data GEMM must already be
+        enqueued when ``update`` is given."""
+        G.gemm_wgrad_splitk_group([(self.act[i], self.dz[i + 1], self.layers[i].gw, self.layers[i].gb, wire, update)
+                                   for i, wire, update in items], split)
 
     def backward_data(self, i: int):
         if i == 0:

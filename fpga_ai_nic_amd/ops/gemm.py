@@ -164,6 +164,75 @@ def gemm_wgrad_group(problems, wire=None):
         Cx.gemm_wgrad_group(Xs, dYs, Cs, css, offs, ws, buf, int(shard), int(own), int(codec), int(period))
 
 
+def wgrad_static_split(x, dz) -> int:
+    """The split-K count of a wire bwd-weight GEMM (x [K][M], dz [K][N], with the fused bias gradient) when it would
+    run the planner rule's 256x256 split-K plan, else 0: a ``FAN_GEMM_PLAN`` entry, the measured plan table or the
+    tuner (a decision for the shape other than that plan, or a shape it would still tune) overrides the rule."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and dz.dtype == torch.bfloat16):
+        return 0
+    Cx = _ext.require()
+    K, M, N = x.shape[0], x.shape[1], dz.shape[1]
+    static = tuple(Cx.gemm_plan(M, N, K, 0, 0, 0, 0))
+    if static[:2] != (256, 256) or static[2] <= 1 or Cx.gemm_plan_overridden(M, N, K):
+        return 0
+    from . import gemm_tune
+
+    T = gemm_tune.tuner()
+    if T.enabled:
+        plan = T.lookup(T.key(M, N, K, True, False, EPI_WIRE, True, 1, x.device))
+        if plan is None:
+            if T.worth_tuning(M, N, static, x.device):
+                return 0
+        elif tuple(plan) != static[:3]:
+            return 0
+    return int(static[2])
+
+
+def wgrad_group_split(problems, cus: int = 256) -> int:
+    """The common split-K count at which the bwd-weight GEMMs ``(x, dz, ...)`` run as one grouped launch
+    (:func:`gemm_wgrad_splitk_group`): the smallest power of two s whose s * (256x256 tiles of the group) reach the
+    CU count, within the planner's limits for a split (K % (64 s) == 0, K / s >= 1024) and the launcher's (s 2 or 4,
+    2 to 8 problems). 0: no such s (or a lone problem) — the caller launches the GEMMs one by one."""
+    if not 2 <= len(problems) <= 8:
+        return 0
+    tiles = sum((p[0].shape[1] // 256) * (p[1].shape[1] // 256) for p in problems)
+    s = 1
+    while s * tiles < cus:
+        s *= 2
+    if s not in (2, 4) or any(p[0].shape[0] % (64 * s) or p[0].shape[0] // s < 1024 for p in problems):
+        return 0
+    mnk = [(p[0].shape[1], p[1].shape[1], p[0].shape[0]) for p in problems]
+    return s if _ext.require().gemm_wgrad_splitk_group_supported(mnk, s) else 0
+
+
+def gemm_wgrad_splitk_group(problems, split: int):
+    """2 to 8 wire bwd-weight GEMMs in ONE dispatch at the common split-K count ``split`` (2 or 4) and ONE slab
+    reduce: for each ``(X, dY, C, colsum, wire, update)`` what :func:`linear_bwd_weight` does with
+    ``tile=(256, 256), split_k=split`` — bit-identical outputs (csrc/gemm/gemm_group.hip
+    launch_gemm_wgrad_splitk_group). ``wire`` as in :func:`gemm` (one codec for the group); ``update`` a
+    :class:`LocalUpdate` for every problem (with the same hyper-parameters) or None for every problem. The reduce
+    also runs the bias-gradient reduces queued on the stream (``defer_colsum``)."""
+    Cx = _ext.require()
+    Xs, dYs, Cs, css = ([p[i] for p in problems] for i in range(4))
+    wires = [tuple(p[4]) + (0, 0)[len(p[4]) - 4:] for p in problems]
+    upds = [p[5] if len(p) > 5 else None for p in problems]
+    if len({int(w[3]) for w in wires}) != 1:
+        raise ValueError("gemm_wgrad_splitk_group: one wire codec for the group")
+    u0 = upds[0]
+    hyper = lambda u: (u.lr, u.grad_scale, u.weight_decay, u.momentum, u.nesterov)  # noqa: E731
+    if any((u is None) != (u0 is None) or (u is not None and hyper(u) != hyper(u0)) for u in upds):
+        raise ValueError("gemm_wgrad_splitk_group: the fused update on every problem (same hyper-parameters) or none")
+    ws = _workspace(Cs[0].device, Cx.gemm_wgrad_splitk_group_ws([(x.shape[1], y.shape[1]) for x, y in zip(Xs, dYs)],
+                                                                int(split)))
+    kw = {} if u0 is None else dict(upd_lr=u0.lr, upd_grad_scale=u0.grad_scale, upd_weight_decay=u0.weight_decay,
+                                    upd_momentum=u0.momentum, upd_nesterov=u0.nesterov)
+    Cx.gemm_wgrad_splitk_group(Xs, dYs, Cs, css, int(split), ws, [w[0] for w in wires], [int(w[1]) for w in wires],
+                               [int(w[2]) for w in wires], [int(w[4]) for w in wires], [int(w[5]) for w in wires],
+                               int(wires[0][3]), [None if u is None else u.master for u in upds],
+                               [None if u is None else u.lp for u in upds],
+                               [None if u is None else u.mom for u in upds], **kw)
+
+
 def _aligned16(C, bias, aux) -> bool:
     """A bf16 output's epilogue stores (and the bias / activation loads beside them) are 16 B per lane."""
     ok = C.data_ptr() % 16 == 0 and C.stride(0) % 8 == 0
@@ -371,12 +440,14 @@ def linear_bwd_data(dz, w, out, relu_input=None):
     return gemm(dz, False, w, True, out, EPI_NONE)
 
 
-def linear_bwd_weight(x, dz, out, accumulate=False, bias_grad=None, wire=None, update=None, defer_colsum=False):
+def linear_bwd_weight(x, dz, out, accumulate=False, bias_grad=None, wire=None, update=None, defer_colsum=False,
+                      split_k=None, tile=None):
     """dW = Xᵀ · dZ (f32 out); with ``bias_grad`` also db = colsum(dZ), fused into the same kernel; with
     ``wire`` dW is written BFP-encoded into the all-reduce wire buffer instead (see :func:`gemm`); with ``update``
     (single-rank engine) the encoded dW updates the weights in place instead (``defer_colsum``: the bias part
-    queued, see :func:`gemm`)."""
+    queued, see :func:`gemm`). ``split_k`` / ``tile``: an explicit plan (see :func:`gemm`)."""
     if wire is not None:
         return gemm(x, True, dz, False, out, EPI_WIRE, colsum=bias_grad, wire=wire, update=update,
-                    defer_colsum=defer_colsum)
-    return gemm(x, True, dz, False, out, EPI_NONE, accumulate=accumulate, colsum=bias_grad)
+                    defer_colsum=defer_colsum, split_k=split_k, tile=tile)
+    return gemm(x, True, dz, False, out, EPI_NONE, accumulate=accumulate, colsum=bias_grad, split_k=split_k,
+                tile=tile)

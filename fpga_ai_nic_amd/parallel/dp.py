@@ -19,7 +19,7 @@ import torch
 
 from ..models.mlp import MLP
 from ..ops import gemm as G
-from ..ops import wire
+from ..ops import gemm_tune, wire
 from ..utils import tracing
 from .allreduce import CompressedAllReduce, Handle, _round_up
 from .transport import Transport
@@ -79,7 +79,7 @@ class DataParallelTrainer:
                  weight_decay: float = 0.0, momentum: float = 0.0, nesterov: bool = False,
                  loss_scale: float = 1.0, average: bool = True, profile: bool = False, prepack: bool = True,
                  commit_at_end: bool | None = None, fused_update: bool | None = None,
-                 gemm_inflight: str | None = None):
+                 gemm_inflight: str | None = None, wgrad_pair: bool | str | None = None):
         """``fused_update`` (default env FAN_FUSED_UPDATE, else on): with a single-rank engine (world 1, requests
         inline: the all-reduce of one rank is the identity) and the GEMM-encoded wire, the bwd-weight GEMM's epilogue
         takes each encoded gradient group through its BFP round trip in registers and applies the SGD update to the
@@ -92,7 +92,13 @@ class DataParallelTrainer:
         looping over tiles — it holds every CU until it ends, so the comm stream's kernels start only at GEMM
         boundaries; 'grid': one workgroup per tile from the first submit to the end of backward, so comm kernels
         start at tile boundaries (the forced 1-rank path's comm phase took half the device time that way,
-        profiles/r3_persist_vs_tile_grid_forced.txt). bench.py picks between them by timing both at world > 1."""
+        profiles/r3_persist_vs_tile_grid_forced.txt). bench.py picks between them by timing both at world > 1.
+
+        ``wgrad_pair`` (default env FAN_WGRAD_PAIR, else on; fused update only): the bwd-weight GEMMs whose plan is
+        the planner rule's 256x256 split-K one (the narrow layers: too few tiles to fill the CUs unsplit) are
+        postponed to the end of the backward and run as ONE grouped launch at a smaller common split with ONE slab
+        reduce (models/mlp.py backward_weight_group). False: each in its layer's turn. 'single' (tests, A/B):
+        postponed alike, but launched one by one at the group's split — the grouped launch is bit-identical to it."""
         self.m = model
         self.engine = engine
         self.world = engine.world if engine is not None else 1
@@ -124,6 +130,12 @@ class DataParallelTrainer:
         # a split-K classifier GEMM leaves its slabs to the softmax-xent kernel, which folds them (FAN_FOLD_LOGITS=0:
         # the GEMM's own slab reduce launch; bit-identical either way)
         self.fold_logits = os.environ.get("FAN_FOLD_LOGITS", "1") != "0"
+        wp = os.environ.get("FAN_WGRAD_PAIR", "1") != "0" if wgrad_pair is None else wgrad_pair
+        if wp not in (True, False, "single"):
+            raise ValueError(f"wgrad_pair must be True|False|'single', got {wgrad_pair!r}")
+        self.wgrad_pair = wp
+        self.wgrad_groups = 0  # grouped bwd-weight launches so far
+        self._wgrad_plan = (None, [], 0)
         # layer-chain launches (ops/gemm.py linear_chain, FAN_GEMM_CHAIN): the forward at every world size; the
         # bwd-data chain only with the fused world-1 update — with a multi-rank engine each layer's all-reduce is
         # issued right after its own bwd-weight GEMM and overlaps that layer's bwd-data GEMM, which a chain of the
@@ -223,6 +235,9 @@ class DataParallelTrainer:
                  if self.prepack and l.cout % 16 == 0 else None) for l in m.layers]
         chained = (self.fused_update and self.chain_bwd and all(t is not None for t in tgts)
                    and m.backward_data_chain())
+        # (with or without the bwd-data chain: the two schedules stay bit-identical, tests/test_gpu_gemm_chain.py)
+        post, split = self._wgrad_postponed(tgts)
+        late = []  # the postponed layers' (i, wire, update), in the backward's order
         try:
             for i in reversed(range(m.L)):
                 l = m.layers[i]
@@ -240,7 +255,10 @@ class DataParallelTrainer:
                                             weight_decay=self.wd, momentum=self.momentum, nesterov=self.nesterov)
                         # (the bwd-weight GEMMs of layers >= 1 on a second stream, beside the next GEMM, measured 1.5-2 %
                         # slower: profiles/r3_fused_update_ab.txt)
-                        m.backward_weight(i, wire=tgt, update=upd, defer_colsum=self.defer_colsum)
+                        if i in post:
+                            late.append((i, tgt, upd))
+                        else:
+                            m.backward_weight(i, wire=tgt, update=upd, defer_colsum=self.defer_colsum)
                         self.fused_updates += 1
                     else:
                         m.backward_weight(i, wire=tgt)
@@ -269,6 +287,15 @@ class DataParallelTrainer:
                     self.times["bwd_first"] += t1 - t0
                     self.times["bwd"] += t1 - t0
                     t0 = t1
+            if late and self.wgrad_pair == "single":
+                for i, tgt, upd in late:
+                    m.backward_weight(i, wire=tgt, update=upd, split_k=split, tile=(256, 256))
+            elif late:
+                # every layer's bwd-data GEMM is enqueued (the updates are in place); the reduce of this launch also
+                # runs the bias-gradient reduces the unsplit layers queued
+                with tracing.range("bwd_wgrad_group"):
+                    m.backward_weight_group(late, split)
+                self.wgrad_groups += 1
         finally:
             # the bias updates still queued (every layer's lands before the next forward; after an exception too, so
             # no queued reduce is left for an unrelated later GEMM of the stream to run)
@@ -288,6 +315,24 @@ class DataParallelTrainer:
         if prof:
             self._sync()
             self.times["bwd"] += time.perf_counter() - t0
+
+    def _wgrad_postponed(self, tgts):
+        """The layers whose bwd-weight GEMM is postponed into the grouped launch that ends the backward, and its
+        common split (([], 0): none). World 1 with the fused update only — with a multi-rank engine a postponed layer
+        would delay its all-reduce. A layer qualifies when its GEMM would run the planner rule's 256x256 split-K plan
+        (ops/gemm.py wgrad_static_split); the group needs two or more of them and a common split within the
+        planner's limits (wgrad_group_split), which holds from 4096 rows upward for 1024-wide layers."""
+        m = self.m
+        if not (self.wgrad_pair and self.fused_update and self.cuda and m.bias):
+            return [], 0
+        # (decided once per batch size and state of the tuner's decisions, not per step)
+        T = gemm_tune.tuner()
+        key = (m.act[0].shape[0], tuple(t is not None for t in tgts), id(T), T.enabled, len(T.plans))
+        if self._wgrad_plan[0] != key:
+            post = [i for i in range(m.L) if tgts[i] is not None and G.wgrad_static_split(*m.wgrad_problem(i)) > 1]
+            split = G.wgrad_group_split([m.wgrad_problem(i) for i in post])
+            self._wgrad_plan = (key, post if split else [], split)
+        return self._wgrad_plan[1:]
 
     def _gemm_grid(self, on: bool):
         """gemm_inflight='grid': GEMMs enqueued while a request is in flight run one workgroup per tile."""
