@@ -46,7 +46,8 @@ _LINEARS = (("ffn_out", "output.dense", bert.FFN, bert.HIDDEN), ("ffn_in", "inte
             ("qkv", "attention.self.qkv", bert.HIDDEN, 3 * bert.HIDDEN))
 
 
-def measure(eng, dev, world, tokens=4096, layers=12, rounds=5, only="", last_on_producer=True, group_wgrad=None):
+def measure(eng, dev, world, tokens=4096, layers=12, rounds=5, only="", last_on_producer=True, group_wgrad=None,
+            optimizer="sgd"):
     """Config 5 on an engine: a BERT-base backward whose gradients ARE the all-reduce's input. Per encoder layer (last
     first) the four projections' bwd-data GEMM (bf16 dX) and bwd-weight GEMM run on the compute stream; each
     bwd-weight GEMM writes its dW — and, fused, its bias gradient — straight into the layer's gradient bucket, BFP-
@@ -57,7 +58,8 @@ def measure(eng, dev, world, tokens=4096, layers=12, rounds=5, only="", last_on_
     bucket last, where a real backward produces them (their producers — the pooler's tiny GEMM, the embedding
     scatter-add — are modelled as the encode of their buckets). Timed as compute only (GEMMs + encodes), comm only
     (the all-reduces of the encoded buckets) and both; medians over ``rounds`` (max over ranks). Also called by
-    bench.py (``extra.config5``)."""
+    bench.py (``extra.config5``). ``optimizer='adamw'``: every bucket's update is AdamW (two moment planes per bucket,
+    the step count advancing per round) instead of plain SGD."""
     from fpga_ai_nic_amd import _ext
 
     C = _ext.require()
@@ -79,6 +81,9 @@ def measure(eng, dev, world, tokens=4096, layers=12, rounds=5, only="", last_on_
         tgt = eng.prepack_target(g, b.numel) if getattr(eng, "prepack", False) else None
         prepacked_buckets += tgt is not None
         bufs.append((b, g, w, w.to(torch.bfloat16), L, tgt, _offsets(b)))
+    adam = optimizer == "adamw"
+    moments = [(torch.zeros_like(w), torch.zeros_like(w)) if adam else None for _, _, w, *_ in bufs]
+    steps = [0] * len(bufs)
 
     def encode_range(g, tgt, lo, hi):
         if tgt is not None and hi > lo:
@@ -125,6 +130,11 @@ def measure(eng, dev, world, tokens=4096, layers=12, rounds=5, only="", last_on_
             # the backward's last bucket (embeddings): nothing left to overlap it with, so on the compute stream (the
             # trainer's schedule, dp.py last_on_producer)
             kw["on_producer"] = True
+        if adam:
+            steps[bi] += 1
+            return eng.allreduce_sgd(g, w, lp, moments[bi][0], n_valid=b.numel, lr=1e-4, grad_scale=1.0 / world,
+                                     name=b.name, opt="adamw", var=moments[bi][1], weight_decay=1e-2, step=steps[bi],
+                                     **kw)
         return eng.allreduce_sgd(g, w, lp, n_valid=b.numel, lr=1e-4, grad_scale=1.0 / world, name=b.name, **kw)
 
     enq = {}
@@ -182,6 +192,8 @@ def main():
     ap.add_argument("--engine", default="native", choices=["python", "native"])
     ap.add_argument("--forced", action="store_true",
                     help="world 1 through the multi-rank path (1-rank RCCL group, sharded update: bench.py extra.config5)")
+    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw"],
+                    help="the update fused into every bucket's all-reduce")
     ap.add_argument("--only", default="", choices=["", "compute", "comm", "overlap"],
                     help="profiling: run only rounds of this kind (one kernel trace per kind, for tools/overlap_report.py)")
     a = ap.parse_args()
@@ -204,10 +216,12 @@ def main():
         if world == 1:  # force the side-stream path so the overlap is real even on one GPU
             eng.inline = False
             eng.stream = torch.cuda.Stream(priority=-1)
-    r = measure(eng, dev, world, tokens=a.tokens, layers=a.layers, rounds=a.rounds, only=a.only)
+    r = measure(eng, dev, world, tokens=a.tokens, layers=a.layers, rounds=a.rounds, only=a.only,
+                optimizer=a.optimizer)
     if rank == 0:
         print(json.dumps({"bench": "bert_base_bwd_overlap", "n_gpus": world, "compress": a.compress,
-                          "engine": a.engine, "algo": a.algo, **r, "only": a.only or None}), flush=True)
+                          "engine": a.engine, "algo": a.algo, "optimizer": a.optimizer, **r, "only": a.only or None}),
+              flush=True)
     D.cleanup()
 
 

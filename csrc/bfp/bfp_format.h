@@ -36,6 +36,35 @@ struct SgdParams {
   int nesterov;
 };
 
+// AdamW (decoupled decay, bias correction) of the update kernels. The per-step scalars are computed on the host in
+// float64 and rounded once to f32 (ops/bfp_oracle.py adamw_scalars): omb1 = 1 - beta1, omb2 = 1 - beta2,
+// step_size = lr / (1 - beta1^t), rsbc2 = 1 / sqrt(1 - beta2^t), decay = 1 - lr * wd. `var` is the second-moment
+// plane (the first moment travels in the launchers' `mom`), at the same flat indices as master. A struct of its own:
+// SgdParams is embedded in the GEMM kernels' argument block and stays as it is.
+struct AdamWParams {
+  float grad_scale;
+  float beta1, omb1;
+  float beta2, omb2;
+  float step_size;
+  float rsbc2;
+  float eps;
+  float weight_decay;  // only tested against 0: the decay itself is `decay`
+  float decay;
+  float* var;
+};
+
+// One element's AdamW step, all f32, in the order bfp_oracle.adamw emulates (change both together):
+//   g = g * grad_scale; m' = fma(beta1, m, omb1 * g); v' = fma(beta2, v, (omb2 * g) * g)
+//   d = fma(sqrt(v'), rsbc2, eps); w' = fma(-step_size, m' / d, wd != 0 ? w * decay : w)
+// `/` and sqrtf are the correctly rounded forms (v_div_scale / v_div_fmas / v_div_fixup; v_sqrt_f32 + refinement).
+__device__ __forceinline__ void adamw_update(const AdamWParams& p, float g, float& w, float& m, float& v) {
+  g = g * p.grad_scale;
+  m = fmaf(p.beta1, m, p.omb1 * g);
+  v = fmaf(p.beta2, v, (p.omb2 * g) * g);
+  const float d = fmaf(sqrtf(v), p.rsbc2, p.eps);
+  w = fmaf(-p.step_size, m / d, p.weight_decay != 0.0f ? w * p.decay : w);
+}
+
 __host__ __device__ inline size_t wire_shard_bytes(int codec, size_t n_s) {
   switch (codec) {
     case kBfpTrunc:
@@ -299,6 +328,10 @@ void launch_wire_reduce(int codec, int local_dtype, const void* slots, size_t sl
 void launch_wire_sgd(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
                      float* master, bf16_t* lp, float* mom, SgdParams p, size_t n_valid, hipStream_t stream,
                      size_t shard_stride = 0);
+// launch_wire_sgd with the AdamW step: `mom` is the first moment, p.var the second, both required.
+void launch_wire_adamw(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
+                       float* master, bf16_t* lp, float* mom, AdamWParams p, size_t n_valid, hipStream_t stream,
+                       size_t shard_stride = 0);
 // Decode to f32/bf16 from a strided wire (as launch_wire_sgd's shard_stride).
 void launch_wire_unpack_strided(int codec, int out_dtype, const void* in, size_t shard_stride, void* out, size_t n_s,
                                 int n_shards, hipStream_t stream);
@@ -320,6 +353,12 @@ void launch_wire_reduce_to(int codec, int local_dtype, const void* slots, size_t
 void launch_wire_reduce_sgd(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots,
                             int self_pos, const void* local, float* master, float* mom, SgdParams p, size_t n_valid,
                             const WirePtrs& dst, int n_dst, size_t n_s, bool peers, hipStream_t stream);
+// launch_wire_reduce_sgd with the AdamW step (`mom` / p.var: this shard's moment planes, both required):
+// bit-identical to wire_reduce (re-encode) + wire_adamw.
+void launch_wire_reduce_adamw(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots,
+                              int self_pos, const void* local, float* master, float* mom, AdamWParams p,
+                              size_t n_valid, const WirePtrs& dst, int n_dst, size_t n_s, bool peers,
+                              hipStream_t stream);
 // BFP codecs: the lane-contiguous form of that kernel, 4 values per lane (1, default) or one 16-value group per lane
 // (0) (FAN_WIRE_REDUCE4); bit-identical either way
 void set_wire_reduce4(int on);

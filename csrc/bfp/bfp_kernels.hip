@@ -12,11 +12,14 @@
 //   wire_reduce  = the ring engine's 8-lane fadd stage + re-encode (hw/all_reduce.sv:1090-1183)
 //   wire_sgd     = weight_update FFMA w' = fma(-lr, g, w) (hw/weight_update.sv:433-452), fused
 //                  into the all-gather epilogue so weights never take an extra HBM round trip.
+//   AdamW        = no counterpart in the reference (its update unit is one FFMA): the same three update kernels
+//                  instantiated with AdamWParams run adamw_update (bfp_format.h) per value, with a second moment plane.
 #include "bfp/bfp_format.h"
 
 #include <algorithm>
 #include <atomic>
 #include <cstring>
+#include <type_traits>
 
 namespace fan {
 
@@ -346,11 +349,14 @@ __device__ __forceinline__ void codec_roundtrip16(float v[16]) {
   }
 }
 
-template <typename TL, int C, bool HAS_MOM>
+// P: SgdParams, or AdamWParams (HAS_MOM: mom is the first moment, p.var the second; adamw_update per value).
+template <typename TL, int C, bool HAS_MOM, typename P = SgdParams>
 __global__ void __launch_bounds__(kBlock)
     wire_reduce_sgd_kernel(const uint8_t* __restrict__ slots, size_t slot_stride, int n_slots, int self_pos,
                            const TL* __restrict__ local, float* __restrict__ master, float* __restrict__ mom,
-                           SgdParams p, size_t n_valid, WirePtrs dst, int n_dst, size_t n_s, int rel) {
+                           P p, size_t n_valid, WirePtrs dst, int n_dst, size_t n_s, int rel) {
+  constexpr bool kAdam = std::is_same<P, AdamWParams>::value;
+  static_assert(!kAdam || HAS_MOM, "AdamW needs both moment planes");
   const size_t tasks = n_s >> 4;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
@@ -369,16 +375,25 @@ __global__ void __launch_bounds__(kBlock)
     float w[16], m[16];
     DenseLane16<float>::load16(master, le, w);
     if (HAS_MOM) DenseLane16<float>::load16(mom, le, m);
+    if constexpr (kAdam) {
+      float v2[16];
+      DenseLane16<float>::load16(p.var, le, v2);
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {  // wire_sgd_kernel's operations, in its order
-      if (le + j >= n_valid) continue;
-      float gj = acc[j] * p.grad_scale;
-      if (p.weight_decay != 0.0f) gj = fmaf(p.weight_decay, w[j], gj);
-      if (HAS_MOM) {
-        m[j] = fmaf(p.momentum, m[j], gj);
-        gj = p.nesterov ? fmaf(p.momentum, m[j], gj) : m[j];
+      for (int j = 0; j < 16; ++j)
+        if (le + j < n_valid) adamw_update(p, acc[j], w[j], m[j], v2[j]);
+      if (le < n_valid) DenseLane16<float>::store16(p.var, le, v2);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {  // wire_sgd_kernel's operations, in its order
+        if (le + j >= n_valid) continue;
+        float gj = acc[j] * p.grad_scale;
+        if (p.weight_decay != 0.0f) gj = fmaf(p.weight_decay, w[j], gj);
+        if (HAS_MOM) {
+          m[j] = fmaf(p.momentum, m[j], gj);
+          gj = p.nesterov ? fmaf(p.momentum, m[j], gj) : m[j];
+        }
+        w[j] = fmaf(-p.lr, gj, w[j]);
       }
-      w[j] = fmaf(-p.lr, gj, w[j]);
     }
     if (le < n_valid) {
       DenseLane16<float>::store16(master, le, w);
@@ -395,12 +410,14 @@ __global__ void __launch_bounds__(kBlock)
 // covers contiguous bytes instead of striding a group per lane — the same sums in slot order, the same round trip and
 // SGD per value: bit-identical (FAN_WIRE_REDUCE4, default on). n_s is a multiple of 16 and the grid's thread count a
 // multiple of 4, so a quad's lanes are always all in or all out of range.
-template <typename TL, int C, bool HAS_MOM>
+template <typename TL, int C, bool HAS_MOM, typename P = SgdParams>
 __global__ void __launch_bounds__(kBlock)
     wire_reduce_sgd4_kernel(const uint8_t* __restrict__ slots, size_t slot_stride, int n_slots, int self_pos,
                             const TL* __restrict__ local, float* __restrict__ master, float* __restrict__ mom,
-                            SgdParams p, size_t n_valid, WirePtrs dst, int n_dst, size_t n_s, int rel) {
+                            P p, size_t n_valid, WirePtrs dst, int n_dst, size_t n_s, int rel) {
   static_assert(C == kBfpTrunc || C == kBfpRne, "BFP codecs");
+  constexpr bool kAdam = std::is_same<P, AdamWParams>::value;
+  static_assert(!kAdam || HAS_MOM, "AdamW needs both moment planes");
   const size_t tasks = n_s >> 2;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
@@ -449,16 +466,25 @@ __global__ void __launch_bounds__(kBlock)
       const float4 mv = *reinterpret_cast<const float4*>(mom + le);
       m[0] = mv.x; m[1] = mv.y; m[2] = mv.z; m[3] = mv.w;
     }
+    if constexpr (kAdam) {
+      const float4 vv = *reinterpret_cast<const float4*>(p.var + le);
+      float v2[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {  // wire_sgd_kernel's operations, in its order
-      if (le + j >= n_valid) continue;
-      float gj = acc[j] * p.grad_scale;
-      if (p.weight_decay != 0.0f) gj = fmaf(p.weight_decay, w[j], gj);
-      if (HAS_MOM) {
-        m[j] = fmaf(p.momentum, m[j], gj);
-        gj = p.nesterov ? fmaf(p.momentum, m[j], gj) : m[j];
+      for (int j = 0; j < 4; ++j)
+        if (le + j < n_valid) adamw_update(p, acc[j], w[j], m[j], v2[j]);
+      if (le < n_valid) *reinterpret_cast<float4*>(p.var + le) = make_float4(v2[0], v2[1], v2[2], v2[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {  // wire_sgd_kernel's operations, in its order
+        if (le + j >= n_valid) continue;
+        float gj = acc[j] * p.grad_scale;
+        if (p.weight_decay != 0.0f) gj = fmaf(p.weight_decay, w[j], gj);
+        if (HAS_MOM) {
+          m[j] = fmaf(p.momentum, m[j], gj);
+          gj = p.nesterov ? fmaf(p.momentum, m[j], gj) : m[j];
+        }
+        w[j] = fmaf(-p.lr, gj, w[j]);
       }
-      w[j] = fmaf(-p.lr, gj, w[j]);
     }
     if (le < n_valid) {
       *reinterpret_cast<float4*>(master + le) = make_float4(w[0], w[1], w[2], w[3]);
@@ -488,11 +514,13 @@ __global__ void __launch_bounds__(kBlock) wire_unpack_strided_kernel(const uint8
   }
 }
 
-template <int C, bool HAS_LP, bool HAS_MOM>
+template <int C, bool HAS_LP, bool HAS_MOM, typename P = SgdParams>
 __global__ void __launch_bounds__(kBlock)
     wire_sgd_kernel(const uint8_t* __restrict__ wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
-                    float* __restrict__ master, bf16_t* __restrict__ lp, float* __restrict__ mom, SgdParams p,
+                    float* __restrict__ master, bf16_t* __restrict__ lp, float* __restrict__ mom, P p,
                     size_t n_valid, size_t sb) {
+  constexpr bool kAdam = std::is_same<P, AdamWParams>::value;
+  static_assert(!kAdam || HAS_MOM, "AdamW needs both moment planes");
   // 8 elements per lane here (a read-only wire: the 16-per-lane store layout buys nothing, and the smaller
   // register footprint streams master / lp faster: 33.5 vs 42.5 us on a 16.8 M bucket in the flagship step)
   const size_t tasks = n_s >> 3;
@@ -509,17 +537,30 @@ __global__ void __launch_bounds__(kBlock)
       DenseLane<float>::load8(master, e, w);
       float m[8];
       if (HAS_MOM) DenseLane<float>::load8(mom, e, m);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float gj = g[j] * p.grad_scale;
-        if (p.weight_decay != 0.0f) gj = fmaf(p.weight_decay, w[j], gj);
-        if (HAS_MOM) {
-          m[j] = fmaf(p.momentum, m[j], gj);
-          gj = p.nesterov ? fmaf(p.momentum, m[j], gj) : m[j];
-        }
-        w[j] = fmaf(-p.lr, gj, w[j]);
-      }
       const bool full = e + 8 <= n_valid;
+      if constexpr (kAdam) {
+        // the second-moment plane: read whole (the planes are padded to the wire's shards), stored as master is
+        float v2[8];
+        DenseLane<float>::load8(p.var, e, v2);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) adamw_update(p, g[j], w[j], m[j], v2[j]);
+        if (full) {
+          DenseLane<float>::store8(p.var, e, v2);
+        } else {
+          for (int j = 0; j < 8 && e + j < n_valid; ++j) p.var[e + j] = v2[j];
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float gj = g[j] * p.grad_scale;
+          if (p.weight_decay != 0.0f) gj = fmaf(p.weight_decay, w[j], gj);
+          if (HAS_MOM) {
+            m[j] = fmaf(p.momentum, m[j], gj);
+            gj = p.nesterov ? fmaf(p.momentum, m[j], gj) : m[j];
+          }
+          w[j] = fmaf(-p.lr, gj, w[j]);
+        }
+      }
       if (full) {
         DenseLane<float>::store8(master, e, w);
         if (HAS_MOM) DenseLane<float>::store8(mom, e, m);
@@ -673,6 +714,27 @@ void launch_wire_sgd(int codec, const void* wire, size_t n_s, int n_shards, int 
   FAN_HIP_CHECK(hipGetLastError());
 }
 
+void launch_wire_adamw(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
+                       float* master, bf16_t* lp, float* mom, AdamWParams p, size_t n_valid, hipStream_t stream,
+                       size_t shard_stride) {
+  FAN_CHECK(master != nullptr && mom != nullptr && p.var != nullptr, "wire_adamw: master and both moment planes");
+  if (skip_period < 1) skip_period = 1 << 30;
+  check_ns(n_s);
+  if (n_s == 0 || n_shards == 0) return;
+  const int grid = stream_grid(n_s / 8, kBlock, wire_max_blocks());
+  const uint8_t* w = (const uint8_t*)wire;
+  FAN_CODEC_SWITCH(codec, {
+    const size_t sb = shard_stride ? shard_stride : wire_shard_bytes(C, n_s);
+    if (lp)
+      hipLaunchKernelGGL((wire_sgd_kernel<C, true, true, AdamWParams>), grid, kBlock, 0, stream, w, n_s, n_shards,
+                         skip_shard, skip_period, master, lp, mom, p, n_valid, sb);
+    else
+      hipLaunchKernelGGL((wire_sgd_kernel<C, false, true, AdamWParams>), grid, kBlock, 0, stream, w, n_s, n_shards,
+                         skip_shard, skip_period, master, lp, mom, p, n_valid, sb);
+  });
+  FAN_HIP_CHECK(hipGetLastError());
+}
+
 void launch_wire_unpack_strided(int codec, int out_dtype, const void* in, size_t shard_stride, void* out, size_t n_s,
                                 int n_shards, hipStream_t stream) {
   check_ns(n_s);
@@ -759,52 +821,42 @@ static std::atomic<int>& reduce4_flag() {
 void set_wire_reduce4(int on) { reduce4_flag().store(on); }
 int wire_reduce4() { return reduce4_flag().load(std::memory_order_relaxed); }
 
-template <int C>
+template <int C, typename P>
 static void reduce_sgd_dispatch(int local_dtype, int grid, const void* slots, size_t slot_stride, int n_slots,
-                                int self_pos, const void* local, float* master, float* mom, SgdParams p,
+                                int self_pos, const void* local, float* master, float* mom, P p,
                                 size_t n_valid, const WirePtrs& dst, int n_dst, size_t n_s, int rel,
                                 hipStream_t stream, int grid4) {
+  constexpr bool kAdam = std::is_same<P, AdamWParams>::value;  // AdamW: both moment planes, always
   const uint8_t* sl = (const uint8_t*)slots;
+#define FAN_RSGD(KERNEL, TL, MOM, G)                                                                                 \
+  hipLaunchKernelGGL((KERNEL<TL, C, MOM, P>), G, kBlock, 0, stream, sl, slot_stride, n_slots, self_pos,              \
+                     (const TL*)local, master, mom, p, n_valid, dst, n_dst, n_s, rel)
   if constexpr (C == kBfpTrunc || C == kBfpRne) {
     if (grid4 > 0) {
       if (local_dtype == kF32) {
-        if (mom)
-          hipLaunchKernelGGL((wire_reduce_sgd4_kernel<float, C, true>), grid4, kBlock, 0, stream, sl, slot_stride,
-                             n_slots, self_pos, (const float*)local, master, mom, p, n_valid, dst, n_dst, n_s, rel);
-        else
-          hipLaunchKernelGGL((wire_reduce_sgd4_kernel<float, C, false>), grid4, kBlock, 0, stream, sl, slot_stride,
-                             n_slots, self_pos, (const float*)local, master, mom, p, n_valid, dst, n_dst, n_s, rel);
+        if (kAdam || mom) FAN_RSGD(wire_reduce_sgd4_kernel, float, true, grid4);
+        else if constexpr (!kAdam) FAN_RSGD(wire_reduce_sgd4_kernel, float, false, grid4);
       } else {
-        if (mom)
-          hipLaunchKernelGGL((wire_reduce_sgd4_kernel<bf16_t, C, true>), grid4, kBlock, 0, stream, sl, slot_stride,
-                             n_slots, self_pos, (const bf16_t*)local, master, mom, p, n_valid, dst, n_dst, n_s, rel);
-        else
-          hipLaunchKernelGGL((wire_reduce_sgd4_kernel<bf16_t, C, false>), grid4, kBlock, 0, stream, sl, slot_stride,
-                             n_slots, self_pos, (const bf16_t*)local, master, mom, p, n_valid, dst, n_dst, n_s, rel);
+        if (kAdam || mom) FAN_RSGD(wire_reduce_sgd4_kernel, bf16_t, true, grid4);
+        else if constexpr (!kAdam) FAN_RSGD(wire_reduce_sgd4_kernel, bf16_t, false, grid4);
       }
       return;
     }
   }
   if (local_dtype == kF32) {
-    if (mom)
-      hipLaunchKernelGGL((wire_reduce_sgd_kernel<float, C, true>), grid, kBlock, 0, stream, sl, slot_stride, n_slots,
-                         self_pos, (const float*)local, master, mom, p, n_valid, dst, n_dst, n_s, rel);
-    else
-      hipLaunchKernelGGL((wire_reduce_sgd_kernel<float, C, false>), grid, kBlock, 0, stream, sl, slot_stride, n_slots,
-                         self_pos, (const float*)local, master, mom, p, n_valid, dst, n_dst, n_s, rel);
+    if (kAdam || mom) FAN_RSGD(wire_reduce_sgd_kernel, float, true, grid);
+    else if constexpr (!kAdam) FAN_RSGD(wire_reduce_sgd_kernel, float, false, grid);
   } else {
-    if (mom)
-      hipLaunchKernelGGL((wire_reduce_sgd_kernel<bf16_t, C, true>), grid, kBlock, 0, stream, sl, slot_stride, n_slots,
-                         self_pos, (const bf16_t*)local, master, mom, p, n_valid, dst, n_dst, n_s, rel);
-    else
-      hipLaunchKernelGGL((wire_reduce_sgd_kernel<bf16_t, C, false>), grid, kBlock, 0, stream, sl, slot_stride,
-                         n_slots, self_pos, (const bf16_t*)local, master, mom, p, n_valid, dst, n_dst, n_s, rel);
+    if (kAdam || mom) FAN_RSGD(wire_reduce_sgd_kernel, bf16_t, true, grid);
+    else if constexpr (!kAdam) FAN_RSGD(wire_reduce_sgd_kernel, bf16_t, false, grid);
   }
+#undef FAN_RSGD
 }
 
-void launch_wire_reduce_sgd(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots,
-                            int self_pos, const void* local, float* master, float* mom, SgdParams p, size_t n_valid,
-                            const WirePtrs& dst, int n_dst, size_t n_s, bool peers, hipStream_t stream) {
+template <typename P>
+static void launch_reduce_update(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots,
+                                 int self_pos, const void* local, float* master, float* mom, P p, size_t n_valid,
+                                 const WirePtrs& dst, int n_dst, size_t n_s, bool peers, hipStream_t stream) {
   check_ns(n_s);
   FAN_CHECK(n_dst <= kMaxPeers && local != nullptr && master != nullptr,
             "reduce_sgd: local operand, master shard and at most 16 destinations");
@@ -813,9 +865,25 @@ void launch_wire_reduce_sgd(int codec, int local_dtype, const void* slots, size_
   const int grid = stream_grid(n_s / 16, kBlock, cap);
   const int grid4 = wire_reduce4_for(n_slots) ? stream_grid(n_s / 4, kBlock, cap) : 0;
   const int rel = peers ? p2p_release_mode() : -1;
-  FAN_CODEC_SWITCH(codec, reduce_sgd_dispatch<C>(local_dtype, grid, slots, slot_stride, n_slots, self_pos, local,
-                                                 master, mom, p, n_valid, dst, n_dst, n_s, rel, stream, grid4));
+  FAN_CODEC_SWITCH(codec, (reduce_sgd_dispatch<C, P>(local_dtype, grid, slots, slot_stride, n_slots, self_pos, local,
+                                                     master, mom, p, n_valid, dst, n_dst, n_s, rel, stream, grid4)));
   FAN_HIP_CHECK(hipGetLastError());
+}
+
+void launch_wire_reduce_sgd(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots,
+                            int self_pos, const void* local, float* master, float* mom, SgdParams p, size_t n_valid,
+                            const WirePtrs& dst, int n_dst, size_t n_s, bool peers, hipStream_t stream) {
+  launch_reduce_update(codec, local_dtype, slots, slot_stride, n_slots, self_pos, local, master, mom, p, n_valid, dst,
+                       n_dst, n_s, peers, stream);
+}
+
+void launch_wire_reduce_adamw(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots,
+                              int self_pos, const void* local, float* master, float* mom, AdamWParams p,
+                              size_t n_valid, const WirePtrs& dst, int n_dst, size_t n_s, bool peers,
+                              hipStream_t stream) {
+  FAN_CHECK(mom != nullptr && p.var != nullptr, "reduce_adamw: both moment shards");
+  launch_reduce_update(codec, local_dtype, slots, slot_stride, n_slots, self_pos, local, master, mom, p, n_valid, dst,
+                       n_dst, n_s, peers, stream);
 }
 
 }  // namespace fan

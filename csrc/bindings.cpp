@@ -139,6 +139,33 @@ void wire_sgd(const at::Tensor& wire, int64_t shard_elems, int64_t n_shards, int
                        master.data_ptr<float>(), lpp, mp, p, (size_t)n_valid, fan_stream());
 }
 
+void wire_adamw(const at::Tensor& wire, int64_t shard_elems, int64_t n_shards, int64_t skip_shard, int64_t skip_period,
+                at::Tensor& master, const c10::optional<at::Tensor>& lp, at::Tensor& mom, at::Tensor& var,
+                const std::vector<double>& scalars, double grad_scale, double weight_decay, int64_t n_valid,
+                int64_t codec, int64_t shard_stride) {
+  FAN_T_CUDA_CONTIG(wire);
+  FAN_T_CUDA_CONTIG(master);
+  FAN_T_CUDA_CONTIG(mom);
+  TORCH_CHECK(master.scalar_type() == at::kFloat, "master weights must be float32");
+  TORCH_CHECK(master.numel() >= n_valid, "master too small");
+  TORCH_CHECK(mom.scalar_type() == at::kFloat && mom.numel() >= n_valid, "bad first-moment buffer");
+  const size_t sb = fan::wire_shard_bytes((int)codec, shard_elems);
+  TORCH_CHECK(shard_stride == 0 || (size_t)shard_stride >= sb, "shard_stride below the packed shard size");
+  const size_t need = n_shards > 0 ? (shard_stride ? (size_t)shard_stride * (n_shards - 1) + sb : sb * n_shards) : 0;
+  TORCH_CHECK((size_t)wire.numel() * wire.element_size() >= need, "wire buffer too small");
+  TORCH_CHECK(shard_stride % 16 == 0, "shard_stride must keep 16-byte alignment");
+  fan::bf16_t* lpp = nullptr;
+  if (lp) {
+    FAN_T_CUDA_CONTIG((*lp));
+    TORCH_CHECK(lp->scalar_type() == at::kBFloat16 && lp->numel() >= n_valid, "bad lp weights");
+    lpp = reinterpret_cast<fan::bf16_t*>(lp->data_ptr());
+  }
+  const fan::AdamWParams p = fan_adamw_params(scalars, grad_scale, weight_decay, var, n_valid);
+  fan::launch_wire_adamw((int)codec, wire.data_ptr(), (size_t)shard_elems, (int)n_shards, (int)skip_shard,
+                         (int)skip_period, master.data_ptr<float>(), lpp, mom.data_ptr<float>(), p, (size_t)n_valid,
+                         fan_stream(), (size_t)shard_stride);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -159,6 +186,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("n_slots"), pybind11::arg("self_pos"), pybind11::arg("local"), pybind11::arg("out_wire"),
         pybind11::arg("out_f32"), pybind11::arg("shard_elems"), pybind11::arg("codec"));
   m.def("wire_sgd", &wire_sgd, "fused decode + SGD weight update in place");
+  m.def("wire_adamw", &wire_adamw, "fused decode + AdamW weight update in place", pybind11::arg("wire"),
+        pybind11::arg("shard_elems"), pybind11::arg("n_shards"), pybind11::arg("skip_shard"),
+        pybind11::arg("skip_period"), pybind11::arg("master"), pybind11::arg("lp"), pybind11::arg("mom"),
+        pybind11::arg("var"), pybind11::arg("scalars"), pybind11::arg("grad_scale"), pybind11::arg("weight_decay"),
+        pybind11::arg("n_valid"), pybind11::arg("codec"), pybind11::arg("shard_stride") = 0);
   fan::register_gemm(m);
   fan::register_nn(m);
   fan::register_planner(m);

@@ -9,3 +9,18 @@
   TORCH_CHECK((t).is_contiguous(), #t " must be contiguous")
 
 inline hipStream_t fan_stream() { return c10::hip::getCurrentHIPStream().stream(); }
+
+#include <vector>
+
+#include "bfp/bfp_format.h"
+
+// AdamWParams from the Python side's scalars (bfp_oracle.adamw_scalars, already rounded to f32, in its order:
+// beta1, omb1, beta2, omb2, step_size, rsbc2, eps, decay) and the second-moment plane.
+inline fan::AdamWParams fan_adamw_params(const std::vector<double>& s, double grad_scale, double weight_decay,
+                                         const at::Tensor& var, int64_t n_valid) {
+  TORCH_CHECK(s.size() == 8, "adamw: 8 scalars (beta1, omb1, beta2, omb2, step_size, rsbc2, eps, decay)");
+  FAN_T_CUDA_CONTIG(var);
+  TORCH_CHECK(var.scalar_type() == at::kFloat && var.numel() >= n_valid, "var: f32[n_valid]");
+  return fan::AdamWParams{(float)grad_scale, (float)s[0], (float)s[1], (float)s[2], (float)s[3], (float)s[4],
+                          (float)s[5], (float)s[6], (float)weight_decay, (float)s[7], var.data_ptr<float>()};
+}

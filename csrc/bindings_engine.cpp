@@ -249,7 +249,8 @@ void register_engine(pybind11::module_& m) {
               c10::optional<at::Tensor> mom, int64_t n_valid, double lr, double grad_scale, double wd,
               double momentum, bool nesterov, bool defer, bool update, c10::optional<at::Tensor> out_sum,
               c10::optional<at::Tensor> prepacked, int64_t prepacked_elems, int64_t layout_shard,
-              int64_t layout_chunks, bool on_producer) {
+              int64_t layout_chunks, bool on_producer, int64_t opt, c10::optional<at::Tensor> var,
+              c10::optional<std::vector<double>> adamw) {
              FAN_T_CUDA_CONTIG(grad);
              TORCH_CHECK(grad.scalar_type() == at::kFloat || grad.scalar_type() == at::kBFloat16,
                          "gradients must be f32 or bf16");
@@ -292,16 +293,31 @@ void register_engine(pybind11::module_& m) {
                pre = prepacked->data_ptr<uint8_t>();
              }
              SgdParams p{(float)lr, (float)grad_scale, (float)wd, (float)momentum, nesterov ? 1 : 0};
+             TORCH_CHECK(opt == kOptSgd || opt == kOptAdamW, "opt: 0 (SGD) or 1 (AdamW)");
+             AdamWParams ap{};
+             if (opt == kOptAdamW) {
+               TORCH_CHECK(adamw.has_value(), "AdamW needs its scalars");
+               TORCH_CHECK(!update || (momp != nullptr && var && var->defined()),
+                           "AdamW needs both moment planes (mom, var)");
+               if (update) {
+                 // the kernels read the planes a whole lane (and, in the owner reduce, a whole shard) at a time
+                 TORCH_CHECK(var->numel() >= L.n_pad && mom->numel() >= L.n_pad && master.numel() >= L.n_pad,
+                             "AdamW: master, mom and var must be padded to the layout's ", L.n_pad, " elements");
+                 ap = fan_adamw_params(*adamw, grad_scale, wd, *var, n_valid);
+               }
+             }
              return e.submit(grad.data_ptr(), grad.scalar_type() == at::kFloat ? kF32 : kBF16,
                              update ? master.data_ptr<float>() : nullptr, lpp, momp, n_valid, p, fan_stream(), defer,
-                             update, outp, pre, prepacked_elems, layout_shard, layout_chunks, on_producer);
+                             update, outp, pre, prepacked_elems, layout_shard, layout_chunks, on_producer,
+                             opt == kOptAdamW && update ? &ap : nullptr);
            },
            py::arg("grad"), py::arg("master"), py::arg("lp") = py::none(), py::arg("mom") = py::none(),
            py::arg("n_valid"), py::arg("lr"), py::arg("grad_scale") = 1.0, py::arg("weight_decay") = 0.0,
            py::arg("momentum") = 0.0, py::arg("nesterov") = false, py::arg("defer") = false,
            py::arg("update") = true, py::arg("out_sum") = py::none(), py::arg("prepacked") = py::none(),
            py::arg("prepacked_elems") = 0, py::arg("layout_shard") = 0, py::arg("layout_chunks") = 0,
-           py::arg("on_producer") = false, py::call_guard<py::gil_scoped_release>())
+           py::arg("on_producer") = false, py::arg("opt") = 0, py::arg("var") = py::none(),
+           py::arg("adamw") = py::none(), py::call_guard<py::gil_scoped_release>())
       .def("prepack_shape", [](AllReduceEngine& e, int64_t n) {
         const auto s = e.prepack_shape(n);
         return py::make_tuple(s[0], s[1], s[2]);

@@ -234,14 +234,43 @@ uint8_t* AllReduceEngine::epi_scratch(const std::string& base, size_t bytes) {
   return scratch(key, bytes);
 }
 
+// The decode + update launch of a request's optimizer over planes that start `off` elements into the bucket.
+static void update_at(const UpdateParams& p, int codec, const void* wire, size_t n_s, int n_shards, int skip_shard,
+                      int skip_period, float* master, bf16_t* lp, float* mom, int64_t off, size_t n_valid,
+                      hipStream_t st, size_t shard_stride = 0) {
+  if (p.kind == kOptAdamW) {
+    AdamWParams a = p.adamw;
+    a.var += off;
+    launch_wire_adamw(codec, wire, n_s, n_shards, skip_shard, skip_period, master + off, lp ? lp + off : nullptr,
+                      mom + off, a, n_valid, st, shard_stride);
+  } else {
+    launch_wire_sgd(codec, wire, n_s, n_shards, skip_shard, skip_period, master + off, lp ? lp + off : nullptr,
+                    mom ? mom + off : nullptr, p.sgd, n_valid, st, shard_stride);
+  }
+}
+
+// The sharded update's owner reduce + update of the shard that starts `off` elements into the bucket.
+static void reduce_update_at(const UpdateParams& p, int codec, int local_dtype, const void* slots, size_t slot_stride,
+                             int n_slots, int self_pos, const void* local, float* master, float* mom, int64_t off,
+                             size_t n_valid, const WirePtrs& dst, int n_dst, size_t n_s, bool peers, hipStream_t st) {
+  if (p.kind == kOptAdamW) {
+    AdamWParams a = p.adamw;
+    a.var += off;
+    launch_wire_reduce_adamw(codec, local_dtype, slots, slot_stride, n_slots, self_pos, local, master + off, mom + off,
+                             a, n_valid, dst, n_dst, n_s, peers, st);
+  } else {
+    launch_wire_reduce_sgd(codec, local_dtype, slots, slot_stride, n_slots, self_pos, local, master + off,
+                           mom ? mom + off : nullptr, p.sgd, n_valid, dst, n_dst, n_s, peers, st);
+  }
+}
+
 // Epilogue over a gathered wire region: fused decode + SGD (and/or decoded sum output).
 static void epilogue(int codec, hipStream_t st, const uint8_t* G, int64_t shard, int n_shards, int64_t off,
-                     int64_t len, float* master, bf16_t* lp, float* mom, int64_t n_valid, SgdParams p, bool update,
+                     int64_t len, float* master, bf16_t* lp, float* mom, int64_t n_valid, UpdateParams p, bool update,
                      float* out_sum, int skip_shard = -1, int skip_period = 0) {
   const int64_t nv = std::max<int64_t>(0, std::min<int64_t>(n_valid - off, len));
   if (update && nv > 0)
-    launch_wire_sgd(codec, G, (size_t)shard, n_shards, skip_shard, skip_period, master + off, lp ? lp + off : nullptr,
-                    mom ? mom + off : nullptr, p, (size_t)nv, st);
+    update_at(p, codec, G, (size_t)shard, n_shards, skip_shard, skip_period, master, lp, mom, off, (size_t)nv, st);
   if (out_sum) launch_wire_unpack(codec, kF32, G, out_sum + off, (size_t)shard, n_shards, st);
 }
 
@@ -259,7 +288,7 @@ std::array<int64_t, 3> AllReduceEngine::prepack_shape(int64_t n) const {
 
 std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const void* grad, int gdt,
                                                              float* master, bf16_t* lp, float* mom, int64_t n_valid,
-                                                             SgdParams p, bool update, float* out_sum,
+                                                             UpdateParams p, bool update, float* out_sum,
                                                              const uint8_t* prepacked, int64_t prepacked_elems) {
   const int N = world_, r = rank_, c = cfg_.codec;
   const int64_t s = L.shard;
@@ -319,8 +348,8 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const voi
       const int64_t nv = std::max<int64_t>(0, std::min<int64_t>(n_valid - (int64_t)r * s, s));
       WirePtrs out{};
       out.p[0] = reinterpret_cast<uint8_t*>(lp + (size_t)r * s);
-      launch_wire_reduce_sgd(c, gdt, R, sb, N, r, g + (size_t)r * s * esize(gdt), master + (size_t)r * s,
-                             mom ? mom + (size_t)r * s : nullptr, p, (size_t)nv, out, 1, (size_t)s, false, st);
+      reduce_update_at(p, c, gdt, R, sb, N, r, g + (size_t)r * s * esize(gdt), master, mom, (int64_t)r * s, (size_t)nv,
+                       out, 1, (size_t)s, false, st);
     }
     mark(kTpReduced);
     if (!ident) {
@@ -376,7 +405,7 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const voi
 // that reads it (sites "mesh direct send" / "mesh direct gather", row = sender rank). Memory ordering: p2p_comm.h.
 std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineLayout& L, const void* grad, int gdt,
                                                        float* master, bf16_t* lp, float* mom, int64_t n_valid,
-                                                       SgdParams p, bool update, float* out_sum,
+                                                       UpdateParams p, bool update, float* out_sum,
                                                        const uint8_t* prepacked, bool defer) {
   const int N = world_, r = rank_, c = cfg_.codec;
   const int64_t s = L.shard;
@@ -436,9 +465,8 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineL
       WirePtrs out{};
       for (int q = 0; q < N; ++q) out.p[q] = q == r ? reinterpret_cast<uint8_t*>(lp + (size_t)r * s) : d->dst(r2, q);
       const int64_t nv = std::max<int64_t>(0, std::min<int64_t>(n_valid - (int64_t)r * s, s));
-      launch_wire_reduce_sgd(c, gdt, d->src_base(r1), d->src_stride(), N, r, g + (size_t)r * s * esize(gdt),
-                             master + (size_t)r * s, mom ? mom + (size_t)r * s : nullptr, p, (size_t)nv, out, N,
-                             (size_t)s, true, st);
+      reduce_update_at(p, c, gdt, d->src_base(r1), d->src_stride(), N, r, g + (size_t)r * s * esize(gdt), master, mom,
+                       (int64_t)r * s, (size_t)nv, out, N, (size_t)s, true, st);
       d->release(r1, st);
       tag_sent(r2, "mesh_reduce", wb);
     }
@@ -490,7 +518,7 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineL
     RoctxRange rr("fan/mesh/direct_epilogue");
     const int64_t nv = std::max<int64_t>(0, std::min<int64_t>(n_valid, n_pad));
     if (update && nv > 0)
-      launch_wire_sgd(c, Gv, (size_t)s, N, -1, 0, master, lp, mom, p, (size_t)nv, st, gstride);
+      update_at(p, c, Gv, (size_t)s, N, -1, 0, master, lp, mom, 0, (size_t)nv, st, gstride);
     if (out_sum) launch_wire_unpack_strided(c, kF32, Gv, gstride, out_sum, (size_t)s, N, st);
   }
   d->release(r2, st);
@@ -511,7 +539,7 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineL
 //   epilogue(c) on the aux stream.
 std::vector<EpiThunk> AllReduceEngine::run_mesh_chunked(const EngineLayout& L, const void* grad, int gdt,
                                                         float* master, bf16_t* lp, float* mom, int64_t n_valid,
-                                                        SgdParams p, bool update, float* out_sum,
+                                                        UpdateParams p, bool update, float* out_sum,
                                                         const uint8_t* prepacked, bool defer) {
   const int N = world_, r = rank_, c = cfg_.codec;
   const int64_t s = L.shard, C = L.chunks;
@@ -616,7 +644,7 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_chunked(const EngineLayout& L, c
 
 std::vector<EpiThunk> AllReduceEngine::run_ring(const EngineLayout& L, const void* grad, int gdt,
                                                              float* master, bf16_t* lp, float* mom, int64_t n_valid,
-                                                             SgdParams p, bool update, float* out_sum,
+                                                             UpdateParams p, bool update, float* out_sum,
                                                              const uint8_t* prepacked, int64_t prepacked_elems) {
   const int N = world_, c = cfg_.codec;
   const int64_t S = L.slice;
@@ -748,8 +776,7 @@ std::vector<EpiThunk> AllReduceEngine::run_ring(const EngineLayout& L, const voi
           const int64_t o2 = off + (b * N + own) * S;
           const int64_t nv = std::max<int64_t>(0, std::min<int64_t>(n_valid - o2, S));
           if (nv > 0)
-            launch_wire_sgd(kRawF32, f32 + b * S, (size_t)S, 1, -1, 0, master + o2, lp ? lp + o2 : nullptr,
-                            mom ? mom + o2 : nullptr, p, (size_t)nv, es);
+            update_at(p, kRawF32, f32 + b * S, (size_t)S, 1, -1, 0, master, lp, mom, o2, (size_t)nv, es);
         }
       });
     } else {
@@ -781,7 +808,7 @@ std::vector<EpiThunk> AllReduceEngine::run_ring(const EngineLayout& L, const voi
 // record four device timestamps per sub-round (hop_mark): start, credits granted, upstream data ready, kernels done.
 std::vector<EpiThunk> AllReduceEngine::run_ring_direct(P2PComm* d, const EngineLayout& L, const void* grad, int gdt,
                                                        float* master, bf16_t* lp, float* mom, int64_t n_valid,
-                                                       SgdParams p, bool update, float* out_sum,
+                                                       UpdateParams p, bool update, float* out_sum,
                                                        const uint8_t* prepacked) {
   const int N = world_, c = cfg_.codec;
   const int P = L.sub;
@@ -1012,8 +1039,15 @@ void AllReduceEngine::hop_mark(int point) {
 int AllReduceEngine::submit(const void* grad, int grad_dtype, float* master, bf16_t* lp, float* mom, int64_t n_valid,
                             SgdParams sgd, hipStream_t producer, bool defer, bool update, float* out_sum,
                             const uint8_t* prepacked, int64_t prepacked_elems, int64_t layout_shard,
-                            int64_t layout_chunks, bool on_producer) {
+                            int64_t layout_chunks, bool on_producer, const AdamWParams* adamw) {
   RoctxRange rr("fan/allreduce/submit");
+  UpdateParams upd;
+  upd.sgd = sgd;
+  if (adamw != nullptr) {
+    FAN_CHECK(!update || (mom != nullptr && adamw->var != nullptr), "AdamW needs both moment planes");
+    upd.kind = kOptAdamW;
+    upd.adamw = *adamw;
+  }
   FAN_HIP_CHECK(hipSetDevice(device_));
   // slot state machine (slot_table.h): the next slot (a still-deferred occupant is committed first, ordered after
   // the producer: the NIC's 8-deep command queue never drops a request), ordering after anything that may still
@@ -1056,9 +1090,9 @@ int AllReduceEngine::submit(const void* grad, int grad_dtype, float* master, bf1
   cur_defer_ = defer;
   trace_marked_ = 1u << kTpStart;
   std::vector<EpiThunk> thunks =
-      cfg_.algo == 0 ? run_mesh(L, grad, grad_dtype, master, lp, mom, n_valid, sgd, update, out_sum, prepacked,
+      cfg_.algo == 0 ? run_mesh(L, grad, grad_dtype, master, lp, mom, n_valid, upd, update, out_sum, prepacked,
                                 prepacked_elems)
-                     : run_ring(L, grad, grad_dtype, master, lp, mom, n_valid, sgd, update, out_sum, prepacked,
+                     : run_ring(L, grad, grad_dtype, master, lp, mom, n_valid, upd, update, out_sum, prepacked,
                                 prepacked_elems);
   FAN_HIP_CHECK(hipGetLastError());
   // phases this schedule does not have (ring hops, the world-1 local path) collapse onto the end of comm

@@ -128,6 +128,16 @@ enum VerifySite : uint32_t {
   kSiteMeshWeightGather = 7,  // the sharded update's bf16 weight all-gather (run_mesh)
 };
 
+// The weight update of one request: SGD (the default), or AdamW with its own scalars and second-moment plane
+// (adamw.var; the first moment travels where SGD's momentum does). One value through every schedule, so a site that
+// offsets the planes offsets adamw.var with them (update_at in engine.cpp).
+enum OptKind : int { kOptSgd = 0, kOptAdamW = 1 };
+struct UpdateParams {
+  int kind = kOptSgd;
+  SgdParams sgd{};
+  AdamWParams adamw{};
+};
+
 // Deferred epilogue of a request (decode + SGD), launched on the given stream at commit().
 using EpiThunk = std::function<void(hipStream_t)>;
 
@@ -187,7 +197,9 @@ class AllReduceEngine {
   int submit(const void* grad, int grad_dtype, float* master, bf16_t* lp, float* mom, int64_t n_valid,
              SgdParams sgd, hipStream_t producer, bool defer, bool update = true, float* out_sum = nullptr,
              const uint8_t* prepacked = nullptr, int64_t prepacked_elems = 0, int64_t layout_shard = 0,
-             int64_t layout_chunks = 0, bool on_producer = false);
+             int64_t layout_chunks = 0, bool on_producer = false, const AdamWParams* adamw = nullptr);
+  // adamw: the update is AdamW with these scalars (`sgd` is ignored, `mom` is the first moment and adamw->var the
+  // second, both required and laid out as master).
   // (shard elements, shards, owner shard whose f32 values the reduce needs or -1) for a prepacked bucket,
   // or shard elements 0 when this configuration cannot take prepacked input.
   std::array<int64_t, 3> prepack_shape(int64_t n) const;
@@ -276,19 +288,19 @@ class AllReduceEngine {
   void count_peers(size_t bytes, P2PComm* direct = nullptr);  // `bytes` sent to every other rank
   uint8_t* scratch(const std::string& key, size_t bytes);
   std::vector<EpiThunk> run_mesh(const EngineLayout& L, const void* grad, int gdt, float* master,
-                                              bf16_t* lp, float* mom, int64_t n_valid, SgdParams p, bool update,
+                                              bf16_t* lp, float* mom, int64_t n_valid, UpdateParams p, bool update,
                                               float* out_sum, const uint8_t* prepacked, int64_t prepacked_elems);
   std::vector<EpiThunk> run_mesh_direct(P2PComm* d, const EngineLayout& L, const void* grad, int gdt, float* master,
-                                        bf16_t* lp, float* mom, int64_t n_valid, SgdParams p, bool update,
+                                        bf16_t* lp, float* mom, int64_t n_valid, UpdateParams p, bool update,
                                         float* out_sum, const uint8_t* prepacked, bool defer);
   std::vector<EpiThunk> run_mesh_chunked(const EngineLayout& L, const void* grad, int gdt, float* master,
-                                         bf16_t* lp, float* mom, int64_t n_valid, SgdParams p, bool update,
+                                         bf16_t* lp, float* mom, int64_t n_valid, UpdateParams p, bool update,
                                          float* out_sum, const uint8_t* prepacked, bool defer);
   std::vector<EpiThunk> run_ring(const EngineLayout& L, const void* grad, int gdt, float* master,
-                                              bf16_t* lp, float* mom, int64_t n_valid, SgdParams p, bool update,
+                                              bf16_t* lp, float* mom, int64_t n_valid, UpdateParams p, bool update,
                                               float* out_sum, const uint8_t* prepacked, int64_t prepacked_elems);
   std::vector<EpiThunk> run_ring_direct(P2PComm* d, const EngineLayout& L, const void* grad, int gdt, float* master,
-                                        bf16_t* lp, float* mom, int64_t n_valid, SgdParams p, bool update,
+                                        bf16_t* lp, float* mom, int64_t n_valid, UpdateParams p, bool update,
                                         float* out_sum, const uint8_t* prepacked);
 
   Comm* comm_;

@@ -95,7 +95,7 @@ def run(argv=None, out=sys.stdout):
     impl = cfg.engine if device.type == "cuda" else "python"
     engine = make_engine(transport, kind, rounding=cfg.rounding, algo=cfg.algo, rings=cfg.rings,
                          max_slice_elems=cfg.slice_elems, compat_owner_fp32=cfg.compat_owner_fp32,
-                         timeout_s=cfg.timeout_s, impl=impl,
+                         timeout_s=cfg.timeout_s, impl=impl, device=device if device.type == "cpu" else None,
                          comm=transport.comm if isinstance(transport, P2PTransport) and impl == "native" else None)
     pad_fn = (lambda n: engine.layout(n).n_pad) if engine is not None else None
     if a.model_fuse == "hidden":
@@ -103,16 +103,21 @@ def run(argv=None, out=sys.stdout):
     else:  # reference fuse_type mapping (sw:479-489)
         bias, relu = {1: (True, "none"), 2: (False, "all"), 3: (True, "all")}.get(a.fuse_type, (False, "none"))
     model = MLP(sizes, dtype=dtype, device=device, pad_fn=pad_fn, seed=cfg.seed, momentum=cfg.momentum > 0,
-                bias=bias, relu=relu)
+                bias=bias, relu=relu, adam=cfg.optimizer == "adamw")
     if world > 1:  # reference C3/C4: broadcast weights + bias from rank 0
         for l in model.layers:
             transport.broadcast_(l.master, 0)
         model.sync_lp()
-    start_iter = 0
+    start_iter, opt_step = 0, 0
     if cfg.resume:
-        start_iter = int(checkpoint.load(cfg.resume, model).get("iteration", 0))
+        info = checkpoint.load(cfg.resume, model)
+        start_iter = int(info.get("iteration", 0))
+        if info.get("optimizer", "sgd") == cfg.optimizer:  # the update count belongs to the moments it was saved with
+            opt_step = int(info.get("opt_step", 0))
     trainer = DataParallelTrainer(model, engine, lr=cfg.lr, weight_decay=cfg.weight_decay, momentum=cfg.momentum,
-                                  loss_scale=cfg.loss_scale, profile=cfg.profile)
+                                  loss_scale=cfg.loss_scale, profile=cfg.profile, optimizer=cfg.optimizer,
+                                  betas=(cfg.beta1, cfg.beta2), eps=cfg.eps)
+    trainer.opt_step = opt_step
     x, y = make_data(mb, sizes[0], sizes[-1], rank, cfg.seed, device, dtype)
     threads = int(os.environ.get("OMP_NUM_THREADS", "1"))
     check = abs(float(os.environ.get("CHECK", "1") or 1))  # reference: env CHECK (sw:227-228)
@@ -180,7 +185,8 @@ def run(argv=None, out=sys.stdout):
         trainer.gather_state()
     if cfg.checkpoint and rank == 0:
         checkpoint.save(cfg.checkpoint, model, iteration=start_iter + cfg.warmup + cfg.iters, dtype=cfg.dtype,
-                        meta={"bn": a.bn, "bk": a.bk, "bc": a.bc, "world": world})
+                        meta={"bn": a.bn, "bk": a.bk, "bc": a.bc, "world": world}, optimizer=cfg.optimizer,
+                        opt_step=trainer.opt_step)
     D.cleanup()
     return {"loss": loss, "s_per_iter": total / max(cfg.iters, 1), "model": model}
 

@@ -38,6 +38,10 @@ class TrainConfig:
     lr: float = 0.1
     momentum: float = 0.0
     weight_decay: float = 0.0
+    optimizer: str = "sgd"         # sgd | adamw
+    beta1: float = 0.9
+    beta2: float = 0.999
+    eps: float = 1e-8
     loss_scale: float = 1.0
     warmup: int = 2
     seed: int = 1
@@ -67,6 +71,11 @@ def add_named_flags(ap: argparse.ArgumentParser):
     ap.add_argument("--lr", type=float, default=d.lr)
     ap.add_argument("--momentum", type=float, default=d.momentum)
     ap.add_argument("--weight-decay", type=float, default=d.weight_decay)
+    ap.add_argument("--optimizer", default=d.optimizer, choices=["sgd", "adamw"],
+                    help="weight update fused into the all-reduce epilogue")
+    ap.add_argument("--beta1", type=float, default=d.beta1, help="AdamW first-moment decay")
+    ap.add_argument("--beta2", type=float, default=d.beta2, help="AdamW second-moment decay")
+    ap.add_argument("--eps", type=float, default=d.eps, help="AdamW denominator term")
     ap.add_argument("--loss-scale", type=float, default=d.loss_scale)
     ap.add_argument("--warmup", type=int, default=d.warmup)
     ap.add_argument("--seed", type=int, default=d.seed)

@@ -32,6 +32,7 @@ class LayerBucket:
     grad: torch.Tensor
     lp: torch.Tensor | None
     mom: torch.Tensor | None
+    var: torch.Tensor | None = None  # AdamW's second moment (mom is then the first)
 
     @property
     def w_master(self):
@@ -65,8 +66,9 @@ class MLP:
 
     def __init__(self, sizes, *, dtype=torch.bfloat16, device="cpu", pad_fn=None, seed: int = 1,
                  momentum: bool = False, init_scale: float | None = None, bias: bool = True,
-                 relu: str = "hidden"):
-        """``bias`` / ``relu`` select the layer epilogue. ``relu``: 'hidden' (every layer but the classifier,
+                 relu: str = "hidden", adam: bool = False):
+        """``adam``: allocate both AdamW moment planes per layer (``mom`` the first, ``var`` the second).
+        ``bias`` / ``relu`` select the layer epilogue. ``relu``: 'hidden' (every layer but the classifier,
         the default model), 'all' or 'none'. The reference's fuse_type (sw:479-489) maps to
         0 -> (bias=False, relu='none'), 1 -> (True, 'none'), 2 -> (False, 'all'), 3 -> (True, 'all')."""
         if len(sizes) < 2:
@@ -93,8 +95,9 @@ class MLP:
             master = master.to(self.device)
             lp = master.to(torch.bfloat16) if dtype == torch.bfloat16 else None
             grad = torch.zeros(n_pad, dtype=torch.float32, device=self.device)
-            mom = torch.zeros(n_pad, dtype=torch.float32, device=self.device) if momentum else None
-            self.layers.append(LayerBucket(cin, cout, n, n_pad, master, grad, lp, mom))
+            mom = torch.zeros(n_pad, dtype=torch.float32, device=self.device) if momentum or adam else None
+            var = torch.zeros(n_pad, dtype=torch.float32, device=self.device) if adam else None
+            self.layers.append(LayerBucket(cin, cout, n, n_pad, master, grad, lp, mom, var))
         self._act_mb = None
         self._zero_b: dict[int, torch.Tensor] = {}
 
@@ -154,6 +157,7 @@ class MLP:
             return u
 
         l.master, l.grad, l.lp, l.mom = grow(l.master), grow(l.grad), grow(l.lp), grow(l.mom)
+        l.var = grow(l.var)
         l.n_pad = n_pad
 
     # ------------------------------------------------------------------ activations

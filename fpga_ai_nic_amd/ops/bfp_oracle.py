@@ -179,3 +179,60 @@ def sgd(w: np.ndarray, g: np.ndarray, lr: float, grad_scale: float = 1.0, weight
         g = (np.float64(np.float32(momentum)) * m.astype(np.float64) + g).astype(np.float32) if nesterov else m
     w = (np.float64(-np.float32(lr)) * g.astype(np.float64) + w.astype(np.float64)).astype(np.float32)
     return w, new_mom
+
+
+class AdamWScalars(tuple):
+    """The per-step AdamW scalars, each already rounded to f32 (``adamw_scalars``); ``wd`` rides along because the
+    update tests it against 0."""
+    FIELDS = ("beta1", "omb1", "beta2", "omb2", "step_size", "rsbc2", "eps", "decay", "wd")
+
+    def __new__(cls, *vals):
+        assert len(vals) == len(cls.FIELDS)
+        return super().__new__(cls, (np.float32(x) for x in vals))
+
+    def __getattr__(self, name):
+        try:
+            return self[self.FIELDS.index(name)]
+        except ValueError:
+            raise AttributeError(name) from None
+
+    def kernel_args(self):
+        """The eight scalars the native launchers take (all but wd), as Python floats holding the f32 values."""
+        return [float(x) for x in self[:8]]
+
+
+def adamw_scalars(lr: float, wd: float, beta1: float, beta2: float, eps: float, step: int) -> AdamWScalars:
+    """The scalars of update ``step`` (1-based), computed in float64 and rounded once to f32; the kernels, the C++
+    engine and ``adamw`` below all receive these values, so every path sees the same bits."""
+    if not eps > 0:
+        raise ValueError(f"AdamW: eps must be positive, got {eps}")
+    if int(step) != step or step < 1:
+        raise ValueError(f"AdamW: step is the 1-based update count, got {step}")
+    if not (0.0 <= beta1 < 1.0 and 0.0 <= beta2 < 1.0):
+        raise ValueError(f"AdamW: betas must lie in [0, 1), got {(beta1, beta2)}")
+    lr, wd, b1, b2, t = float(lr), float(wd), float(beta1), float(beta2), int(step)
+    return AdamWScalars(b1, 1.0 - b1, b2, 1.0 - b2, lr / (1.0 - b1 ** t), 1.0 / np.sqrt(1.0 - b2 ** t), float(eps),
+                        1.0 - lr * wd, wd)
+
+
+def adamw(w: np.ndarray, g: np.ndarray, m: np.ndarray, v: np.ndarray, scalars: AdamWScalars,
+          grad_scale: float = 1.0):
+    """fp32 AdamW with the kernel's operation order (csrc/bfp/bfp_format.h adamw_update): fma emulated in float64
+    and rounded, sqrt and division in float64 and rounded (exact double rounding for both). Returns (w', m', v')."""
+    s = scalars
+    f64 = np.float64
+    w = np.asarray(w, np.float32)
+    m = np.asarray(m, np.float32)
+    v = np.asarray(v, np.float32)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore", under="ignore"):
+        g = (np.asarray(g, np.float32) * np.float32(grad_scale)).astype(np.float32)
+        t1 = (s.omb1 * g).astype(np.float32)
+        m2 = (f64(s.beta1) * m.astype(f64) + t1.astype(f64)).astype(np.float32)
+        t2 = ((s.omb2 * g).astype(np.float32) * g).astype(np.float32)
+        v2 = (f64(s.beta2) * v.astype(f64) + t2.astype(f64)).astype(np.float32)
+        r = np.sqrt(v2.astype(f64)).astype(np.float32)
+        d = (r.astype(f64) * f64(s.rsbc2) + f64(s.eps)).astype(np.float32)
+        q = (m2.astype(f64) / d.astype(f64)).astype(np.float32)
+        base = (w * s.decay).astype(np.float32) if s.wd != 0 else w
+        w2 = (f64(-s.step_size) * q.astype(f64) + base.astype(f64)).astype(np.float32)
+    return w2, m2, v2

@@ -111,3 +111,40 @@ def sgd(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Tenso
             m[lo:hi] = nm
     if lp is not None:
         lp.view(-1)[:n_valid].copy_(master.view(-1)[:n_valid].to(lp.dtype))
+
+
+def adamw(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Tensor, *, codec,
+          mom: torch.Tensor, var: torch.Tensor, scalars: O.AdamWScalars, lp: torch.Tensor | None = None,
+          grad_scale: float = 1.0, n_valid: int | None = None, skip_shard: int = -1, skip_period: int = 0,
+          shard_stride: int = 0):
+    """Fused decode + AdamW in place (``bfp_oracle.adamw``'s arithmetic): ``mom`` / ``var`` are the first / second
+    moment planes, ``scalars`` the step's ``bfp_oracle.adamw_scalars``; lp = bf16(master). ``shard_stride``: bytes
+    between consecutive wire shards (0: packed)."""
+    c = codec_id(codec)
+    if mom is None or var is None:
+        raise ValueError("AdamW needs both moment planes (mom, var)")
+    n_valid = master.numel() if n_valid is None else int(n_valid)
+    if master.is_cuda:
+        _ext.require().wire_adamw(wire, int(shard_elems), int(n_shards), int(skip_shard), int(skip_period), master,
+                                  lp, mom, var, scalars.kernel_args(), float(grad_scale), float(scalars.wd), n_valid,
+                                  c, int(shard_stride))
+        return
+    sb = O.shard_bytes(c, shard_elems)
+    raw = _np_u8(wire)
+    if shard_stride:
+        raw = np.concatenate([raw[s * shard_stride: s * shard_stride + sb] for s in range(n_shards)])
+    n = shard_elems * n_shards
+    g = O.unpack(raw, n, shard_elems, c)
+    w = master.view(-1).numpy()
+    m = mom.view(-1).numpy()
+    v = var.view(-1).numpy()
+    period = skip_period if skip_period >= 1 else (1 << 30)
+    for s in range(n_shards):
+        if skip_shard >= 0 and s % period == skip_shard:
+            continue
+        lo, hi = s * shard_elems, min((s + 1) * shard_elems, n_valid)
+        if hi <= lo:
+            continue
+        w[lo:hi], m[lo:hi], v[lo:hi] = O.adamw(w[lo:hi], g[lo:hi], m[lo:hi], v[lo:hi], scalars, grad_scale)
+        if lp is not None:
+            lp.view(-1)[lo:hi].copy_(master.view(-1)[lo:hi].to(lp.dtype))

@@ -66,6 +66,26 @@ def _round_up(a, b):
     return _cdiv(a, b) * b
 
 
+OPTIMIZERS = ("sgd", "adamw")
+
+
+def adamw_request(opt, mom, var, *, lr, weight_decay, momentum, nesterov, betas, eps, step):
+    """Validate one request's optimizer arguments; the step's ``bfp_oracle.AdamWScalars`` for ``opt="adamw"``
+    (``mom`` the first moment, ``var`` the second, ``step`` the bucket's 1-based update count), None for SGD."""
+    if opt not in OPTIMIZERS:
+        raise ValueError(f"unknown optimizer {opt!r} (one of {OPTIMIZERS})")
+    if opt == "sgd":
+        return None
+    if momentum or nesterov:
+        raise ValueError("momentum / nesterov belong to SGD: AdamW's first moment is governed by betas[0]")
+    if step is None:
+        raise ValueError("AdamW needs step, the 1-based update count of the bucket")
+    scalars = wire.O.adamw_scalars(lr, weight_decay, betas[0], betas[1], eps, step)
+    if mom is None or var is None:
+        raise ValueError("AdamW needs both moment planes: mom (first) and var (second)")
+    return scalars
+
+
 # ------------------------------------------------------------------------------------------ planning
 def ring_geometry(n: int, world: int, max_slice_elems: int):
     C = _ext.load()
@@ -282,28 +302,39 @@ class CompressedAllReduce:
                       mom: torch.Tensor | None = None, *, n_valid: int | None = None, lr: float,
                       grad_scale: float = 1.0, weight_decay: float = 0.0, momentum: float = 0.0,
                       nesterov: bool = False, update_after=None, defer: bool = False,
-                      name: str = "bucket") -> Handle:
-        """All-reduce ``grad`` (flat, padded to ``layout(n).n_pad``) and apply SGD to ``master`` (+bf16 ``lp``)."""
+                      name: str = "bucket", opt: str = "sgd", var: torch.Tensor | None = None,
+                      betas=(0.9, 0.999), eps: float = 1e-8, step: int | None = None) -> Handle:
+        """All-reduce ``grad`` (flat, padded to ``layout(n).n_pad``) and apply SGD to ``master`` (+bf16 ``lp``).
+        ``opt="adamw"``: AdamW instead, ``mom`` / ``var`` the first / second moment planes (both required), ``step``
+        the bucket's 1-based update count."""
+        scalars = adamw_request(opt, mom, var, lr=lr, weight_decay=weight_decay, momentum=momentum,
+                                nesterov=nesterov, betas=betas, eps=eps, step=step)
         n_valid = int(n_valid if n_valid is not None else master.numel())
         L = self.layout(n_valid)
         self._check(grad, L)
         sgd_kw = dict(lr=lr, grad_scale=grad_scale, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov)
 
+        def update(G, shard, n_shards, off, length, nv, codec, skip=(-1, 0)):
+            planes = dict(lp=None if lp is None else lp.view(-1)[off:off + length],
+                          mom=None if mom is None else mom.view(-1)[off:off + length])
+            if scalars is not None:
+                wire.adamw(G, shard, n_shards, master.view(-1)[off:off + length], codec=codec,
+                           var=var.view(-1)[off:off + length], scalars=scalars, grad_scale=grad_scale, n_valid=nv,
+                           skip_shard=skip[0], skip_period=skip[1], **planes)
+            else:
+                wire.sgd(G, shard, n_shards, master.view(-1)[off:off + length], codec=codec, n_valid=nv,
+                         skip_shard=skip[0], skip_period=skip[1], **planes, **sgd_kw)
+
         def finish(G, shard, n_shards, off, length, skip=(-1, 0)):
             nv = max(0, min(n_valid - off, length))
             if nv == 0:
                 return
-            wire.sgd(G, shard, n_shards, master.view(-1)[off:off + length], codec=self.codec_id,
-                     lp=None if lp is None else lp.view(-1)[off:off + length],
-                     mom=None if mom is None else mom.view(-1)[off:off + length], n_valid=nv,
-                     skip_shard=skip[0], skip_period=skip[1], **sgd_kw)
+            update(G, shard, n_shards, off, length, nv, self.codec_id, skip)
 
-        def owner_fp32(buf, off, length):  # compat: owner applies SGD from the un-quantised fp32 sum
+        def owner_fp32(buf, off, length):  # compat: owner applies the update from the un-quantised fp32 sum
             nv = max(0, min(n_valid - off, length))
             if nv:
-                wire.sgd(buf, length, 1, master.view(-1)[off:off + length], codec="raw_f32",
-                         lp=None if lp is None else lp.view(-1)[off:off + length],
-                         mom=None if mom is None else mom.view(-1)[off:off + length], n_valid=nv, **sgd_kw)
+                update(buf, length, 1, off, length, nv, "raw_f32")
 
         return self._launch(lambda: self._run(L, grad, finish, owner_fp32), name, L, defer, update_after)
 
@@ -545,13 +576,21 @@ class CompressedAllReduce:
 
 
 def uncompressed_allreduce_sgd(transport: Transport, grad, master, lp=None, mom=None, *, n_valid=None, lr,
-                               grad_scale=1.0, weight_decay=0.0, momentum=0.0, nesterov=False):
-    """Baseline: RCCL all-reduce (sum) of the raw gradients + a separate SGD kernel (BASELINE config 2;
+                               grad_scale=1.0, weight_decay=0.0, momentum=0.0, nesterov=False, opt="sgd", var=None,
+                               betas=(0.9, 0.999), eps=1e-8, step=None):
+    """Baseline: RCCL all-reduce (sum) of the raw gradients + a separate SGD (or AdamW) kernel (BASELINE config 2;
     the reference's commented MPI_Iallreduce + libxsmm opt path, sw:615-647)."""
+    scalars = adamw_request(opt, mom, var, lr=lr, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov,
+                            betas=betas, eps=eps, step=step)
     transport.all_reduce_(grad)
     n_valid = master.numel() if n_valid is None else n_valid
     n = _round_up(n_valid, 256)
     codec = "raw_f32" if grad.dtype == torch.float32 else "raw_bf16"
+    if scalars is not None:
+        wire.adamw(wire.as_bytes(grad.view(-1)[:n]) if grad.numel() >= n else wire.as_bytes(grad), n, 1,
+                   master.view(-1), codec=codec, lp=None if lp is None else lp.view(-1), mom=mom.view(-1),
+                   var=var.view(-1), scalars=scalars, grad_scale=grad_scale, n_valid=n_valid)
+        return
     wire.sgd(wire.as_bytes(grad.view(-1)[:n]) if grad.numel() >= n else wire.as_bytes(grad), n, 1,
              master.view(-1), codec=codec, lp=None if lp is None else lp.view(-1),
              mom=None if mom is None else mom.view(-1), lr=lr, grad_scale=grad_scale, weight_decay=weight_decay,

@@ -21,7 +21,7 @@ from ..models.mlp import MLP
 from ..ops import gemm as G
 from ..ops import gemm_tune, wire
 from ..utils import tracing
-from .allreduce import CompressedAllReduce, Handle, _round_up
+from .allreduce import OPTIMIZERS, CompressedAllReduce, Handle, _round_up
 from .transport import Transport
 
 
@@ -54,15 +54,17 @@ class RcclAllReduce(CompressedAllReduce):
 def make_engine(transport: Transport | None, kind: str = "bfp", *, rounding: str = "rne", algo: str = "mesh",
                 rings: int = 1, max_slice_elems: int = 1 << 22, compat_owner_fp32: bool = False,
                 timeout_s: float = 600.0, force_comm: bool = False, impl: str = "python", comm=None,
-                side_stream: bool = False, ring_sub: int = 0, shard_update: bool | None = None):
-    """kind: 'bfp' (compressed engine), 'raw' (engine, uncompressed fp32 wire), 'rccl' (baseline),
+                side_stream: bool = False, ring_sub: int = 0, shard_update: bool | None = None, device=None):
+    """``device`` (Python engines): where the engine keeps its buffers; None: the current GPU when there is one. A
+    CPU run on a machine that has a GPU must name it, or the engine's scratch lands on the GPU beside CPU gradients.
+    kind: 'bfp' (compressed engine), 'raw' (engine, uncompressed fp32 wire), 'rccl' (baseline),
     'local' (no communication: world 1). impl: 'python' (request path issued from Python over any
     transport) or 'native' (C++ engine over its own RCCL communicator, or over ``comm``, e.g. the direct P2P
     communicator of :func:`~fpga_ai_nic_amd.parallel.transport.make_p2p_comm`; GPU only)."""
     if kind == "local" or transport is None:
         return None
     if kind == "rccl":
-        return RcclAllReduce(transport, timeout_s=timeout_s, force_comm=force_comm)
+        return RcclAllReduce(transport, timeout_s=timeout_s, force_comm=force_comm, device=device)
     codec = {"bfp": f"bfp_{rounding}", "raw": "raw_f32", "raw_bf16": "raw_bf16"}[kind]
     if impl == "native":
         from .native_engine import NativeAllReduce
@@ -71,7 +73,8 @@ def make_engine(transport: Transport | None, kind: str = "bfp", *, rounding: str
                                compat_owner_fp32=compat_owner_fp32, timeout_s=timeout_s, force_comm=force_comm,
                                comm=comm, side_stream=side_stream, ring_sub=ring_sub, shard_update=shard_update)
     return CompressedAllReduce(transport, codec=codec, algo=algo, rings=rings, max_slice_elems=max_slice_elems,
-                               compat_owner_fp32=compat_owner_fp32, timeout_s=timeout_s, force_comm=force_comm)
+                               compat_owner_fp32=compat_owner_fp32, timeout_s=timeout_s, force_comm=force_comm,
+                               device=device)
 
 
 class DataParallelTrainer:
@@ -79,8 +82,14 @@ class DataParallelTrainer:
                  weight_decay: float = 0.0, momentum: float = 0.0, nesterov: bool = False,
                  loss_scale: float = 1.0, average: bool = True, profile: bool = False, prepack: bool = True,
                  commit_at_end: bool | None = None, fused_update: bool | None = None,
-                 gemm_inflight: str | None = None, wgrad_pair: bool | str | None = None):
-        """``fused_update`` (default env FAN_FUSED_UPDATE, else on): with a single-rank engine (world 1, requests
+                 gemm_inflight: str | None = None, wgrad_pair: bool | str | None = None, optimizer: str = "sgd",
+                 betas=(0.9, 0.999), eps: float = 1e-8):
+        """``optimizer``: 'sgd' or 'adamw' (``betas``, ``eps``; the model must hold the second-moment planes,
+        ``MLP(..., adam=True)``). AdamW runs in the engine's decode + update epilogue — not in the bwd-weight GEMM's,
+        so ``fused_update`` is off with it — with ``opt_step``, the 1-based update count, advanced once per
+        ``backward_pass``.
+
+        ``fused_update`` (default env FAN_FUSED_UPDATE, else on): with a single-rank engine (world 1, requests
         inline: the all-reduce of one rank is the identity) and the GEMM-encoded wire, the bwd-weight GEMM's epilogue
         takes each encoded gradient group through its BFP round trip in registers and applies the SGD update to the
         layer's weights in place — the engine's decode + SGD pass over the whole bucket (master read + write, bf16
@@ -103,6 +112,16 @@ class DataParallelTrainer:
         self.engine = engine
         self.world = engine.world if engine is not None else 1
         self.lr, self.wd, self.momentum, self.nesterov = lr, weight_decay, momentum, nesterov
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
+        self.optimizer, self.betas, self.eps = optimizer, (float(betas[0]), float(betas[1])), float(eps)
+        self.opt_step = 0  # updates applied so far (AdamW's bias correction; checkpointed)
+        if optimizer == "adamw":
+            if momentum or nesterov:
+                raise ValueError("momentum / nesterov belong to SGD: AdamW's first moment is governed by betas[0]")
+            wire.O.adamw_scalars(lr, weight_decay, self.betas[0], self.betas[1], self.eps, 1)  # validates
+            if any(l.mom is None or l.var is None for l in model.layers):
+                raise ValueError("optimizer='adamw' needs a model with both moment planes: MLP(..., adam=True)")
         self.loss_scale = loss_scale
         # gradients are of the LOCAL mean loss; the all-reduce sums over ranks -> average with 1/N
         self.grad_scale = (1.0 / self.world) if average else 1.0
@@ -120,8 +139,9 @@ class DataParallelTrainer:
         self.prepack = (prepack and engine is not None and getattr(engine, "prepack", False) and self.cuda
                         and model.dtype == torch.bfloat16)
         fu = os.environ.get("FAN_FUSED_UPDATE", "1") != "0" if fused_update is None else bool(fused_update)
+        # (the GEMM epilogue's update is SGD: AdamW takes the engine's decode + update pass)
         self.fused_update = (fu and self.prepack and bool(getattr(engine, "inline", False))
-                             and getattr(engine, "codec", "") == "bfp_rne")
+                             and getattr(engine, "codec", "") == "bfp_rne" and optimizer == "sgd")
         self.fused_updates = 0
         # fused update: the layers' bias-gradient reduces of unsplit bwd-weight plans are queued and run by the next
         # split-K wire reduce of the backward, or all in one grouped launch after it (FAN_DEFER_COLSUM=0: one launch
@@ -158,7 +178,18 @@ class DataParallelTrainer:
         self.last_on_producer = (self.cuda and engine is not None and not getattr(engine, "inline", True)
                                  and hasattr(engine, "C") and os.environ.get("FAN_LAST_ON_PRODUCER", "1") != "0")
 
+    def _opt_kw(self, l):
+        """The optimizer arguments of layer l's request in the step being enqueued."""
+        if self.optimizer != "adamw":
+            return {}
+        return dict(opt="adamw", var=l.var, betas=self.betas, eps=self.eps, step=self.opt_step)
+
     def _sgd_local(self, l):
+        if self.optimizer == "adamw":
+            scalars = wire.O.adamw_scalars(self.lr, self.wd, self.betas[0], self.betas[1], self.eps, self.opt_step)
+            wire.adamw(wire.as_bytes(l.grad), l.n_pad, 1, l.master, codec="raw_f32", lp=l.lp, mom=l.mom, var=l.var,
+                       scalars=scalars, grad_scale=self.grad_scale, n_valid=l.n)
+            return
         wire.sgd(wire.as_bytes(l.grad), l.n_pad, 1, l.master, codec="raw_f32", lp=l.lp, mom=l.mom, lr=self.lr,
                  grad_scale=self.grad_scale, weight_decay=self.wd, momentum=self.momentum, nesterov=self.nesterov,
                  n_valid=l.n)
@@ -220,6 +251,10 @@ class DataParallelTrainer:
         """Loss fwd+bwd, then per layer L-1..0: dW -> async all-reduce+SGD -> dX (reference type 'B')."""
         m = self.m
         prof = self.profile
+        if self.optimizer == "adamw" and self.cuda and torch.cuda.is_current_stream_capturing():
+            # the step's scalars are by-value kernel arguments: a captured graph would replay step 1's for ever
+            raise RuntimeError("an AdamW step cannot be captured into a graph (its per-step scalars would be frozen)")
+        self.opt_step += 1
         self._wait_updates()  # no-op after forward_pass; needed when backward passes run back to back
         t0 = time.perf_counter()
         with tracing.range("loss"):
@@ -273,7 +308,7 @@ class DataParallelTrainer:
                             h = self.engine.allreduce_sgd(l.grad, l.master, lp_out, l.mom, n_valid=l.n, lr=self.lr,
                                                           grad_scale=self.grad_scale, weight_decay=self.wd,
                                                           momentum=self.momentum, nesterov=self.nesterov, defer=True,
-                                                          name=f"fc{i}", **kw)
+                                                          name=f"fc{i}", **kw, **self._opt_kw(l))
                             self._gemm_grid(True)
                         m.backward_data(i)
                         if h is not None:
@@ -358,7 +393,7 @@ class DataParallelTrainer:
         self._wait_updates()
 
     def gather_state(self):
-        """Sharded-update engine: collect every layer's owner-sharded master (and momentum) onto every rank, so the
+        """Sharded-update engine: collect every layer's owner-sharded master (and moments) onto every rank, so the
         planes are whole again (checkpoint, replica check). Collective; a no-op for other engines."""
         if not self.shard:
             return
@@ -367,6 +402,8 @@ class DataParallelTrainer:
             self.engine.gather_owned(l.master, l.n)
             if l.mom is not None:
                 self.engine.gather_owned(l.mom, l.n)
+            if l.var is not None:
+                self.engine.gather_owned(l.var, l.n)
 
     def finish(self, timeout: float | None = None):
         """Wait (host) for every outstanding all-reduce/update."""

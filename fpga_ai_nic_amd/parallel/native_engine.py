@@ -23,7 +23,7 @@ import torch
 
 from .. import _ext
 from ..ops import wire
-from .allreduce import NUM_SLOTS, BucketLayout, ChecksumError, CommTimeoutError
+from .allreduce import NUM_SLOTS, BucketLayout, ChecksumError, CommTimeoutError, adamw_request
 from .transport import NativeTransport, Transport
 
 _ALGOS = {"mesh": 0, "ring": 1}
@@ -244,12 +244,19 @@ class NativeAllReduce:
                       mom: torch.Tensor | None = None, *, n_valid: int | None = None, lr: float,
                       grad_scale: float = 1.0, weight_decay: float = 0.0, momentum: float = 0.0,
                       nesterov: bool = False, update_after=None, defer: bool = False,
-                      name: str = "bucket", prepacked=None, layout=None, on_producer: bool = False) -> NativeHandle:
-        """``prepacked=(wire_u8, elems)``: flat elements [0, elems) were already encoded into ``wire_u8``
+                      name: str = "bucket", prepacked=None, layout=None, on_producer: bool = False,
+                      opt: str = "sgd", var: torch.Tensor | None = None, betas=(0.9, 0.999), eps: float = 1e-8,
+                      step: int | None = None) -> NativeHandle:
+        """``opt="adamw"``: AdamW instead of SGD, ``mom`` / ``var`` the first / second moment planes (both required),
+        ``step`` the bucket's 1-based update count (as :meth:`CompressedAllReduce.allreduce_sgd`).
+        ``prepacked=(wire_u8, elems)``: flat elements [0, elems) were already encoded into ``wire_u8``
         (from :meth:`prepack_target`); the engine encodes the rest and skips its pack pass. ``layout=(shard,
         chunks)``: an explicit chunked mesh layout (shard elements x world x chunks). ``on_producer``: run the request on the
         current (producer) stream instead of the engine's comm stream — the last request of a backward, which has
         nothing left to overlap with (saves two cross-stream hand-offs on the critical path)."""
+        scalars = adamw_request(opt, mom, var, lr=lr, weight_decay=weight_decay, momentum=momentum,
+                                nesterov=nesterov, betas=betas, eps=eps, step=step)
+        okw = {} if scalars is None else dict(opt=1, var=var.view(-1), adamw=scalars.kernel_args())
         n_valid = int(n_valid if n_valid is not None else master.numel())
         pre, pre_n = (None, 0) if prepacked is None else prepacked
         ls, lc = (0, 0) if layout is None else (int(layout[0]), int(layout[1]))
@@ -258,7 +265,7 @@ class NativeAllReduce:
         eng_defer = defer or update_after is not None
         slot = self.C.submit(grad.view(-1), master.view(-1), None if lp is None else lp.view(-1),
                              None if mom is None else mom.view(-1), n_valid, lr, grad_scale, weight_decay, momentum,
-                             nesterov, eng_defer, True, None, pre, int(pre_n), ls, lc, bool(on_producer))
+                             nesterov, eng_defer, True, None, pre, int(pre_n), ls, lc, bool(on_producer), **okw)
         h = NativeHandle(self, slot, self.C.slot_seq(slot), name, pending=eng_defer)
         self._account(n_valid)
         return h if defer else h.commit(update_after)

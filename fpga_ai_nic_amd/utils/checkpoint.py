@@ -5,7 +5,8 @@ The reference never writes weights to disk; its in-memory layo
 defines the on-disk format as exactly that:
 
 * ``<path>.safetensors`` — tensors ``fc{i}.weight`` [C_i, C_{i+1}] and ``fc{i}.bias`` [C_{i+1}] in f32 (or bf16),
-  optional ``fc{i}.momentum`` (flat, f32);
+  optional ``fc{i}.momentum`` (flat, f32), or for an AdamW model ``fc{i}.exp_avg`` / ``fc{i}.exp_avg_sq`` (its two
+  moment planes, flat, f32; the index then carries ``optimizer`` and ``opt_step``, the updates applied so far);
 * ``<path>.json`` — index: layer shapes / dtypes / byte offsets into a plain concatenated ``.bin`` image, the
   libxsmm blocking ``bn/bk/bc`` as metadata, iteration counter, world size and engine settings.
 * ``<path>.bin`` — the raw concatenation (weight_0, bias_0, weight_1, ...) so a C/C++ consumer (e.g. the
@@ -23,7 +24,8 @@ import torch
 from safetensors.torch import load_file, save_file
 
 
-def save(path: str, model, *, iteration: int = 0, dtype: str = "f32", meta: dict | None = None):
+def save(path: str, model, *, iteration: int = 0, dtype: str = "f32", meta: dict | None = None,
+         optimizer: str | None = None, opt_step: int | None = None):
     tdt = torch.float32 if dtype == "f32" else torch.bfloat16
     tensors, index, off = {}, [], 0
     blobs = []
@@ -32,7 +34,10 @@ def save(path: str, model, *, iteration: int = 0, dtype: str = "f32", meta: dict
         b = l.b_master.detach().to("cpu", tdt).contiguous()
         tensors[f"fc{i}.weight"] = w
         tensors[f"fc{i}.bias"] = b
-        if l.mom is not None:
+        if getattr(l, "var", None) is not None:
+            tensors[f"fc{i}.exp_avg"] = l.mom[: l.n].detach().to("cpu").contiguous()
+            tensors[f"fc{i}.exp_avg_sq"] = l.var[: l.n].detach().to("cpu").contiguous()
+        elif l.mom is not None:
             tensors[f"fc{i}.momentum"] = l.mom[: l.n].detach().to("cpu").contiguous()
         for name, t in ((f"fc{i}.weight", w), (f"fc{i}.bias", b)):
             raw = t.view(torch.uint8).numpy().tobytes() if tdt == torch.bfloat16 else t.numpy().tobytes()
@@ -46,6 +51,10 @@ def save(path: str, model, *, iteration: int = 0, dtype: str = "f32", meta: dict
             f.write(raw)
     info = {"format": "fpga_ai_nic_amd/mlp-v1", "sizes": model.sizes, "iteration": iteration, "dtype": dtype,
             "layout": "row-major C[i] x C[i+1] (reference fil_libxsmm order)", "tensors": index}
+    if optimizer is not None:
+        info["optimizer"] = optimizer
+    if opt_step is not None:
+        info["opt_step"] = int(opt_step)
     info.update(meta or {})
     with open(path + ".json", "w") as f:
         json.dump(info, f, indent=1)
@@ -61,7 +70,10 @@ def load(path: str, model) -> dict:
     for i, l in enumerate(model.layers):
         l.w_master.copy_(sd[f"fc{i}.weight"].to(l.master.device, torch.float32))
         l.b_master.copy_(sd[f"fc{i}.bias"].to(l.master.device, torch.float32))
-        if l.mom is not None and f"fc{i}.momentum" in sd:
+        if getattr(l, "var", None) is not None and f"fc{i}.exp_avg_sq" in sd:
+            l.mom[: l.n].copy_(sd[f"fc{i}.exp_avg"].to(l.mom.device))
+            l.var[: l.n].copy_(sd[f"fc{i}.exp_avg_sq"].to(l.var.device))
+        elif l.mom is not None and f"fc{i}.momentum" in sd:
             l.mom[: l.n].copy_(sd[f"fc{i}.momentum"].to(l.mom.device))
     model.sync_lp()
     return info
