@@ -261,26 +261,33 @@ void register_engine(pybind11::module_& m) {
                FAN_T_CUDA_CONTIG(master);
                TORCH_CHECK(master.scalar_type() == at::kFloat && master.numel() >= n_valid, "master: f32[n_valid]");
              }
-             bf16_t* lpp = nullptr;
-             float* momp = nullptr;
-             float* outp = nullptr;
+             EngineRequest req;
+             req.grad = grad.data_ptr();
+             req.grad_dtype = grad.scalar_type() == at::kFloat ? kF32 : kBF16;
+             req.master = update ? master.data_ptr<float>() : nullptr;
+             req.n_valid = n_valid;
+             req.update = update;
+             req.defer = defer;
+             req.prepacked_elems = prepacked_elems;
+             req.layout_shard = layout_shard;
+             req.layout_chunks = layout_chunks;
+             req.on_producer = on_producer;
              if (lp && lp->defined()) {
                FAN_T_CUDA_CONTIG(*lp);
                TORCH_CHECK(lp->scalar_type() == at::kBFloat16 && lp->numel() >= n_valid, "lp: bf16[n_valid]");
-               lpp = reinterpret_cast<bf16_t*>(lp->data_ptr());
+               req.lp = reinterpret_cast<bf16_t*>(lp->data_ptr());
              }
              if (mom && mom->defined()) {
                FAN_T_CUDA_CONTIG(*mom);
                TORCH_CHECK(mom->scalar_type() == at::kFloat && mom->numel() >= n_valid, "mom: f32[n_valid]");
-               momp = mom->data_ptr<float>();
+               req.mom = mom->data_ptr<float>();
              }
              if (out_sum && out_sum->defined()) {
                FAN_T_CUDA_CONTIG(*out_sum);
                TORCH_CHECK(out_sum->scalar_type() == at::kFloat && out_sum->numel() >= L.n_pad,
                            "out_sum: f32[n_pad]");
-               outp = out_sum->data_ptr<float>();
+               req.out_sum = out_sum->data_ptr<float>();
              }
-             const uint8_t* pre = nullptr;
              if (prepacked && prepacked->defined()) {
                FAN_T_CUDA_CONTIG(*prepacked);
                TORCH_CHECK(e.prepack_shape(n_valid)[0] > 0, "this engine configuration cannot take prepacked input");
@@ -290,26 +297,23 @@ void register_engine(pybind11::module_& m) {
                                               (int64_t)wire_shard_bytes(e.codec(), L.slice / L.sub);
                TORCH_CHECK(prepacked->scalar_type() == at::kByte && prepacked->numel() >= need,
                            "prepacked wire buffer too small");
-               pre = prepacked->data_ptr<uint8_t>();
+               req.prepacked = prepacked->data_ptr<uint8_t>();
              }
-             SgdParams p{(float)lr, (float)grad_scale, (float)wd, (float)momentum, nesterov ? 1 : 0};
+             req.upd.sgd = SgdParams{(float)lr, (float)grad_scale, (float)wd, (float)momentum, nesterov ? 1 : 0};
              TORCH_CHECK(opt == kOptSgd || opt == kOptAdamW, "opt: 0 (SGD) or 1 (AdamW)");
-             AdamWParams ap{};
              if (opt == kOptAdamW) {
                TORCH_CHECK(adamw.has_value(), "AdamW needs its scalars");
-               TORCH_CHECK(!update || (momp != nullptr && var && var->defined()),
+               TORCH_CHECK(!update || (req.mom != nullptr && var && var->defined()),
                            "AdamW needs both moment planes (mom, var)");
                if (update) {
                  // the kernels read the planes a whole lane (and, in the owner reduce, a whole shard) at a time
                  TORCH_CHECK(var->numel() >= L.n_pad && mom->numel() >= L.n_pad && master.numel() >= L.n_pad,
                              "AdamW: master, mom and var must be padded to the layout's ", L.n_pad, " elements");
-                 ap = fan_adamw_params(*adamw, grad_scale, wd, *var, n_valid);
+                 req.upd.kind = kOptAdamW;
+                 req.upd.adamw = fan_adamw_params(*adamw, grad_scale, wd, *var, n_valid);
                }
              }
-             return e.submit(grad.data_ptr(), grad.scalar_type() == at::kFloat ? kF32 : kBF16,
-                             update ? master.data_ptr<float>() : nullptr, lpp, momp, n_valid, p, fan_stream(), defer,
-                             update, outp, pre, prepacked_elems, layout_shard, layout_chunks, on_producer,
-                             opt == kOptAdamW && update ? &ap : nullptr);
+             return e.submit(req, fan_stream());
            },
            py::arg("grad"), py::arg("master"), py::arg("lp") = py::none(), py::arg("mom") = py::none(),
            py::arg("n_valid"), py::arg("lr"), py::arg("grad_scale") = 1.0, py::arg("weight_decay") = 0.0,

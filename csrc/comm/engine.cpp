@@ -19,6 +19,14 @@ static double now_s() {
 static int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static int64_t round_up(int64_t a, int64_t b) { return cdiv(a, b) * b; }
 static size_t esize(int dtype) { return dtype == kF32 ? 4 : 2; }
+// elements of [off, off + len) that lie inside the bucket's n_valid
+static int64_t valid_in(int64_t n_valid, int64_t off, int64_t len) {
+  return std::max<int64_t>(0, std::min<int64_t>(n_valid - off, len));
+}
+// the gradient buffer already is the wire format: nothing to pack
+static bool zero_copy(int codec, int gdt) {
+  return (codec == kRawF32 && gdt == kF32) || (codec == kRawBf16 && gdt == kBF16);
+}
 
 AllReduceEngine::AllReduceEngine(Comm* comm, int rank, int world, EngineConfig cfg, int device)
     : comm_(comm), rank_(rank), world_(world), device_(device), cfg_(cfg) {
@@ -56,7 +64,6 @@ AllReduceEngine::AllReduceEngine(Comm* comm, int rank, int world, EngineConfig c
   FAN_HIP_CHECK(hipStreamCreateWithPriority(&aux_stream_, hipStreamNonBlocking, cfg.stream_priority));
   for (auto& row : cev_)
     for (auto& e : row) FAN_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  run_stream_ = stream_;
   void* h = nullptr;
   FAN_HIP_CHECK(hipHostMalloc(&h, kSlots * 64, hipHostMallocMapped));
   std::memset(h, 0, kSlots * 64);
@@ -210,7 +217,7 @@ int64_t AllReduceEngine::wire_bytes(const EngineLayout& L) const {
   return (int64_t)L.rings * L.blocks * 2 * (N - 1) * (int64_t)wire_shard_bytes(cfg_.codec, L.slice);
 }
 
-uint8_t* AllReduceEngine::scratch(const std::string& key, size_t bytes) {
+uint8_t* AllReduceEngine::scratch(const std::string& key, size_t bytes, hipStream_t st) {
   auto it = scratch_.find(key);
   if (it != scratch_.end() && it->second.second >= bytes) return it->second.first;
   if (it != scratch_.end()) {
@@ -219,7 +226,7 @@ uint8_t* AllReduceEngine::scratch(const std::string& key, size_t bytes) {
   }
   void* p = nullptr;
   FAN_HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 256)));
-  FAN_HIP_CHECK(hipMemsetAsync(p, 0, std::max<size_t>(bytes, 256), run_stream_));
+  FAN_HIP_CHECK(hipMemsetAsync(p, 0, std::max<size_t>(bytes, 256), st));
   scratch_[key] = {reinterpret_cast<uint8_t*>(p), bytes};
   return reinterpret_cast<uint8_t*>(p);
 }
@@ -228,50 +235,56 @@ uint8_t* AllReduceEngine::epi_scratch(const std::string& base, size_t bytes) {
   // one buffer per request slot; for ordinary buckets all kSlots are allocated on a key's first use, so the slot
   // rotation never allocates later (inside a timed loop); buckets above 64 MB allocate per slot on first use
   // (8 copies of a multi-GB gathered wire would be pure waste for a request stream that rarely defers them)
-  const std::string key = base + "_s" + std::to_string(epi_slot_);
+  const std::string key = base + "_s" + std::to_string(cur_.slot);
   if (scratch_.find(key) == scratch_.end() && bytes <= (size_t(64) << 20))
-    for (int s = 0; s < kSlots; ++s) scratch(base + "_s" + std::to_string(s), bytes);
-  return scratch(key, bytes);
+    for (int s = 0; s < kSlots; ++s) scratch(base + "_s" + std::to_string(s), bytes, cur_.run);
+  return scratch(key, bytes, cur_.run);
 }
 
-// The decode + update launch of a request's optimizer over planes that start `off` elements into the bucket.
-static void update_at(const UpdateParams& p, int codec, const void* wire, size_t n_s, int n_shards, int skip_shard,
-                      int skip_period, float* master, bf16_t* lp, float* mom, int64_t off, size_t n_valid,
-                      hipStream_t st, size_t shard_stride = 0) {
-  if (p.kind == kOptAdamW) {
-    AdamWParams a = p.adamw;
+// The decode + update launch of a request's optimizer over `nv` elements of its planes, `off` elements into the bucket.
+static void update_at(const EngineRequest& req, int codec, const void* wire, size_t n_s, int n_shards, int skip_shard,
+                      int skip_period, int64_t off, size_t nv, hipStream_t st, size_t shard_stride = 0) {
+  bf16_t* lp = req.lp ? req.lp + off : nullptr;
+  if (req.upd.kind == kOptAdamW) {
+    AdamWParams a = req.upd.adamw;
     a.var += off;
-    launch_wire_adamw(codec, wire, n_s, n_shards, skip_shard, skip_period, master + off, lp ? lp + off : nullptr,
-                      mom + off, a, n_valid, st, shard_stride);
+    launch_wire_adamw(codec, wire, n_s, n_shards, skip_shard, skip_period, req.master + off, lp, req.mom + off, a, nv,
+                      st, shard_stride);
   } else {
-    launch_wire_sgd(codec, wire, n_s, n_shards, skip_shard, skip_period, master + off, lp ? lp + off : nullptr,
-                    mom ? mom + off : nullptr, p.sgd, n_valid, st, shard_stride);
+    launch_wire_sgd(codec, wire, n_s, n_shards, skip_shard, skip_period, req.master + off, lp,
+                    req.mom ? req.mom + off : nullptr, req.upd.sgd, nv, st, shard_stride);
   }
 }
 
 // The sharded update's owner reduce + update of the shard that starts `off` elements into the bucket.
-static void reduce_update_at(const UpdateParams& p, int codec, int local_dtype, const void* slots, size_t slot_stride,
-                             int n_slots, int self_pos, const void* local, float* master, float* mom, int64_t off,
-                             size_t n_valid, const WirePtrs& dst, int n_dst, size_t n_s, bool peers, hipStream_t st) {
-  if (p.kind == kOptAdamW) {
-    AdamWParams a = p.adamw;
+static void reduce_update_at(const EngineRequest& req, int codec, const void* slots, size_t slot_stride, int n_slots,
+                             int self_pos, const void* local, int64_t off, size_t nv, const WirePtrs& dst, int n_dst,
+                             size_t n_s, bool peers, hipStream_t st) {
+  if (req.upd.kind == kOptAdamW) {
+    AdamWParams a = req.upd.adamw;
     a.var += off;
-    launch_wire_reduce_adamw(codec, local_dtype, slots, slot_stride, n_slots, self_pos, local, master + off, mom + off,
-                             a, n_valid, dst, n_dst, n_s, peers, st);
+    launch_wire_reduce_adamw(codec, req.grad_dtype, slots, slot_stride, n_slots, self_pos, local, req.master + off,
+                             req.mom + off, a, nv, dst, n_dst, n_s, peers, st);
   } else {
-    launch_wire_reduce_sgd(codec, local_dtype, slots, slot_stride, n_slots, self_pos, local, master + off,
-                           mom ? mom + off : nullptr, p.sgd, n_valid, dst, n_dst, n_s, peers, st);
+    launch_wire_reduce_sgd(codec, req.grad_dtype, slots, slot_stride, n_slots, self_pos, local, req.master + off,
+                           req.mom ? req.mom + off : nullptr, req.upd.sgd, nv, dst, n_dst, n_s, peers, st);
   }
 }
 
-// Epilogue over a gathered wire region: fused decode + SGD (and/or decoded sum output).
-static void epilogue(int codec, hipStream_t st, const uint8_t* G, int64_t shard, int n_shards, int64_t off,
-                     int64_t len, float* master, bf16_t* lp, float* mom, int64_t n_valid, UpdateParams p, bool update,
-                     float* out_sum, int skip_shard = -1, int skip_period = 0) {
-  const int64_t nv = std::max<int64_t>(0, std::min<int64_t>(n_valid - off, len));
-  if (update && nv > 0)
-    update_at(p, codec, G, (size_t)shard, n_shards, skip_shard, skip_period, master, lp, mom, off, (size_t)nv, st);
-  if (out_sum) launch_wire_unpack(codec, kF32, G, out_sum + off, (size_t)shard, n_shards, st);
+// Epilogue over a gathered wire region: fused decode + update (and/or decoded sum output).
+static void epilogue(const EngineRequest& req, int codec, hipStream_t st, const uint8_t* G, int64_t shard, int n_shards,
+                     int64_t off, int64_t len, int skip_shard = -1, int skip_period = 0) {
+  const int64_t nv = valid_in(req.n_valid, off, len);
+  if (req.update && nv > 0)
+    update_at(req, codec, G, (size_t)shard, n_shards, skip_shard, skip_period, off, (size_t)nv, st);
+  if (req.out_sum) launch_wire_unpack(codec, kF32, G, req.out_sum + off, (size_t)shard, n_shards, st);
+}
+
+EpiThunk AllReduceEngine::make_epilogue(const EngineRequest& req, const uint8_t* wire, int64_t shard_elems,
+                                        int n_shards, int64_t off, int64_t len, int skip_shard,
+                                        int skip_period) const {
+  const int c = cfg_.codec;
+  return [=](hipStream_t es) { epilogue(req, c, es, wire, shard_elems, n_shards, off, len, skip_shard, skip_period); };
 }
 
 std::array<int64_t, 3> AllReduceEngine::prepack_shape(int64_t n) const {
@@ -286,38 +299,30 @@ std::array<int64_t, 3> AllReduceEngine::prepack_shape(int64_t n) const {
   return {L.shard, world_ * L.chunks, local ? -1 : rank_};
 }
 
-std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const void* grad, int gdt,
-                                                             float* master, bf16_t* lp, float* mom, int64_t n_valid,
-                                                             UpdateParams p, bool update, float* out_sum,
-                                                             const uint8_t* prepacked, int64_t prepacked_elems) {
-  const int N = world_, r = rank_, c = cfg_.codec;
+std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const EngineRequest& req) {
+  const int N = world_, r = rank_, c = cfg_.codec, gdt = req.grad_dtype;
   const int64_t s = L.shard;
   const size_t sb = wire_shard_bytes(c, s);
-  const uint8_t* g = reinterpret_cast<const uint8_t*>(grad);
-  hipStream_t st = run_stream_;
-  if (prepacked) {  // encode what the producer did not (bias gradient + padding)
-    launch_wire_pack_range(c, gdt, grad, const_cast<uint8_t*>(prepacked), (size_t)s, (size_t)prepacked_elems,
-                           (size_t)L.n_pad, st);
+  const uint8_t* g = reinterpret_cast<const uint8_t*>(req.grad);
+  hipStream_t st = cur_.run;
+  if (req.prepacked) {  // encode what the producer did not (bias gradient + padding)
+    launch_wire_pack_range(c, gdt, req.grad, const_cast<uint8_t*>(req.prepacked), (size_t)s,
+                           (size_t)req.prepacked_elems, (size_t)L.n_pad, st);
   }
   if ((N == 1 && !cfg_.force_comm) || comm_ == nullptr) {
-    if (prepacked) {  // the producer's encoding IS the (single-rank) result: no reduce pass
-      const uint8_t* W = prepacked;
-      return {[=](hipStream_t es) { epilogue(c, es, W, s, 1, 0, s, master, lp, mom, n_valid, p, update, out_sum); }};
-    }
+    // the producer's encoding IS the (single-rank) result: no reduce pass
+    if (req.prepacked) return {make_epilogue(req, req.prepacked, s, 1, 0, s)};
     uint8_t* S = epi_scratch("mesh_S" + std::to_string(sb), sb);
     launch_wire_reduce(c, gdt, S, sb, 1, 0, g, S, nullptr, (size_t)s, st);
-    return {[=](hipStream_t es) { epilogue(c, es, S, s, 1, 0, s, master, lp, mom, n_valid, p, update, out_sum); }};
+    return {make_epilogue(req, S, s, 1, 0, s)};
   }
-  if (L.chunks > 1)
-    return run_mesh_chunked(L, grad, gdt, master, lp, mom, n_valid, p, update, out_sum, prepacked, cur_defer_);
-  if (P2PComm* d = comm_->direct(); d && N <= kMaxPeers)
-    return run_mesh_direct(d, L, grad, gdt, master, lp, mom, n_valid, p, update, out_sum, prepacked, cur_defer_);
-  uint8_t* S = scratch("mesh_S" + std::to_string(sb), sb);
-  const uint8_t* P = prepacked ? prepacked : g;
-  const bool zero_copy = (c == kRawF32 && gdt == kF32) || (c == kRawBf16 && gdt == kBF16);
-  if (!zero_copy && !prepacked) {
+  if (L.chunks > 1) return run_mesh_chunked(L, req);
+  if (P2PComm* d = comm_->direct(); d && N <= kMaxPeers) return run_mesh_direct(d, L, req);
+  uint8_t* S = scratch("mesh_S" + std::to_string(sb), sb, st);
+  const uint8_t* P = req.prepacked ? req.prepacked : g;
+  if (!zero_copy(c, gdt) && !req.prepacked) {
     RoctxRange rr("fan/mesh/pack");
-    uint8_t* Pb = scratch("mesh_P" + std::to_string(sb * N), sb * N);
+    uint8_t* Pb = scratch("mesh_P" + std::to_string(sb * N), sb * N, st);
     launch_wire_pack(c, gdt, g, Pb, (size_t)s, N, st);
     P = Pb;
   }
@@ -327,44 +332,29 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const voi
   // ~25-30 us of hand-off each around them, profiles/r5_forced_step_timeline.txt) — unless verify mode or a fault rule
   // wants to see the messages.
   const bool ident = N == 1 && !verify_ && !fault_.active();
-  uint8_t* R = ident ? const_cast<uint8_t*>(P) : scratch("mesh_R" + std::to_string(sb * N), sb * N);
+  uint8_t* R = ident ? const_cast<uint8_t*>(P) : scratch("mesh_R" + std::to_string(sb * N), sb * N, st);
   if (!ident) {
     RoctxRange rr("fan/mesh/all_to_all");
-    if (verify_) launch_msg_tags(P, sb, sb, N, req_seq_, tag_region(0), st);
-    fault_.maybe_corrupt("mesh_pack", const_cast<uint8_t*>(P), sb * N, st);  // in flight: after the tags
-    comm_->all_to_all(P, R, sb, st);
-    count_peers(sb);
-    if (verify_) {
-      comm_->all_to_all(tag_region(0), tag_region(1), 16, st);
-      verify_rows(R, sb, N, tag_region(1), kSiteMeshAllToAll, 0, st);
-    }
+    all_to_all_checked(P, R, sb, 0, st);
   }
   mark(kTpExchanged);
-  if (shard_upd_ && update && out_sum == nullptr && lp != nullptr) {
+  if (sharded(req)) {
     // sharded update: the owner's reduce + round trip + SGD of shard r writes its new bf16 weights into lp's shard r,
     // then the weights are all-gathered in place (every rank's lp shard q comes from rank q)
+    uint8_t* W = reinterpret_cast<uint8_t*>(req.lp);
+    const size_t wb = (size_t)s * 2;
     {
       RoctxRange rr("fan/mesh/reduce_sgd");
-      const int64_t nv = std::max<int64_t>(0, std::min<int64_t>(n_valid - (int64_t)r * s, s));
       WirePtrs out{};
-      out.p[0] = reinterpret_cast<uint8_t*>(lp + (size_t)r * s);
-      reduce_update_at(p, c, gdt, R, sb, N, r, g + (size_t)r * s * esize(gdt), master, mom, (int64_t)r * s, (size_t)nv,
-                       out, 1, (size_t)s, false, st);
+      out.p[0] = W + (size_t)r * wb;
+      reduce_update_at(req, c, R, sb, N, r, g + (size_t)r * s * esize(gdt), (int64_t)r * s,
+                       (size_t)valid_in(req.n_valid, (int64_t)r * s, s), out, 1, (size_t)s, false, st);
     }
     mark(kTpReduced);
     if (!ident) {
       RoctxRange rr("fan/mesh/all_gather_weights");
       // the weight shard goes through the same verify tags and fault hook as the unsharded path's gathered gradient
-      uint8_t* W = reinterpret_cast<uint8_t*>(lp);
-      const size_t wb = (size_t)s * 2;
-      if (verify_) launch_msg_tags(W + (size_t)r * wb, wb, wb, 1, req_seq_, tag_region(3), st);
-      fault_.maybe_corrupt("mesh_reduce", W + (size_t)r * wb, wb, st);
-      comm_->all_gather(lp + (size_t)r * s, lp, wb, st);
-      count_peers(wb);
-      if (verify_) {
-        comm_->all_gather(tag_region(3), tag_region(4), 16, st);
-        verify_rows(W, wb, N, tag_region(4), kSiteMeshWeightGather, 0, st);
-      }
+      all_gather_checked(W + (size_t)r * wb, W, wb, kSiteMeshWeightGather, 0, st);
     }
     counters_.sharded_updates++;
     return {};
@@ -378,17 +368,33 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const voi
   mark(kTpReduced);
   if (!ident) {
     RoctxRange rr("fan/mesh/all_gather");
-    if (verify_) launch_msg_tags(S, sb, sb, 1, req_seq_, tag_region(3), st);
-    fault_.maybe_corrupt("mesh_reduce", S, sb, st);
-    comm_->all_gather(S, G, sb, st);
-    count_peers(sb);
-    if (verify_) {
-      comm_->all_gather(tag_region(3), tag_region(4), 16, st);
-      verify_rows(G, sb, N, tag_region(4), kSiteMeshAllGather, 0, st);
-    }
+    all_gather_checked(S, G, sb, kSiteMeshAllGather, 0, st);
   }
-  const int64_t n_pad = L.n_pad;
-  return {[=](hipStream_t es) { epilogue(c, es, G, s, N, 0, n_pad, master, lp, mom, n_valid, p, update, out_sum); }};
+  return {make_epilogue(req, G, s, N, 0, L.n_pad)};
+}
+
+void AllReduceEngine::all_to_all_checked(const uint8_t* src, uint8_t* dst, size_t row_bytes, uint32_t row_base,
+                                         hipStream_t st) {
+  if (verify_) launch_msg_tags(src, row_bytes, row_bytes, world_, cur_.seq, tag_region(0), st);
+  fault_.maybe_corrupt("mesh_pack", const_cast<uint8_t*>(src), row_bytes * world_, st);  // in flight: after the tags
+  comm_->all_to_all(src, dst, row_bytes, st);
+  count_peers(row_bytes);
+  if (verify_) {
+    comm_->all_to_all(tag_region(0), tag_region(1), 16, st);
+    verify_rows(dst, row_bytes, world_, tag_region(1), kSiteMeshAllToAll, row_base, st);
+  }
+}
+
+void AllReduceEngine::all_gather_checked(uint8_t* src, uint8_t* dst, size_t bytes, uint32_t verify_site,
+                                         uint32_t row_base, hipStream_t st) {
+  if (verify_) launch_msg_tags(src, bytes, bytes, 1, cur_.seq, tag_region(3), st);
+  fault_.maybe_corrupt("mesh_reduce", src, bytes, st);
+  comm_->all_gather(src, dst, bytes, st);
+  count_peers(bytes);
+  if (verify_) {
+    comm_->all_gather(tag_region(3), tag_region(4), 16, st);
+    verify_rows(dst, bytes, world_, tag_region(4), verify_site, row_base, st);
+  }
 }
 
 // Mesh over the direct P2P transport: the encoder is the sender (the NIC streams its sums
@@ -403,17 +409,14 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const voi
 // No staging buffer and no copy kernel on either side of a link. Verify mode tags every message where it landed
 // (the slot trailer, P2PComm::dst_tag) and checks it on the consumer side after the ready flag, before the kernel
 // that reads it (sites "mesh direct send" / "mesh direct gather", row = sender rank). Memory ordering: p2p_comm.h.
-std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineLayout& L, const void* grad, int gdt,
-                                                       float* master, bf16_t* lp, float* mom, int64_t n_valid,
-                                                       UpdateParams p, bool update, float* out_sum,
-                                                       const uint8_t* prepacked, bool defer) {
-  const int N = world_, r = rank_, c = cfg_.codec;
+std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineLayout& L, const EngineRequest& req) {
+  const int N = world_, r = rank_, c = cfg_.codec, gdt = req.grad_dtype;
   const int64_t s = L.shard;
   const size_t sb = wire_shard_bytes(c, s);
   FAN_CHECK(sb <= d->payload_bytes(), "p2p: shard larger than the arena slot (raise slot_bytes)");
-  const uint8_t* g = reinterpret_cast<const uint8_t*>(grad);
-  hipStream_t st = run_stream_;
-  const bool zero_copy = (c == kRawF32 && gdt == kF32) || (c == kRawBf16 && gdt == kBF16);
+  const uint8_t* g = reinterpret_cast<const uint8_t*>(req.grad);
+  hipStream_t st = cur_.run;
+  const bool raw = zero_copy(c, gdt);
   // verify / fault hooks of one direct round: tag what this rank stored into each peer's slot (trailer tag 0), and
   // the receiver's check of every peer's message once its flag is up
   auto tag_sent = [&](const P2PComm::Round& rd, const char* fault_site, size_t bytes) {
@@ -441,10 +444,10 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineL
     for (int q = 0; q < N; ++q) {
       if (q == r) continue;
       to.p[q] = d->dst(r1, q);
-      if (prepacked) segs.push_back({prepacked + (size_t)q * sb, to.p[q], sb});
-      else if (zero_copy) segs.push_back({g + (size_t)q * s * esize(gdt), to.p[q], sb});
+      if (req.prepacked) segs.push_back({req.prepacked + (size_t)q * sb, to.p[q], sb});
+      else if (raw) segs.push_back({g + (size_t)q * s * esize(gdt), to.p[q], sb});
     }
-    if (prepacked || zero_copy) d->move(segs, st);
+    if (req.prepacked || raw) d->move(segs, st);
     else launch_wire_pack_to(c, gdt, g, to, (size_t)s, N, st);
     tag_sent(r1, "mesh_pack", sb);
   }
@@ -455,18 +458,18 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineL
   check_received(r1, kSiteMeshDirectSend, sb);
   mark(kTpExchanged);
   P2PComm::Round r2 = d->begin(st);
-  if (shard_upd_ && update && out_sum == nullptr && lp != nullptr) {
+  if (sharded(req)) {
     // sharded update: the owner reduces the received shards in place, takes the sum through the codec round trip,
     // applies SGD to its master shard and stores its new bf16 weights straight into every peer's round-2 slot and
     // into its own lp shard; each rank then copies the peers' weight shards into lp (the layer's next weights)
+    bf16_t* lp = req.lp;
     const size_t wb = (size_t)s * 2;
     {
       RoctxRange rr("fan/mesh/direct_reduce_sgd");
       WirePtrs out{};
       for (int q = 0; q < N; ++q) out.p[q] = q == r ? reinterpret_cast<uint8_t*>(lp + (size_t)r * s) : d->dst(r2, q);
-      const int64_t nv = std::max<int64_t>(0, std::min<int64_t>(n_valid - (int64_t)r * s, s));
-      reduce_update_at(p, c, gdt, d->src_base(r1), d->src_stride(), N, r, g + (size_t)r * s * esize(gdt), master, mom,
-                       (int64_t)r * s, (size_t)nv, out, N, (size_t)s, true, st);
+      reduce_update_at(req, c, d->src_base(r1), d->src_stride(), N, r, g + (size_t)r * s * esize(gdt), (int64_t)r * s,
+                       (size_t)valid_in(req.n_valid, (int64_t)r * s, s), out, N, (size_t)s, true, st);
       d->release(r1, st);
       tag_sent(r2, "mesh_reduce", wb);
     }
@@ -504,22 +507,20 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineL
   counters_.direct_rounds += 2;
   const uint8_t* Gv = d->src_base(r2);
   const size_t gstride = d->src_stride();
-  const int64_t n_pad = L.n_pad;
-  if (defer) {
+  if (req.defer) {
     uint8_t* G = epi_scratch("mesh_G" + std::to_string(sb * N), sb * N);
     std::vector<P2PCopy> segs;
     for (int q = 0; q < N; ++q) segs.push_back({Gv + (size_t)q * gstride, G + (size_t)q * sb, sb});
     d->move(segs, st);
     d->release(r2, st);
-    return {[=](hipStream_t es) { epilogue(c, es, G, s, N, 0, n_pad, master, lp, mom, n_valid, p, update, out_sum); }};
+    return {make_epilogue(req, G, s, N, 0, L.n_pad)};
   }
   mark(kTpCommEnd);
   {
     RoctxRange rr("fan/mesh/direct_epilogue");
-    const int64_t nv = std::max<int64_t>(0, std::min<int64_t>(n_valid, n_pad));
-    if (update && nv > 0)
-      update_at(p, c, Gv, (size_t)s, N, -1, 0, master, lp, mom, 0, (size_t)nv, st, gstride);
-    if (out_sum) launch_wire_unpack_strided(c, kF32, Gv, gstride, out_sum, (size_t)s, N, st);
+    const int64_t nv = valid_in(req.n_valid, 0, L.n_pad);
+    if (req.update && nv > 0) update_at(req, c, Gv, (size_t)s, N, -1, 0, 0, (size_t)nv, st, gstride);
+    if (req.out_sum) launch_wire_unpack_strided(c, kF32, Gv, gstride, req.out_sum, (size_t)s, N, st);
   }
   d->release(r2, st);
   return {};
@@ -537,23 +538,22 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineL
 //   S[c%2] rewritten by reduce(c+2) after all_gather(c): all_gather(c) precedes all_to_all(c+2) on the comm stream
 //   G[c%2] rewritten by all_gather(c+2) after epilogue(c): reduce(c+2), which all_gather(c+2) waits for, follows
 //   epilogue(c) on the aux stream.
-std::vector<EpiThunk> AllReduceEngine::run_mesh_chunked(const EngineLayout& L, const void* grad, int gdt,
-                                                        float* master, bf16_t* lp, float* mom, int64_t n_valid,
-                                                        UpdateParams p, bool update, float* out_sum,
-                                                        const uint8_t* prepacked, bool defer) {
-  const int N = world_, r = rank_, c = cfg_.codec;
+std::vector<EpiThunk> AllReduceEngine::run_mesh_chunked(const EngineLayout& L, const EngineRequest& req) {
+  const int N = world_, r = rank_, c = cfg_.codec, gdt = req.grad_dtype;
   const int64_t s = L.shard, C = L.chunks;
   const size_t sb = wire_shard_bytes(c, s), cb = sb * N;  // one shard / one chunk of wire
-  const uint8_t* g = reinterpret_cast<const uint8_t*>(grad);
-  hipStream_t A = run_stream_, B = aux_stream_;
-  const bool zero_copy = (c == kRawF32 && gdt == kF32) || (c == kRawBf16 && gdt == kBF16);
+  const uint8_t* g = reinterpret_cast<const uint8_t*>(req.grad);
+  const uint8_t* prepacked = req.prepacked;
+  const bool defer = req.defer;
+  hipStream_t A = cur_.run, B = aux_stream_;
+  const bool raw = zero_copy(c, gdt);
   const std::string k = std::to_string(sb);
   uint8_t *Pb[2] = {nullptr, nullptr}, *R[2], *S[2], *Gc[2] = {nullptr, nullptr};
   for (int q = 0; q < 2; ++q) {
-    if (!zero_copy && !prepacked) Pb[q] = scratch("meshc_P" + std::to_string(q) + "_" + k, cb);
-    R[q] = scratch("meshc_R" + std::to_string(q) + "_" + k, cb);
-    S[q] = scratch("meshc_S" + std::to_string(q) + "_" + k, sb);
-    if (!defer) Gc[q] = scratch("meshc_G" + std::to_string(q) + "_" + k, cb);
+    if (!raw && !prepacked) Pb[q] = scratch("meshc_P" + std::to_string(q) + "_" + k, cb, A);
+    R[q] = scratch("meshc_R" + std::to_string(q) + "_" + k, cb, A);
+    S[q] = scratch("meshc_S" + std::to_string(q) + "_" + k, sb, A);
+    if (!defer) Gc[q] = scratch("meshc_G" + std::to_string(q) + "_" + k, cb, A);
   }
   // A deferred request's epilogue reads the whole gathered bucket at commit. One such buffer per bucket size is
   // shared by every deferred chunked request (not one per slot: 17 B per 16 elements of a multi-GB bucket, 8 times
@@ -566,41 +566,34 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_chunked(const EngineLayout& L, c
     if (gb.free == nullptr) FAN_HIP_CHECK(hipEventCreateWithFlags(&gb.free, hipEventDisableTiming));
     if (gb.seq != 0) {
       const auto& prev = table_->slot(gb.slot);
-      if (prev.seq == gb.seq && prev.pending && gb.slot != epi_slot_) {
+      if (prev.seq == gb.seq && prev.pending && gb.slot != cur_.slot) {
         counters_.forced_commits++;
-        table_->commit(gb.slot, true, cur_producer_, gb.seq);
+        table_->commit(gb.slot, true, cur_.producer, gb.seq);
       }
       FAN_HIP_CHECK(hipStreamWaitEvent(A, gb.free, 0));  // recorded after that epilogue (no-op if it never ran)
     }
-    gb.slot = epi_slot_;
-    gb.seq = req_seq_;
-    Gall = scratch("meshc_Gall_" + k + "_" + std::to_string(C), cb * C);
+    gb.slot = cur_.slot;
+    gb.seq = cur_.seq;
+    Gall = scratch("meshc_Gall_" + k + "_" + std::to_string(C), cb * C, A);
     gall_free = gb.free;
   }
   auto gath = [&](int64_t ch) { return defer ? Gall + ch * cb : Gc[ch % 2]; };
   auto gather = [&](int64_t ch) {  // comm stream: all-gather of chunk ch's reduced owner shard
     RoctxRange rr("fan/mesh/all_gather");
     FAN_HIP_CHECK(hipStreamWaitEvent(A, cev_[1][ch % 2], 0));
-    if (verify_) launch_msg_tags(S[ch % 2], sb, sb, 1, req_seq_, tag_region(3), A);
-    fault_.maybe_corrupt("mesh_reduce", S[ch % 2], sb, A);
-    comm_->all_gather(S[ch % 2], gath(ch), sb, A);
-    count_peers(sb);
-    if (verify_) {
-      comm_->all_gather(tag_region(3), tag_region(4), 16, A);
-      verify_rows(gath(ch), sb, N, tag_region(4), kSiteMeshAllGather, (uint32_t)(ch * N), A);
-    }
+    all_gather_checked(S[ch % 2], gath(ch), sb, kSiteMeshAllGather, (uint32_t)(ch * N), A);
     if (!defer) {  // per-chunk epilogue on the aux stream
       FAN_HIP_CHECK(hipEventRecord(cev_[2][ch % 2], A));
       FAN_HIP_CHECK(hipStreamWaitEvent(B, cev_[2][ch % 2], 0));
       RoctxRange re("fan/mesh/epilogue");
-      epilogue(c, B, gath(ch), s, N, ch * N * s, N * s, master, lp, mom, n_valid, p, update, out_sum);
+      epilogue(req, c, B, gath(ch), s, N, ch * N * s, N * s);
     }
   };
   for (int64_t ch = 0; ch < C; ++ch) {
     const uint8_t* P;
     if (prepacked) {
       P = prepacked + ch * cb;
-    } else if (zero_copy) {
+    } else if (raw) {
       P = g + (size_t)ch * N * s * esize(gdt);
     } else {
       RoctxRange rr("fan/mesh/pack");
@@ -610,14 +603,7 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_chunked(const EngineLayout& L, c
     {
       RoctxRange rr("fan/mesh/all_to_all");
       if (ch >= 2) FAN_HIP_CHECK(hipStreamWaitEvent(A, cev_[1][ch % 2], 0));  // reduce(ch-2) done with R, P
-      if (verify_) launch_msg_tags(P, sb, sb, N, req_seq_, tag_region(0), A);
-      fault_.maybe_corrupt("mesh_pack", const_cast<uint8_t*>(P), cb, A);
-      comm_->all_to_all(P, R[ch % 2], sb, A);
-      count_peers(sb);
-      if (verify_) {
-        comm_->all_to_all(tag_region(0), tag_region(1), 16, A);
-        verify_rows(R[ch % 2], sb, N, tag_region(1), kSiteMeshAllToAll, (uint32_t)(ch * N), A);
-      }
+      all_to_all_checked(P, R[ch % 2], sb, (uint32_t)(ch * N), A);
       FAN_HIP_CHECK(hipEventRecord(cev_[0][ch % 2], A));
     }
     {
@@ -634,73 +620,64 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_chunked(const EngineLayout& L, c
   FAN_HIP_CHECK(hipEventRecord(cev_[3][1], B));
   FAN_HIP_CHECK(hipStreamWaitEvent(A, cev_[3][1], 0));
   if (!defer) return {};
-  const int64_t n_pad = L.n_pad, shards = C * N;
-  uint8_t* G = Gall;
+  const EpiThunk epi = make_epilogue(req, Gall, s, (int)(C * N), 0, L.n_pad);
   return {[=](hipStream_t es) {
-    epilogue(c, es, G, s, (int)shards, 0, n_pad, master, lp, mom, n_valid, p, update, out_sum);
+    epi(es);
     FAN_HIP_CHECK(hipEventRecord(gall_free, es));  // the shared gathered wire may be reused after this point
   }};
 }
 
-std::vector<EpiThunk> AllReduceEngine::run_ring(const EngineLayout& L, const void* grad, int gdt,
-                                                             float* master, bf16_t* lp, float* mom, int64_t n_valid,
-                                                             UpdateParams p, bool update, float* out_sum,
-                                                             const uint8_t* prepacked, int64_t prepacked_elems) {
-  const int N = world_, c = cfg_.codec;
+std::vector<AllReduceEngine::RingLane> AllReduceEngine::ring_lanes(const EngineLayout& L) const {
+  const int N = world_;
+  std::vector<RingLane> lanes;
+  for (size_t i = 0; i < orders_.size(); ++i) {
+    const auto& o = orders_[i];
+    int pos = 0;
+    for (int q = 0; q < N; ++q)
+      if (o[q] == rank_) pos = q;
+    lanes.push_back({(int64_t)i * L.part, pos, o[(pos - 1 + N) % N], o[(pos + 1) % N], ring_plan(N, pos, L.blocks)});
+  }
+  return lanes;
+}
+
+std::vector<EpiThunk> AllReduceEngine::run_ring(const EngineLayout& L, const EngineRequest& req) {
+  const int N = world_, c = cfg_.codec, gdt = req.grad_dtype;
   const int64_t S = L.slice;
   const size_t sb = wire_shard_bytes(c, S);
   const int64_t nsl = L.blocks * N;
-  const uint8_t* g = reinterpret_cast<const uint8_t*>(grad);
-  hipStream_t st = run_stream_;
-  const bool compat = cfg_.compat_owner_fp32 && N > 1 && update;
+  const uint8_t* g = reinterpret_cast<const uint8_t*>(req.grad);
+  const uint8_t* prepacked = req.prepacked;
+  hipStream_t st = cur_.run;
+  const bool compat = cfg_.compat_owner_fp32 && N > 1 && req.update;
   if (prepacked)  // encode what the producer did not (bias gradient + padding): slice-sized shards (sub-shards when
                   // the direct ring streams its hops), ring-major
-    launch_wire_pack_range(c, gdt, grad, const_cast<uint8_t*>(prepacked), (size_t)(S / L.sub), (size_t)prepacked_elems,
-                           (size_t)L.n_pad, st);
-  if (P2PComm* d = comm_ ? comm_->direct() : nullptr; d && N > 1 && !compat)
-    return run_ring_direct(d, L, grad, gdt, master, lp, mom, n_valid, p, update, out_sum, prepacked);
-  struct RingState {
-    int64_t off;
-    int down, up, pos;
-    std::vector<RingRound> plan;
+    launch_wire_pack_range(c, gdt, req.grad, const_cast<uint8_t*>(prepacked), (size_t)(S / L.sub),
+                           (size_t)req.prepacked_elems, (size_t)L.n_pad, st);
+  if (P2PComm* d = comm_ ? comm_->direct() : nullptr; d && N > 1 && !compat) return run_ring_direct(d, L, req);
+  struct RingState : RingLane {
     uint8_t *G, *send, *recv[2];
     const uint8_t* last_partial;
     float* fp32;
   };
   std::vector<RingState> rings;
   const std::string k = std::to_string(sb) + "_" + std::to_string(nsl);
-  for (size_t i = 0; i < orders_.size(); ++i) {
-    const auto& o = orders_[i];
-    int pos = 0;
-    for (int q = 0; q < N; ++q)
-      if (o[q] == rank_) pos = q;
-    RingState rs;
-    rs.off = (int64_t)i * L.part;
-    rs.pos = pos;
-    rs.down = o[(pos - 1 + N) % N];
-    rs.up = o[(pos + 1) % N];
-    rs.plan = ring_plan(N, pos, L.blocks);
-    rs.G = epi_scratch("ring_G" + std::to_string(i) + "_" + k, sb * nsl);
-    rs.send = scratch("ring_send" + std::to_string(i) + "_" + k, sb);
-    rs.recv[0] = scratch("ring_recv0_" + std::to_string(i) + "_" + k, sb);
-    rs.recv[1] = scratch("ring_recv1_" + std::to_string(i) + "_" + k, sb);
+  for (RingLane& lane : ring_lanes(L)) {
+    const std::string i = std::to_string(rings.size());
+    RingState rs{std::move(lane)};
+    rs.G = epi_scratch("ring_G" + i + "_" + k, sb * nsl);
+    rs.send = scratch("ring_send" + i + "_" + k, sb, st);
+    rs.recv[0] = scratch("ring_recv0_" + i + "_" + k, sb, st);
+    rs.recv[1] = scratch("ring_recv1_" + i + "_" + k, sb, st);
     rs.last_partial = nullptr;
-    rs.fp32 = compat ? reinterpret_cast<float*>(epi_scratch("ring_fp32_" + std::to_string(i) + "_" + k, 4 * S * L.blocks))
-                     : nullptr;
-    rings.push_back(rs);
-  }
-  const size_t nrows = rings[0].plan.size();
-  std::vector<std::vector<size_t>> rounds;
-  for (size_t j = 0; j < nrows; ++j) {  // a SEND_LOCAL row joins the previous round (OUTPUT_SEND overlap)
-    if (!rounds.empty() && j > 0 && rings[0].plan[j].send_src == kSendLocal) rounds.back().push_back(j);
-    else rounds.push_back({j});
+    rs.fp32 = compat ? reinterpret_cast<float*>(epi_scratch("ring_fp32_" + i + "_" + k, 4 * S * L.blocks)) : nullptr;
+    rings.push_back(std::move(rs));
   }
   auto local = [&](const RingState& rs, int64_t x) { return g + (size_t)(rs.off + x * S) * esize(gdt); };
   uint32_t round_id = 0;
-  for (const auto& rnd : rounds) {
+  for (const auto& rnd : ring_rounds(rings[0].plan)) {
     RoctxRange rr("fan/ring/round");
     if (N > 1) {  // no credit phase on a copying transport: points 0 and 1 coincide; then kernels, exchange
-      if (cur_trace_ >= 0) trace_pool_[cur_trace_].hop_kernel_first = true;
+      if (cur_.trace >= 0) trace_pool_[cur_.trace].hop_kernel_first = true;
       hop_mark(0);
       hop_mark(1);
     }
@@ -744,7 +721,7 @@ std::vector<EpiThunk> AllReduceEngine::run_ring(const EngineLayout& L, const voi
       if (verify_) {  // one tag per message, sent after all of the round's payloads (per-peer order is kept)
         FAN_CHECK(nd <= (size_t)kTagRows && nr <= (size_t)kTagRows, "verify: too many messages in a ring round");
         for (size_t q = 0; q < nd; ++q) {
-          launch_msg_tags(static_cast<const uint8_t*>(sends[q].ptr), sb, sb, 1, req_seq_, tag_region(0) + q * 4, st);
+          launch_msg_tags(static_cast<const uint8_t*>(sends[q].ptr), sb, sb, 1, cur_.seq, tag_region(0) + q * 4, st);
           sends.push_back({tag_region(0) + q * 4, 16, sends[q].peer});
         }
         for (size_t q = 0; q < nr; ++q) recvs.push_back({tag_region(1) + q * 4, 16, recvs[q].peer});
@@ -765,23 +742,23 @@ std::vector<EpiThunk> AllReduceEngine::run_ring(const EngineLayout& L, const voi
   }
   std::vector<EpiThunk> thunks;
   for (auto& rs : rings) {
-    const int64_t off = rs.off, part = L.part, blocks = L.blocks;
-    uint8_t* G = rs.G;
-    if (compat) {
-      const int own = (rs.pos - 1 + N) % N;
-      float* f32 = rs.fp32;
-      thunks.push_back([=](hipStream_t es) {
-        epilogue(c, es, G, S, (int)nsl, off, part, master, lp, mom, n_valid, p, update, out_sum, own, N);
-        for (int64_t b = 0; b < blocks; ++b) {
-          const int64_t o2 = off + (b * N + own) * S;
-          const int64_t nv = std::max<int64_t>(0, std::min<int64_t>(n_valid - o2, S));
-          if (nv > 0)
-            update_at(p, kRawF32, f32 + b * S, (size_t)S, 1, -1, 0, master, lp, mom, o2, (size_t)nv, es);
-        }
-      });
-    } else {
-      thunks.push_back([=](hipStream_t es) { epilogue(c, es, G, S, (int)nsl, off, part, master, lp, mom, n_valid, p, update, out_sum); });
+    if (!compat) {
+      thunks.push_back(make_epilogue(req, rs.G, S, (int)nsl, rs.off, L.part));
+      continue;
     }
+    // the owner of each slice updates it from the un-quantised f32 sum instead of the wire
+    const int own = (rs.pos - 1 + N) % N;
+    const EpiThunk rest = make_epilogue(req, rs.G, S, (int)nsl, rs.off, L.part, own, N);
+    const int64_t off = rs.off, blocks = L.blocks;
+    float* f32 = rs.fp32;
+    thunks.push_back([=](hipStream_t es) {
+      rest(es);
+      for (int64_t b = 0; b < blocks; ++b) {
+        const int64_t o2 = off + (b * N + own) * S;
+        const int64_t nv = valid_in(req.n_valid, o2, S);
+        if (nv > 0) update_at(req, kRawF32, f32 + b * S, (size_t)S, 1, -1, 0, o2, (size_t)nv, es);
+      }
+    });
   }
   return thunks;
 }
@@ -806,11 +783,8 @@ std::vector<EpiThunk> AllReduceEngine::run_ring(const EngineLayout& L, const voi
 // Verify mode tags message k of a sub-round in its slot trailer (tag k) after the kernels and checks every message
 // before the kernels that read it (site "ring direct hop", row = the sub-round it was sent in). Traced requests
 // record four device timestamps per sub-round (hop_mark): start, credits granted, upstream data ready, kernels done.
-std::vector<EpiThunk> AllReduceEngine::run_ring_direct(P2PComm* d, const EngineLayout& L, const void* grad, int gdt,
-                                                       float* master, bf16_t* lp, float* mom, int64_t n_valid,
-                                                       UpdateParams p, bool update, float* out_sum,
-                                                       const uint8_t* prepacked) {
-  const int N = world_, c = cfg_.codec;
+std::vector<EpiThunk> AllReduceEngine::run_ring_direct(P2PComm* d, const EngineLayout& L, const EngineRequest& req) {
+  const int N = world_, c = cfg_.codec, gdt = req.grad_dtype;
   const int P = L.sub;
   const int64_t S = L.slice, Sp = S / P;
   const size_t sb = wire_shard_bytes(c, Sp);  // one message: one sub-shard
@@ -818,12 +792,10 @@ std::vector<EpiThunk> AllReduceEngine::run_ring_direct(P2PComm* d, const EngineL
   FAN_CHECK(S % (256 * (int64_t)P) == 0 && P <= d->depth() - 1, "p2p ring: bad sub-slice geometry");
   FAN_CHECK(2 * msg <= d->payload_bytes(), "p2p ring: two slices per round must fit an arena slot (lower max_slice_elems)");
   const int64_t nsl = L.blocks * N, nsh = nsl * P;  // slices / wire (sub-)shards per ring part
-  const uint8_t* g = reinterpret_cast<const uint8_t*>(grad);
-  hipStream_t st = run_stream_;
-  struct RS {
-    int64_t off;
-    int down, up;
-    std::vector<RingRound> plan;
+  const uint8_t* g = reinterpret_cast<const uint8_t*>(req.grad);
+  const uint8_t* prepacked = req.prepacked;
+  hipStream_t st = cur_.run;
+  struct RS : RingLane {
     uint8_t* G;
   };
   struct Rx {
@@ -835,27 +807,14 @@ std::vector<EpiThunk> AllReduceEngine::run_ring_direct(P2PComm* d, const EngineL
   std::vector<RS> rings;
   std::vector<int> downs, ups;
   const std::string k = std::to_string(sb) + "_" + std::to_string(nsh);
-  for (size_t i = 0; i < orders_.size(); ++i) {
-    const auto& o = orders_[i];
-    int pos = 0;
-    for (int q = 0; q < N; ++q)
-      if (o[q] == rank_) pos = q;
-    RS rs;
-    rs.off = (int64_t)i * L.part;
-    rs.down = o[(pos - 1 + N) % N];
-    rs.up = o[(pos + 1) % N];
-    rs.plan = ring_plan(N, pos, L.blocks);
-    rs.G = epi_scratch("ring_G" + std::to_string(i) + "_" + k, sb * nsh);
+  for (RingLane& lane : ring_lanes(L)) {
+    RS rs{std::move(lane)};
+    rs.G = epi_scratch("ring_G" + std::to_string(rings.size()) + "_" + k, sb * nsh);
     downs.push_back(rs.down);
     ups.push_back(rs.up);
-    rings.push_back(rs);
+    rings.push_back(std::move(rs));
   }
-  const size_t nrows = rings[0].plan.size();
-  std::vector<std::vector<size_t>> rounds;
-  for (size_t j = 0; j < nrows; ++j) {  // a SEND_LOCAL row joins the previous round (OUTPUT_SEND overlap)
-    if (!rounds.empty() && j > 0 && rings[0].plan[j].send_src == kSendLocal) rounds.back().push_back(j);
-    else rounds.push_back({j});
-  }
+  const std::vector<std::vector<size_t>> rounds = ring_rounds(rings[0].plan);
   // local f32 / bf16 elements of sub-slice s of slice x
   auto local = [&](const RS& rs, int64_t x, int s) { return g + (size_t)(rs.off + x * S + (int64_t)s * Sp) * esize(gdt); };
   auto gsub = [&](const RS& rs, int64_t x, int s) { return rs.G + (size_t)(x * P + s) * sb; };  // G sub-shard
@@ -870,7 +829,7 @@ std::vector<EpiThunk> AllReduceEngine::run_ring_direct(P2PComm* d, const EngineL
       }
   };
   if (counters_.peer_bytes.size() != (size_t)world_) counters_.peer_bytes.assign(world_, 0);
-  if (cur_trace_ >= 0) trace_pool_[cur_trace_].hop_kernel_first = false;  // points: credit, ready, kernels
+  if (cur_.trace >= 0) trace_pool_[cur_.trace].hop_kernel_first = false;  // points: credit, ready, kernels
   // got[s][ring]: the messages sub-round (t - 1, s) delivered, consumed by (t, s)
   std::vector<std::vector<std::vector<Rx>>> got(P, std::vector<std::vector<Rx>>(rings.size()));
   for (size_t t = 0; t < rounds.size(); ++t) {
@@ -967,11 +926,7 @@ std::vector<EpiThunk> AllReduceEngine::run_ring_direct(P2PComm* d, const EngineL
     d->release_from(sub_round[jj], ups, st);
   }
   std::vector<EpiThunk> thunks;
-  for (auto& rs : rings) {
-    const int64_t off = rs.off, part = L.part;
-    uint8_t* G = rs.G;
-    thunks.push_back([=](hipStream_t es) { epilogue(c, es, G, Sp, (int)nsh, off, part, master, lp, mom, n_valid, p, update, out_sum); });
-  }
+  for (auto& rs : rings) thunks.push_back(make_epilogue(req, rs.G, Sp, (int)nsh, rs.off, L.part));
   return thunks;
 }
 
@@ -997,7 +952,7 @@ void AllReduceEngine::gather_owned(float* plane, int64_t n) {
   size_t max_bytes = (size_t)s * 4;
   if (P2PComm* d = comm_->direct()) max_bytes = std::min(max_bytes, d->payload_bytes() / 256 * 256);
   const int64_t piece = std::max<int64_t>(64, (int64_t)(max_bytes / 4) / 64 * 64);
-  uint8_t* G = scratch("gather_owned", (size_t)N * piece * 4);
+  uint8_t* G = scratch("gather_owned", (size_t)N * piece * 4, st);
   for (int64_t off = 0; off < s; off += piece) {
     const int64_t k = std::min(piece, s - off);
     comm_->all_gather(plane + (size_t)r * s + off, G, (size_t)k * 4, st);
@@ -1023,88 +978,70 @@ void AllReduceEngine::verify_direct(const uint8_t* msg, size_t bytes, const uint
 }
 
 void AllReduceEngine::hop_mark(int point) {
-  if (cur_trace_ < 0) return;
+  if (cur_.trace < 0) return;
   if (hop_used_ == hop_pool_.size()) {
     hipEvent_t e;
     FAN_HIP_CHECK(hipEventCreate(&e));
     hop_pool_.push_back(e);
   }
-  RequestTrace& t = trace_pool_[cur_trace_];
+  RequestTrace& t = trace_pool_[cur_.trace];
   if (t.hop_count == 0) t.hop_first = hop_used_;
-  FAN_HIP_CHECK(hipEventRecord(hop_pool_[hop_used_++], run_stream_));
+  FAN_HIP_CHECK(hipEventRecord(hop_pool_[hop_used_++], cur_.run));
   t.hop_count++;
   (void)point;
 }
 
-int AllReduceEngine::submit(const void* grad, int grad_dtype, float* master, bf16_t* lp, float* mom, int64_t n_valid,
-                            SgdParams sgd, hipStream_t producer, bool defer, bool update, float* out_sum,
-                            const uint8_t* prepacked, int64_t prepacked_elems, int64_t layout_shard,
-                            int64_t layout_chunks, bool on_producer, const AdamWParams* adamw) {
+int AllReduceEngine::submit(const EngineRequest& req, hipStream_t producer) {
   RoctxRange rr("fan/allreduce/submit");
-  UpdateParams upd;
-  upd.sgd = sgd;
-  if (adamw != nullptr) {
-    FAN_CHECK(!update || (mom != nullptr && adamw->var != nullptr), "AdamW needs both moment planes");
-    upd.kind = kOptAdamW;
-    upd.adamw = *adamw;
-  }
+  cur_ = Current{};
+  FAN_CHECK(req.upd.kind != kOptAdamW || !req.update || (req.mom != nullptr && req.upd.adamw.var != nullptr),
+            "AdamW needs both moment planes");
   FAN_HIP_CHECK(hipSetDevice(device_));
   // slot state machine (slot_table.h): the next slot (a still-deferred occupant is committed first, ordered after
   // the producer: the NIC's 8-deep command queue never drops a request), ordering after anything that may still
   // read the slot's buffers, and the stream this request's communication phase runs on
-  const SlotTable<HipSlotDevice>::Begin b = table_->begin(producer, on_producer && !inline_);
-  const int slot = b.slot;
-  req_seq_ = b.seq;  // the sequence number this request will get (its messages' tags carry it)
+  const SlotTable<HipSlotDevice>::Begin b = table_->begin(producer, req.on_producer && !inline_);
+  cur_.run = b.run;
+  cur_.producer = producer;
+  cur_.slot = b.slot;  // also keys the buffers a deferred epilogue reads (epi_scratch)
+  cur_.seq = b.seq;    // the sequence number this request will get
   submitted_++;
-  const EngineLayout L = layout(n_valid, layout_shard, layout_chunks);
-  cur_producer_ = producer;
-  run_stream_ = b.run;
-  SlotExtra& x = extra_[slot];
+  const EngineLayout L = layout(req.n_valid, req.layout_shard, req.layout_chunks);
+  SlotExtra& x = extra_[b.slot];
   x.timed = timing_;
   x.counted = false;
-  if (x.timed) FAN_HIP_CHECK(hipEventRecord(x.t0, run_stream_));
+  if (x.timed) FAN_HIP_CHECK(hipEventRecord(x.t0, cur_.run));
   const int64_t wb = wire_bytes(L);
   counters_.requests++;
-  counters_.logical_bytes += n_valid * 4;
+  counters_.logical_bytes += req.n_valid * 4;
   counters_.wire_bytes += wb;
   x.trace = -1;
-  cur_trace_ = -1;
   if (tracing_) {
     if (trace_used_ < trace_pool_.size()) {
-      x.trace = cur_trace_ = (int)trace_used_++;
-      trace_pool_[cur_trace_].hop_count = 0;
-      trace_pool_[cur_trace_].logical_bytes = n_valid * 4;
-      trace_pool_[cur_trace_].wire_bytes = wb;
+      x.trace = cur_.trace = (int)trace_used_++;
+      trace_pool_[cur_.trace].hop_count = 0;
+      trace_pool_[cur_.trace].logical_bytes = req.n_valid * 4;
+      trace_pool_[cur_.trace].wire_bytes = wb;
       mark(kTpStart);
     } else {
       trace_dropped_++;
     }
   }
-  if (prepacked) {
+  if (req.prepacked) {
     FAN_CHECK(cfg_.codec == kBfpTrunc || cfg_.codec == kBfpRne, "prepacked input needs a BFP codec");
-    FAN_CHECK(prepacked_elems % 16 == 0 && prepacked_elems <= L.n_pad, "bad prepacked_elems");
+    FAN_CHECK(req.prepacked_elems % 16 == 0 && req.prepacked_elems <= L.n_pad, "bad prepacked_elems");
   }
-  // buffers the deferred epilogue reads are per slot: a later request of the same size must not overwrite
-  // them before this one commits (the trainer commits every request at the end of backward)
-  epi_slot_ = slot;
-  cur_defer_ = defer;
-  trace_marked_ = 1u << kTpStart;
-  std::vector<EpiThunk> thunks =
-      cfg_.algo == 0 ? run_mesh(L, grad, grad_dtype, master, lp, mom, n_valid, upd, update, out_sum, prepacked,
-                                prepacked_elems)
-                     : run_ring(L, grad, grad_dtype, master, lp, mom, n_valid, upd, update, out_sum, prepacked,
-                                prepacked_elems);
+  std::vector<EpiThunk> thunks = cfg_.algo == 0 ? run_mesh(L, req) : run_ring(L, req);
   FAN_HIP_CHECK(hipGetLastError());
   // phases this schedule does not have (ring hops, the world-1 local path) collapse onto the end of comm
   for (int tp = kTpPacked; tp <= kTpCommEnd; ++tp)
-    if (!(trace_marked_ & (1u << tp))) mark(tp);
+    if (!(cur_.marked & (1u << tp))) mark(tp);
   // verify mode: the device error block's host mirror, refreshed after every request's communication phase
-  if (verify_) FAN_HIP_CHECK(hipMemcpyAsync(verr_host_, verr_dev_, sizeof(VerifyError), hipMemcpyDeviceToHost, run_stream_));
-  cur_trace_ = -1;
+  if (verify_) FAN_HIP_CHECK(hipMemcpyAsync(verr_host_, verr_dev_, sizeof(VerifyError), hipMemcpyDeviceToHost, cur_.run));
   x.t_issue = now_s();
-  table_->set_keep_done(slot, x.timed || x.trace >= 0);  // timed / traced: a real done point, not a lazy one
-  table_->end(slot, std::move(thunks), defer);  // comm_done, sequence number; an immediate request commits now
-  return slot;
+  table_->set_keep_done(b.slot, x.timed || x.trace >= 0);  // timed / traced: a real done point, not a lazy one
+  table_->end(b.slot, std::move(thunks), req.defer);  // comm_done, sequence number; an immediate request commits now
+  return b.slot;
 }
 
 void AllReduceEngine::commit(int slot, bool after_producer, hipStream_t producer, uint32_t seq) {
@@ -1278,7 +1215,8 @@ void AllReduceEngine::synchronize(int slot, double timeout_s, uint32_t seq) {
 
 void AllReduceEngine::verify_rows(const uint8_t* rows, size_t row_bytes, int nrows, const uint32_t* recv_tags,
                                   uint32_t site, uint32_t row_base, hipStream_t st) {
-  launch_msg_verify(rows, row_bytes, row_bytes, nrows, recv_tags, req_seq_, tag_region(2), verr_dev_, site, row_base, st);
+  launch_msg_verify(rows, row_bytes, row_bytes, nrows, recv_tags, cur_.seq, tag_region(2), verr_dev_, site, row_base,
+                    st);
   counters_.verified_rows += (uint64_t)nrows;
 }
 
@@ -1289,8 +1227,8 @@ void AllReduceEngine::check_verify() {
   const VerifyError e = *verr_host_;
   std::ostringstream os;
   os << "verify: message " << (e.kind == 1 ? "corrupted" : "out of sequence (dropped or reordered)") << " in "
-      << sites[e.site < 7 ? e.site : 0] << " row " << e.row << " (checksum " << e.got_s1 << " vs tag " << e.exp_s1
-     << ", request " << e.got_seq << " vs expected " << e.exp_seq << ") [rank=" << rank_ << " world=" << world_ << "]";
+     << sites[e.site < sizeof(sites) / sizeof(*sites) ? e.site : 0] << " row " << e.row << " (checksum " << e.got_s1
+     << " vs tag " << e.exp_s1 << ", request " << e.got_seq << " vs expected " << e.exp_seq << ") [rank=" << rank_ << " world=" << world_ << "]";
   throw std::runtime_error(os.str());
 }
 

@@ -117,7 +117,7 @@ struct TraceSummary {
   double hop_credit_ms = 0.0, hop_kernel_ms = 0.0, hop_ready_ms = 0.0, hop_max_ms = 0.0;
 };
 
-// verify-error sites (VerifyError::site): copying paths 1-3, direct P2P paths 4-6
+// verify-error sites (VerifyError::site): copying paths 1-3 and 7, direct P2P paths 4-6
 enum VerifySite : uint32_t {
   kSiteMeshAllToAll = 1,
   kSiteMeshAllGather = 2,
@@ -136,6 +136,34 @@ struct UpdateParams {
   int kind = kOptSgd;
   SgdParams sgd{};
   AdamWParams adamw{};
+};
+
+// One all-reduce request, as submit() takes it and every schedule passes it on. grad: padded flat buffer (f32 or
+// bf16) ready on the producer stream. If `defer`, the weight update is enqueued later by commit(); otherwise
+// immediately. upd.kind == kOptAdamW: `mom` is the first moment and upd.adamw.var the second, both required and laid
+// out as master.
+// prepacked (BFP codecs): the producer already encoded flat elements [0, prepacked_elems) of the bucket into
+// `prepacked` (shard layout of prepack_shape(): mesh shards, or ring slices ring-major); the engine packs the
+// rest (bias + padding) and skips its own encode of them (mesh: the pack pass, and at world 1 the reduce pass;
+// ring: every SEND_LOCAL). The shards prepack_shape() names as owned must also be present in f32 in `grad`
+// (mesh: the owner shard; ring: all of them).
+struct EngineRequest {
+  const void* grad = nullptr;
+  int grad_dtype = kF32;
+  float* master = nullptr;
+  bf16_t* lp = nullptr;
+  float* mom = nullptr;
+  int64_t n_valid = 0;
+  UpdateParams upd{};
+  bool update = true;
+  float* out_sum = nullptr;
+  const uint8_t* prepacked = nullptr;
+  int64_t prepacked_elems = 0;
+  bool defer = false;
+  // read by submit() only: explicit layout (layout()), and on_producer (multi-rank): the communication phase runs on
+  // the producer stream itself (SlotTable::begin), not the comm stream
+  int64_t layout_shard = 0, layout_chunks = 0;
+  bool on_producer = false;
 };
 
 // Deferred epilogue of a request (decode + SGD), launched on the given stream at commit().
@@ -186,20 +214,8 @@ class AllReduceEngine {
   // momentum) in place, in pieces that fit the transport; checkpoints and replica checks call it. Host-blocking.
   void gather_owned(float* plane, int64_t n);
 
-  // Enqueue the communication phase of a request. grad: padded flat buffer (f32 or bf16) ready on `producer`.
-  // on_producer (multi-rank): the phase runs on the producer stream itself (SlotTable::begin), not the comm stream.
-  // If `defer`, the weight update is enqueued later by commit(); otherwise immediately. Returns the slot.
-  // prepacked (BFP codecs): the producer already encoded flat elements [0, prepacked_elems) of the bucket into
-  // `prepacked` (shard layout of prepack_shape(): mesh shards, or ring slices ring-major); the engine packs the
-  // rest (bias + padding) and skips its own encode of them (mesh: the pack pass, and at world 1 the reduce pass;
-  // ring: every SEND_LOCAL). The shards prepack_shape() names as owned must also be present in f32 in `grad`
-  // (mesh: the owner shard; ring: all of them).
-  int submit(const void* grad, int grad_dtype, float* master, bf16_t* lp, float* mom, int64_t n_valid,
-             SgdParams sgd, hipStream_t producer, bool defer, bool update = true, float* out_sum = nullptr,
-             const uint8_t* prepacked = nullptr, int64_t prepacked_elems = 0, int64_t layout_shard = 0,
-             int64_t layout_chunks = 0, bool on_producer = false, const AdamWParams* adamw = nullptr);
-  // adamw: the update is AdamW with these scalars (`sgd` is ignored, `mom` is the first moment and adamw->var the
-  // second, both required and laid out as master).
+  // Enqueue the communication phase of a request whose gradient is ready on `producer`. Returns the slot.
+  int submit(const EngineRequest& req, hipStream_t producer);
   // (shard elements, shards, owner shard whose f32 values the reduce needs or -1) for a prepacked bucket,
   // or shard elements 0 when this configuration cannot take prepacked input.
   std::array<int64_t, 3> prepack_shape(int64_t n) const;
@@ -252,57 +268,7 @@ class AllReduceEngine {
   }
 
  private:
-  // Per-slot engine data beside the state machine (slot_table.h holds sequence / pending / streams / events).
-  struct SlotExtra {
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    bool timed = false;
-    bool counted = false;   // device time already added to counters_
-    double t_issue = 0.0;
-    int trace = -1;  // index into trace_pool_ (-1: not traced)
-  };
-  std::array<SlotExtra, kSlots> extra_;
-  // Inline requests record their done event lazily (only when a host query / other stream needs it): an event
-  // marker after every inline epilogue left the GPU idle ~5.5 us before the next GEMM (3x per step,
-  // profiles/r2_lazy_done_event.txt). FAN_LAZY_DONE=0 records every request's done event at commit.
-  HipSlotDevice dev_;
-  std::unique_ptr<SlotTable<HipSlotDevice>> table_;
-  std::vector<hipEvent_t> slot_events_;
-  struct RequestTrace {
-    hipEvent_t ev[kTpCount] = {};
-    int64_t logical_bytes = 0, wire_bytes = 0;
-    size_t hop_first = 0, hop_count = 0;  // ring rounds: 4 events each in hop_pool_
-    bool hop_kernel_first = false;         // point order: credit, kernels, ready (copying) or credit, ready, kernels
-  };
-  std::vector<hipEvent_t> hop_pool_;
-  size_t hop_used_ = 0;
-  void hop_mark(int point);  // ring round timestamp of the traced request being built (point 0..3)
-  // verify mode on the direct P2P paths: tag a message where it landed (trailer of its slot) / check one on arrival
-  void tag_direct(const uint8_t* msg, size_t bytes, uint8_t* trailer, uint32_t seq, hipStream_t st);
-  void verify_direct(const uint8_t* msg, size_t bytes, const uint8_t* trailer, uint32_t seq, uint32_t site,
-                     uint32_t row, hipStream_t st);
-  // record trace point tp of the request being built on the stream its phases run on
-  void mark(int tp) {
-    trace_marked_ |= 1u << tp;
-    if (cur_trace_ >= 0) FAN_HIP_CHECK(hipEventRecord(trace_pool_[cur_trace_].ev[tp], run_stream_));
-  }
-  void count_peers(size_t bytes, P2PComm* direct = nullptr);  // `bytes` sent to every other rank
-  uint8_t* scratch(const std::string& key, size_t bytes);
-  std::vector<EpiThunk> run_mesh(const EngineLayout& L, const void* grad, int gdt, float* master,
-                                              bf16_t* lp, float* mom, int64_t n_valid, UpdateParams p, bool update,
-                                              float* out_sum, const uint8_t* prepacked, int64_t prepacked_elems);
-  std::vector<EpiThunk> run_mesh_direct(P2PComm* d, const EngineLayout& L, const void* grad, int gdt, float* master,
-                                        bf16_t* lp, float* mom, int64_t n_valid, UpdateParams p, bool update,
-                                        float* out_sum, const uint8_t* prepacked, bool defer);
-  std::vector<EpiThunk> run_mesh_chunked(const EngineLayout& L, const void* grad, int gdt, float* master,
-                                         bf16_t* lp, float* mom, int64_t n_valid, UpdateParams p, bool update,
-                                         float* out_sum, const uint8_t* prepacked, bool defer);
-  std::vector<EpiThunk> run_ring(const EngineLayout& L, const void* grad, int gdt, float* master,
-                                              bf16_t* lp, float* mom, int64_t n_valid, UpdateParams p, bool update,
-                                              float* out_sum, const uint8_t* prepacked, int64_t prepacked_elems);
-  std::vector<EpiThunk> run_ring_direct(P2PComm* d, const EngineLayout& L, const void* grad, int gdt, float* master,
-                                        bf16_t* lp, float* mom, int64_t n_valid, UpdateParams p, bool update,
-                                        float* out_sum, const uint8_t* prepacked);
-
+  // streams / configuration
   Comm* comm_;
   int rank_, world_, device_;
   EngineConfig cfg_;
@@ -312,18 +278,68 @@ class AllReduceEngine {
   hipStream_t epi_stream_ = nullptr;  // world-1 side epilogues (normal priority: the producer's GEMMs keep theirs)
   hipEvent_t cev_[4][2] = {};         // chunked mesh pipeline events: [all-to-all, reduce, all-gather, epilogue][parity]
   // world 1 without forced collectives: nothing to overlap, so requests run inline on the producer's
-  // stream (no cross-stream event packets); run_stream_ is the stream of the request being issued.
+  // stream (no cross-stream event packets)
   bool inline_ = false;
   bool shard_upd_ = false;
-  hipStream_t run_stream_ = nullptr;
-  volatile uint32_t* flags_host_ = nullptr;  // host-mapped done words (one 64-B line per slot)
-  uint32_t* flags_dev_ = nullptr;
   bool timing_ = false;
   uint64_t submitted_ = 0;
   EngineCounters counters_;
+  void count_peers(size_t bytes, P2PComm* direct = nullptr);  // `bytes` sent to every other rank
+
+  // request-slot table
+  volatile uint32_t* flags_host_ = nullptr;  // host-mapped done words (one 64-B line per slot)
+  uint32_t* flags_dev_ = nullptr;
+  HipSlotDevice dev_;
+  // Inline requests record their done event lazily (only when a host query / other stream needs it): an event
+  // marker after every inline epilogue left the GPU idle ~5.5 us before the next GEMM (3x per step,
+  // profiles/r2_lazy_done_event.txt). FAN_LAZY_DONE=0 records every request's done event at commit.
+  std::unique_ptr<SlotTable<HipSlotDevice>> table_;
+  std::vector<hipEvent_t> slot_events_;
+  // Per-slot engine data beside the state machine (slot_table.h holds sequence / pending / streams / events).
+  struct SlotExtra {
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    bool timed = false;
+    bool counted = false;   // device time already added to counters_
+    double t_issue = 0.0;
+    int trace = -1;  // index into trace_pool_ (-1: not traced)
+  };
+  std::array<SlotExtra, kSlots> extra_;
+
+  // The request being built: reset at the top of submit(), read only by submit() and the schedules it calls.
+  struct Current {
+    hipStream_t run = nullptr;       // stream its communication phase runs on
+    hipStream_t producer = nullptr;  // its producer stream
+    int slot = 0;
+    uint32_t seq = 0;                  // its sequence number (what its messages' tags carry)
+    int trace = -1;                    // its index into trace_pool_ (-1: not traced)
+    unsigned marked = 1u << kTpStart;  // trace points its schedule has recorded
+  } cur_;
+  bool sharded(const EngineRequest& req) const {  // the request runs the sharded update (EngineConfig::shard_update)
+    return shard_upd_ && req.update && req.out_sum == nullptr && req.lp != nullptr;
+  }
+  // Epilogue of `req` (captured by value) over the gathered wire region of n_shards shards that covers bucket
+  // elements [off, off + len)
+  EpiThunk make_epilogue(const EngineRequest& req, const uint8_t* wire, int64_t shard_elems, int n_shards, int64_t off,
+                         int64_t len, int skip_shard = -1, int skip_period = 0) const;
+  std::vector<EpiThunk> run_mesh(const EngineLayout& L, const EngineRequest& req);
+  std::vector<EpiThunk> run_mesh_direct(P2PComm* d, const EngineLayout& L, const EngineRequest& req);
+  std::vector<EpiThunk> run_mesh_chunked(const EngineLayout& L, const EngineRequest& req);
+  std::vector<EpiThunk> run_ring(const EngineLayout& L, const EngineRequest& req);
+  std::vector<EpiThunk> run_ring_direct(P2PComm* d, const EngineLayout& L, const EngineRequest& req);
+  // This rank's place in every ring (orders_) and its schedule there; ring i reduces bucket elements from `off`.
+  struct RingLane {
+    int64_t off;
+    int pos, down, up;
+    std::vector<RingRound> plan;
+  };
+  std::vector<RingLane> ring_lanes(const EngineLayout& L) const;
+
+  // scratch: device buffers by key, zero-filled on `st` when first allocated
   std::map<std::string, std::pair<uint8_t*, size_t>> scratch_;
-  int epi_slot_ = 0;  // slot of the request being built
-  hipStream_t cur_producer_ = nullptr;  // producer stream of the request being built
+  uint8_t* scratch(const std::string& key, size_t bytes, hipStream_t st);
+  // Scratch that a deferred epilogue reads: per request slot, so a later request of the same size cannot
+  // overwrite it before this request commits (the trainer commits every request at the end of backward).
+  uint8_t* epi_scratch(const std::string& base, size_t bytes);
   // deferred chunked requests: the whole-bucket gathered wire, one per bucket size, and who used it last
   struct GallBuf {
     int slot = 0;
@@ -331,27 +347,48 @@ class AllReduceEngine {
     hipEvent_t free = nullptr;  // recorded on the epilogue stream after the last user's epilogue
   };
   std::map<std::string, GallBuf> gall_;
-  bool cur_defer_ = false;  // the request being built defers its epilogue
+
+  // trace
+  struct RequestTrace {
+    hipEvent_t ev[kTpCount] = {};
+    int64_t logical_bytes = 0, wire_bytes = 0;
+    size_t hop_first = 0, hop_count = 0;  // ring rounds: 4 events each in hop_pool_
+    bool hop_kernel_first = false;         // point order: credit, kernels, ready (copying) or credit, ready, kernels
+  };
   bool tracing_ = false;
   std::vector<RequestTrace> trace_pool_;
   size_t trace_used_ = 0;
   uint64_t trace_dropped_ = 0;
-  int cur_trace_ = -1;  // trace of the request being built
+  std::vector<hipEvent_t> hop_pool_;
+  size_t hop_used_ = 0;
+  void hop_mark(int point);  // ring round timestamp of the traced request being built (point 0..3)
+  // record trace point tp of the request being built on the stream its phases run on
+  void mark(int tp) {
+    cur_.marked |= 1u << tp;
+    if (cur_.trace >= 0) FAN_HIP_CHECK(hipEventRecord(trace_pool_[cur_.trace].ev[tp], cur_.run));
+  }
+
   // verify mode / fault injection (verify.h): tag buffers (device), first-error block (device) + its host mirror
   bool verify_ = false;
   FaultInjector fault_;
   uint32_t* tags_ = nullptr;  // [kTagRows][4] x 5 regions: send, recv, scratch, gather-send, gather-recv
   VerifyError* verr_dev_ = nullptr;
   VerifyError* verr_host_ = nullptr;
-  uint32_t req_seq_ = 0;  // sequence number of the request being built (what its tags carry)
   static constexpr int kTagRows = 64;
   uint32_t* tag_region(int r) { return tags_ + (size_t)r * kTagRows * 4; }
   void verify_rows(const uint8_t* rows, size_t row_bytes, int nrows, const uint32_t* recv_tags, uint32_t site,
                    uint32_t row_base, hipStream_t st);
-  unsigned trace_marked_ = 0;  // trace points the schedule of the request being built has recorded
-  // Scratch that a deferred epilogue reads: per request slot, so a later request of the same size cannot
-  // overwrite it before this request commits (the trainer commits every request at the end of backward).
-  uint8_t* epi_scratch(const std::string& base, size_t bytes);
+  // A collective of the copying mesh with its checks, in this order: verify tags of the rows sent, the in-flight
+  // corruption hook ("mesh_pack" / "mesh_reduce"), the collective, the peer byte counts, then the tag exchange and
+  // the check of every row received (rows numbered from row_base). all_to_all: world rows of row_bytes each way;
+  // all_gather: this rank's `bytes` at src into row rank of dst (src may be that row).
+  void all_to_all_checked(const uint8_t* src, uint8_t* dst, size_t row_bytes, uint32_t row_base, hipStream_t st);
+  void all_gather_checked(uint8_t* src, uint8_t* dst, size_t bytes, uint32_t verify_site, uint32_t row_base,
+                          hipStream_t st);
+  // verify mode on the direct P2P paths: tag a message where it landed (trailer of its slot) / check one on arrival
+  void tag_direct(const uint8_t* msg, size_t bytes, uint8_t* trailer, uint32_t seq, hipStream_t st);
+  void verify_direct(const uint8_t* msg, size_t bytes, const uint8_t* trailer, uint32_t seq, uint32_t site,
+                     uint32_t row, hipStream_t st);
 };
 
 }  // namespace fan

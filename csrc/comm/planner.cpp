@@ -46,6 +46,15 @@ std::vector<RingRound> ring_plan(int N, int p, int64_t blocks) {
   return out;
 }
 
+std::vector<std::vector<size_t>> ring_rounds(const std::vector<RingRound>& plan) {
+  std::vector<std::vector<size_t>> rounds;
+  for (size_t j = 0; j < plan.size(); ++j) {
+    if (j > 0 && plan[j].send_src == kSendLocal) rounds.back().push_back(j);
+    else rounds.push_back({j});
+  }
+  return rounds;
+}
+
 std::vector<std::vector<int>> ring_orders(int N, int max_rings, const std::vector<char>* links) {
   std::vector<std::vector<int>> best;
   if (N <= 1) return {{0}};

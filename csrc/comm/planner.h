@@ -9,6 +9,7 @@
 // and owns slice p-1 (hw/all_reduce.sv:1230).
 // Unlike the reference (N in 3..6 only, hw/all_reduce.sv:1152), every N >= 1 is supported.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -39,6 +40,9 @@ struct RingGeometry {
 // granule: the slice is a multiple of it (256: one wire shard; 256 * P: P sub-shards for a streamed ring hop)
 RingGeometry ring_geometry(int64_t n, int world, int64_t max_slice_elems, int64_t granule = 256);
 std::vector<RingRound> ring_plan(int world, int position, int64_t blocks);
+// The plan's rows grouped into communication rounds (row indices, in order): a SEND_LOCAL row after the first joins
+// the previous round (the OUTPUT_SEND overlap above). The grouping is the same at every position of a ring.
+std::vector<std::vector<size_t>> ring_rounds(const std::vector<RingRound>& plan);
 
 // Arc-disjoint directed Hamiltonian cycles of the link digraph on `world` vertices (up to world-1 rings; fewer
 // when no decomposition exists, e.g. world 4 and 6 on a complete graph). `links` (row-major world x world,

@@ -160,5 +160,88 @@ def test_shard_update_forced_one_rank_matches_inline():
     assert sh.counters()["sharded_updates"] == 1
 
 
+def _loopback_ranks(world, n, fn, engine_kw=None):
+    """fn(r, engine, w0) on one thread per virtual rank of a fresh loopback fabric (engine_kw: rank -> extra engine
+    arguments); returns (results, errors)."""
+    engine_kw = engine_kw or {}
+    C = _ext.require()
+    fabric = C.LoopbackFabric(world, 30.0)
+    w0 = np.random.default_rng(11).standard_normal(n).astype(np.float32)
+    engines = [NativeAllReduce(None, codec="bfp_rne", algo="mesh", comm=fabric.comm(r), shard_update=True,
+                               **(engine_kw.get(r, {}))) for r in range(world)]
+    assert all(e.shard_update for e in engines)
+    out, errs = [None] * world, [None] * world
+
+    def run(r):
+        try:
+            torch.cuda.set_device(0)
+            with torch.cuda.stream(torch.cuda.Stream()):
+                out[r] = fn(r, engines[r], w0)
+        except Exception as e:  # noqa: BLE001
+            errs[r] = e
+
+    ts = [threading.Thread(target=run, args=(r,)) for r in range(world)]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join(90)
+    assert not any(t.is_alive() for t in ts), "virtual rank thread hung"
+    return out, errs
+
+
+def _sharded_request(r, eng, w0, n, **kw):
+    L = eng.layout(n)
+    g = torch.zeros(L.n_pad, device="cuda")
+    g[:n] = torch.from_numpy(np.random.default_rng(20 + r).standard_normal(n).astype(np.float32)).cuda()
+    w = torch.zeros(L.n_pad, device="cuda")
+    w[:n] = torch.from_numpy(w0).cuda()
+    lp = torch.zeros(L.n_pad, device="cuda", dtype=torch.bfloat16)
+    return w, eng.allreduce_sgd(g, w, lp, n_valid=n, lr=0.05, **kw), (g, lp)  # (the caller keeps the buffers alive)
+
+
+def test_shard_update_verify_names_the_weight_all_gather():
+    """A weight shard corrupted in flight (rank 1's ``mesh_reduce`` message) is caught by verify mode on the sharded
+    schedule's weight all-gather, and the error names that site."""
+    from fpga_ai_nic_amd.parallel.allreduce import ChecksumError
+
+    n = 3000
+
+    def fn(r, eng, w0):
+        _, h, _bufs = _sharded_request(r, eng, w0, n)
+        h.synchronize(30)
+
+    kw = {r: {"verify": True, "fault": "mesh_reduce:0:flip" if r == 1 else ""} for r in range(3)}
+    _, errs = _loopback_ranks(3, n, fn, engine_kw=kw)
+    caught = [e for e in errs if isinstance(e, ChecksumError)]
+    assert caught, errs
+    assert "corrupted" in str(caught[0]) and "mesh weight all_gather" in str(caught[0]), str(caught[0])
+
+
+def test_gather_owned_first_use_after_on_producer_request():
+    """gather_owned right after a request that ran on the caller's stream (on_producer), on engines that never
+    gathered before: its staging buffer is allocated (and zero-filled) inside this call, on the stream the all-gather
+    runs on, so every rank ends with every owner's shard."""
+    world, n = 3, 3000
+
+    def fn(r, eng, w0):
+        w, h, _bufs = _sharded_request(r, eng, w0, n, defer=True, on_producer=True)
+        h.commit_after_current()
+        eng.gather_owned(w, n)
+        assert eng.counters()["sharded_updates"] == 1
+        return w.cpu().numpy(), eng.layout(n).shard
+
+    out, errs = _loopback_ranks(world, n, fn)
+    assert not any(errs), errs
+    s = out[0][1]
+    w0 = np.zeros(world * s, np.float32)
+    w0[:n] = np.random.default_rng(11).standard_normal(n).astype(np.float32)
+    for q in range(world):
+        own = out[q][0][q * s:(q + 1) * s]  # rank q's own shard: gather_owned leaves it in place
+        assert not np.array_equal(own, w0[q * s:(q + 1) * s]), f"owner {q} did not update its shard"
+        for r in range(world):
+            assert np.array_equal(out[r][0][q * s:(q + 1) * s].view(np.uint32), own.view(np.uint32)), \
+                f"rank {r}: shard {q} differs from its owner's"
+
+
 if __name__ == "__main__":
     print(json.dumps(_case(int(sys.argv[1]), sys.argv[2])), flush=True)
