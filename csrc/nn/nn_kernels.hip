@@ -223,6 +223,7 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
     for (int j = 1; j < V; ++j) cm = fmaxf(cm, v[j]);
     const float nm = fmaxf(m, cm);
+    if (nm == -INFINITY) continue;  // only masked (-inf) classes so far: exp(-inf - -inf) would be NaN; s stays 0
     float cs = 0.f;
 #pragma unroll
     for (int j = 0; j < V; ++j) cs += __expf(v[j] - nm);
