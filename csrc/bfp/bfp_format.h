@@ -65,6 +65,40 @@ __device__ __forceinline__ void adamw_update(const AdamWParams& p, float g, floa
   w = fmaf(-p.step_size, m / d, p.weight_decay != 0.0f ? w * p.decay : w);
 }
 
+// AdamW with a layer-wise trust ratio (LAMB), the two-pass update of the all-reduce epilogues. The host scalars are
+// ops/bfp_oracle.py lamb_scalars (float64, rounded once to f32): AdamW's beta1, omb1, beta2, omb2, rsbc2, eps, plus
+// rbc1 = 1 / (1 - beta1^t), the decay coefficient and lr themselves (the step size is not folded into a scalar: it is
+// multiplied by the trust ratio on the device). `var` as AdamWParams::var.
+struct LambParams {
+  float grad_scale;
+  float beta1, omb1;
+  float beta2, omb2;
+  float rsbc2;
+  float eps;
+  float rbc1;
+  float weight_decay;
+  float lr;
+  float* var;
+};
+
+// Pass 1's moments of one element: adamw_update's first three statements, so the same bits.
+__device__ __forceinline__ void lamb_moments(const LambParams& p, float g, float& m, float& v) {
+  g = g * p.grad_scale;
+  m = fmaf(p.beta1, m, p.omb1 * g);
+  v = fmaf(p.beta2, v, (p.omb2 * g) * g);
+}
+
+// The update direction of one element from the NEW moments and the OLD weight, all f32, in the order
+// bfp_oracle.lamb_moments emulates (change both together):
+//   d = fma(sqrt(v'), rsbc2, eps); u = m' / d; r = wd != 0 ? fma(wd, w, u * rbc1) : u * rbc1
+// Pass 1 (for the norm) and pass 2 (for the step) both call it on the same values, so no `r` plane is kept.
+__device__ __forceinline__ float lamb_direction(const LambParams& p, float w, float m, float v) {
+  const float d = fmaf(sqrtf(v), p.rsbc2, p.eps);
+  const float u = m / d;
+  const float ub = u * p.rbc1;
+  return p.weight_decay != 0.0f ? fmaf(p.weight_decay, w, ub) : ub;
+}
+
 __host__ __device__ inline size_t wire_shard_bytes(int codec, size_t n_s) {
   switch (codec) {
     case kBfpTrunc:
@@ -332,6 +366,26 @@ void launch_wire_sgd(int codec, const void* wire, size_t n_s, int n_shards, int 
 void launch_wire_adamw(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
                        float* master, bf16_t* lp, float* mom, AdamWParams p, size_t n_valid, hipStream_t stream,
                        size_t shard_stride = 0);
+// The trust-ratio (LAMB) epilogue: three launches on one stream.
+// Pass 1, launch_wire_lamb_moments: decode the wire as launch_wire_adamw does (codecs, shard_stride, skipped shards,
+// n_valid tail), store the new moments (`mom`, p.var) and leave `master` untouched; over the flat elements below
+// adapt_end (any value, clamped to n_valid; it may fall inside a 16-value group) accumulate S_w = sum w^2 and
+// S_r = sum r^2 in fp64, reduced in a fixed order per lane, wave and block: block b stores {S_w, S_r} at
+// partials[2b], partials[2b + 1]. The launch has lamb_partials_for(n_s) blocks — a function of n_s and the grid cap
+// alone, so every rank that runs the same launch on the same wire produces the same bits.
+int lamb_partials_for(size_t n_s);
+void launch_wire_lamb_moments(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
+                              const float* master, float* mom, LambParams p, size_t n_valid, size_t adapt_end,
+                              double* partials, hipStream_t stream, size_t shard_stride = 0);
+// One block: sums the n_pairs {S_w, S_r} pairs of every pass-1 launch of a request (each lane takes pairs
+// t, t + 256, ... in ascending order, the lanes' sums then combine in a fixed tree, all fp64) and writes the three f32
+// words {lr * phi, lr, phi}, phi = (float)sqrt(S_w / S_r) when both sums are positive and finite, else 1.
+void launch_lamb_ratio(const double* partials, int n_pairs, float lr, float* words, hipStream_t stream);
+// Pass 2, launch_wire_lamb_apply: a dense pass over elements [0, n_valid) of master / mom / p.var (the planes pass 1
+// left): w' = fma(-(i < adapt_end ? words[0] : words[1]), r, w), lp = bf16(w') when given. Elements of shards s
+// (of n_s elements) with (s % skip_period) == skip_shard are left untouched, as in pass 1.
+void launch_wire_lamb_apply(float* master, bf16_t* lp, const float* mom, LambParams p, const float* words, size_t n_s,
+                            int skip_shard, int skip_period, size_t n_valid, size_t adapt_end, hipStream_t stream);
 // Decode to f32/bf16 from a strided wire (as launch_wire_sgd's shard_stride).
 void launch_wire_unpack_strided(int codec, int out_dtype, const void* in, size_t shard_stride, void* out, size_t n_s,
                                 int n_shards, hipStream_t stream);

@@ -14,6 +14,9 @@
 //                  into the all-gather epilogue so weights never take an extra HBM round trip.
 //   AdamW        = no counterpart in the reference (its update unit is one FFMA): the same three update kernels
 //                  instantiated with AdamWParams run adamw_update (bfp_format.h) per value, with a second moment plane.
+//   trust ratio  = AdamW scaled per bucket by ||w|| / ||update|| (LAMB): no element may move before two norms over
+//                  the whole bucket exist, so three launches — wire_lamb_moments (pass 1), lamb_ratio,
+//                  wire_lamb_apply (pass 2) — with a deterministic fp64 reduction in between (no atomics).
 #include "bfp/bfp_format.h"
 
 #include <algorithm>
@@ -576,6 +579,138 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
+// ---------------------------------------------------------------- trust-ratio (LAMB) epilogue
+// Fixed-order fp64 sum over the workgroup: the wave's lanes by shuffles (32, 16, ... 1), then the waves' sums in wave
+// order by thread 0 through LDS. Every thread of the block must call it; the result is valid in thread 0.
+__device__ __forceinline__ void lamb_block_sum(double& a, double& b) {
+  __shared__ double red[2][kBlock / 64];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    a += __shfl_down(a, off);
+    b += __shfl_down(b, off);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = a;
+    red[1][threadIdx.x >> 6] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a = red[0][0];
+    b = red[1][0];
+#pragma unroll
+    for (int i = 1; i < kBlock / 64; ++i) {
+      a += red[0][i];
+      b += red[1][i];
+    }
+  }
+}
+
+// Pass 1: wire_sgd_kernel's traversal (8 values per lane, shards, skipped shards, the n_valid tail); stores the new
+// moments, reads master only. The lane's fp64 sums grow in its own iteration order, which the grid alone decides.
+template <int C>
+__global__ void __launch_bounds__(kBlock)
+    wire_lamb_moments_kernel(const uint8_t* __restrict__ wire, size_t n_s, int n_shards, int skip_shard,
+                             int skip_period, const float* __restrict__ master, float* __restrict__ mom, LambParams p,
+                             size_t n_valid, size_t adapt_end, size_t sb, double* __restrict__ partials) {
+  const size_t tasks = n_s >> 3;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  double sw = 0.0, sr = 0.0;
+  for (int s = 0; s < n_shards; ++s) {
+    if (skip_shard >= 0 && (s % skip_period) == skip_shard) continue;
+    const uint8_t* src = wire + (size_t)s * sb;
+    const size_t base = (size_t)s * n_s;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
+      const size_t e = base + (t << 3);
+      if (e >= n_valid) continue;
+      float g[8], w[8], m[8], v2[8];
+      WireLane<C>::load8(src, n_s, t << 3, g);
+      DenseLane<float>::load8(master, e, w);
+      DenseLane<float>::load8(mom, e, m);
+      DenseLane<float>::load8(p.var, e, v2);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) lamb_moments(p, g[j], m[j], v2[j]);
+      if (e < adapt_end) {  // (adapt_end <= n_valid: the launcher clamps it)
+        // branch-free per value: a value at or past adapt_end enters as 0, and s + 0.0 is s bit for bit
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const bool in = e + j < adapt_end;
+          const float r = lamb_direction(p, w[j], m[j], v2[j]);
+          const double wa = in ? (double)w[j] : 0.0, ra = in ? (double)r : 0.0;
+          sw = fma(wa, wa, sw);
+          sr = fma(ra, ra, sr);
+        }
+      }
+      if (e + 8 <= n_valid) {
+        DenseLane<float>::store8(mom, e, m);
+        DenseLane<float>::store8(p.var, e, v2);
+      } else {
+        for (int j = 0; j < 8 && e + j < n_valid; ++j) {
+          mom[e + j] = m[j];
+          p.var[e + j] = v2[j];
+        }
+      }
+    }
+  }
+  lamb_block_sum(sw, sr);
+  if (threadIdx.x == 0) {
+    partials[2 * (size_t)blockIdx.x] = sw;
+    partials[2 * (size_t)blockIdx.x + 1] = sr;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+    lamb_ratio_kernel(const double* __restrict__ partials, int n_pairs, float lr, float* __restrict__ words) {
+  double sw = 0.0, sr = 0.0;
+  for (int i = threadIdx.x; i < n_pairs; i += kBlock) {
+    sw += partials[2 * (size_t)i];
+    sr += partials[2 * (size_t)i + 1];
+  }
+  lamb_block_sum(sw, sr);
+  if (threadIdx.x == 0) {
+    const bool ok = sw > 0.0 && sr > 0.0 && sw < __builtin_huge_val() && sr < __builtin_huge_val();
+    const float phi = ok ? (float)sqrt(sw / sr) : 1.0f;
+    words[0] = lr * phi;
+    words[1] = lr;
+    words[2] = phi;
+  }
+}
+
+// Pass 2: dense, 4 values per lane (16-B loads of the three planes, one 16-B store of master, 8 B of bf16).
+template <bool HAS_LP>
+__global__ void __launch_bounds__(kBlock)
+    wire_lamb_apply_kernel(float* __restrict__ master, bf16_t* __restrict__ lp, const float* __restrict__ mom,
+                           LambParams p, const float* __restrict__ words, size_t n_s, int skip_shard, int skip_period,
+                           size_t n_valid, size_t adapt_end) {
+  const float s_adapt = words[0], s_tail = words[1];
+  const size_t tasks = (n_valid + 3) >> 2;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
+    const size_t e = t << 2;
+    // (n_s is a multiple of 256: a lane's 4 values lie in one shard)
+    if (skip_shard >= 0 && (int)((e / n_s) % (size_t)skip_period) == skip_shard) continue;
+    const float4 wv = *reinterpret_cast<const float4*>(master + e);
+    const float4 mv = *reinterpret_cast<const float4*>(mom + e);
+    const float4 vv = *reinterpret_cast<const float4*>(p.var + e);
+    float w[4] = {wv.x, wv.y, wv.z, wv.w};
+    const float m[4] = {mv.x, mv.y, mv.z, mv.w}, v2[4] = {vv.x, vv.y, vv.z, vv.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float r = lamb_direction(p, w[j], m[j], v2[j]);
+      w[j] = fmaf(-(e + j < adapt_end ? s_adapt : s_tail), r, w[j]);
+    }
+    if (e + 4 <= n_valid) {
+      *reinterpret_cast<float4*>(master + e) = make_float4(w[0], w[1], w[2], w[3]);
+      if (HAS_LP)
+        *reinterpret_cast<uint2*>(lp + e) = make_uint2(pack_bf16x2(w[0], w[1]), pack_bf16x2(w[2], w[3]));
+    } else {
+      for (int j = 0; j < 4 && e + j < n_valid; ++j) {
+        master[e + j] = w[j];
+        if (HAS_LP) lp[e + j] = f32_to_bf16(w[j]);
+      }
+    }
+  }
+}
+
 }  // namespace
 
 #define FAN_CODEC_SWITCH(codec, ...)                         \
@@ -732,6 +867,53 @@ void launch_wire_adamw(int codec, const void* wire, size_t n_s, int n_shards, in
       hipLaunchKernelGGL((wire_sgd_kernel<C, false, true, AdamWParams>), grid, kBlock, 0, stream, w, n_s, n_shards,
                          skip_shard, skip_period, master, lp, mom, p, n_valid, sb);
   });
+  FAN_HIP_CHECK(hipGetLastError());
+}
+
+int lamb_partials_for(size_t n_s) { return stream_grid(n_s / 8, kBlock, wire_max_blocks()); }
+
+void launch_wire_lamb_moments(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
+                              const float* master, float* mom, LambParams p, size_t n_valid, size_t adapt_end,
+                              double* partials, hipStream_t stream, size_t shard_stride) {
+  FAN_CHECK(master != nullptr && mom != nullptr && p.var != nullptr && partials != nullptr,
+            "wire_lamb_moments: master, both moment planes and the partials buffer");
+  if (skip_period < 1) skip_period = 1 << 30;
+  check_ns(n_s);
+  // (an empty launch would leave its partials unwritten for launch_lamb_ratio to read)
+  FAN_CHECK(n_s > 0 && n_shards > 0, "wire_lamb_moments: empty wire");
+  if (adapt_end > n_valid) adapt_end = n_valid;
+  const int grid = lamb_partials_for(n_s);
+  const uint8_t* w = (const uint8_t*)wire;
+  FAN_CODEC_SWITCH(codec, {
+    const size_t sb = shard_stride ? shard_stride : wire_shard_bytes(C, n_s);
+    hipLaunchKernelGGL((wire_lamb_moments_kernel<C>), grid, kBlock, 0, stream, w, n_s, n_shards, skip_shard,
+                       skip_period, master, mom, p, n_valid, adapt_end, sb, partials);
+  });
+  FAN_HIP_CHECK(hipGetLastError());
+}
+
+void launch_lamb_ratio(const double* partials, int n_pairs, float lr, float* words, hipStream_t stream) {
+  FAN_CHECK(partials != nullptr && words != nullptr && n_pairs >= 0, "lamb_ratio: partials and the three output words");
+  hipLaunchKernelGGL(lamb_ratio_kernel, 1, kBlock, 0, stream, partials, n_pairs, lr, words);
+  FAN_HIP_CHECK(hipGetLastError());
+}
+
+void launch_wire_lamb_apply(float* master, bf16_t* lp, const float* mom, LambParams p, const float* words, size_t n_s,
+                            int skip_shard, int skip_period, size_t n_valid, size_t adapt_end, hipStream_t stream) {
+  FAN_CHECK(master != nullptr && mom != nullptr && p.var != nullptr && words != nullptr,
+            "wire_lamb_apply: master, both moment planes and the scale words");
+  if (skip_period < 1) skip_period = 1 << 30;
+  check_ns(n_s);
+  FAN_CHECK(n_s > 0 || skip_shard < 0, "wire_lamb_apply: skipped shards need the shard size");
+  if (n_valid == 0) return;
+  if (adapt_end > n_valid) adapt_end = n_valid;
+  const int grid = stream_grid((n_valid + 3) / 4, kBlock, wire_max_blocks());
+  if (lp)
+    hipLaunchKernelGGL((wire_lamb_apply_kernel<true>), grid, kBlock, 0, stream, master, lp, mom, p, words, n_s,
+                       skip_shard, skip_period, n_valid, adapt_end);
+  else
+    hipLaunchKernelGGL((wire_lamb_apply_kernel<false>), grid, kBlock, 0, stream, master, lp, mom, p, words, n_s,
+                       skip_shard, skip_period, n_valid, adapt_end);
   FAN_HIP_CHECK(hipGetLastError());
 }
 

@@ -166,6 +166,73 @@ void wire_adamw(const at::Tensor& wire, int64_t shard_elems, int64_t n_shards, i
                          fan_stream(), (size_t)shard_stride);
 }
 
+// the planes of the trust-ratio passes: f32, whole lanes readable (8 values in pass 1, 4 in pass 2)
+static void lamb_check_planes(const at::Tensor& master, const at::Tensor& mom, const at::Tensor& var, int64_t n_valid) {
+  FAN_T_CUDA_CONTIG(master);
+  FAN_T_CUDA_CONTIG(mom);
+  FAN_T_CUDA_CONTIG(var);
+  const int64_t need = (n_valid + 7) / 8 * 8;
+  TORCH_CHECK(master.scalar_type() == at::kFloat && mom.scalar_type() == at::kFloat && var.scalar_type() == at::kFloat,
+              "master, mom and var must be float32");
+  TORCH_CHECK(master.numel() >= need && mom.numel() >= need && var.numel() >= need,
+              "master, mom and var must hold n_valid rounded up to 8 elements");
+}
+
+int64_t wire_lamb_moments(const at::Tensor& wire, int64_t shard_elems, int64_t n_shards, int64_t skip_shard,
+                          int64_t skip_period, const at::Tensor& master, at::Tensor& mom, at::Tensor& var,
+                          const std::vector<double>& scalars, double grad_scale, int64_t n_valid, int64_t n_adapt,
+                          at::Tensor& partials, int64_t partials_base, int64_t codec, int64_t shard_stride) {
+  FAN_T_CUDA_CONTIG(wire);
+  FAN_T_CUDA_CONTIG(partials);
+  TORCH_CHECK(shard_elems > 0 && n_shards > 0 && n_valid >= 0 && n_valid <= shard_elems * n_shards, "bad shape");
+  TORCH_CHECK(n_adapt >= 0 && n_adapt <= n_valid, "n_adapt must lie in [0, n_valid]");
+  lamb_check_planes(master, mom, var, n_valid);
+  const size_t sb = fan::wire_shard_bytes((int)codec, shard_elems);
+  TORCH_CHECK(shard_stride == 0 || (size_t)shard_stride >= sb, "shard_stride below the packed shard size");
+  TORCH_CHECK(shard_stride % 16 == 0, "shard_stride must keep 16-byte alignment");
+  const size_t need = shard_stride ? (size_t)shard_stride * (n_shards - 1) + sb : sb * n_shards;
+  TORCH_CHECK((size_t)wire.numel() * wire.element_size() >= need, "wire buffer too small");
+  const int64_t pairs = fan::lamb_partials_for((size_t)shard_elems);
+  TORCH_CHECK(partials.scalar_type() == at::kDouble && partials_base >= 0 &&
+                  partials.numel() >= 2 * (partials_base + pairs),
+              "partials: f64[2 * (partials_base + ", pairs, ")]");
+  const fan::LambParams p = fan_lamb_params(scalars, grad_scale, var, n_valid);
+  fan::launch_wire_lamb_moments((int)codec, wire.data_ptr(), (size_t)shard_elems, (int)n_shards, (int)skip_shard,
+                                (int)skip_period, master.data_ptr<float>(), mom.data_ptr<float>(), p, (size_t)n_valid,
+                                (size_t)n_adapt, partials.data_ptr<double>() + 2 * partials_base, fan_stream(),
+                                (size_t)shard_stride);
+  return pairs;
+}
+
+void lamb_ratio(const at::Tensor& partials, int64_t n_pairs, double lr, at::Tensor& words) {
+  FAN_T_CUDA_CONTIG(partials);
+  FAN_T_CUDA_CONTIG(words);
+  TORCH_CHECK(partials.scalar_type() == at::kDouble && n_pairs >= 0 && partials.numel() >= 2 * n_pairs,
+              "partials: f64[2 * n_pairs]");
+  TORCH_CHECK(words.scalar_type() == at::kFloat && words.numel() >= 3, "words: f32[3]");
+  fan::launch_lamb_ratio(partials.data_ptr<double>(), (int)n_pairs, (float)lr, words.data_ptr<float>(), fan_stream());
+}
+
+void wire_lamb_apply(at::Tensor& master, const c10::optional<at::Tensor>& lp, const at::Tensor& mom,
+                     const at::Tensor& var, const std::vector<double>& scalars, const at::Tensor& words,
+                     int64_t shard_elems, int64_t skip_shard, int64_t skip_period, int64_t n_valid, int64_t n_adapt) {
+  FAN_T_CUDA_CONTIG(words);
+  TORCH_CHECK(words.scalar_type() == at::kFloat && words.numel() >= 3, "words: f32[3]");
+  TORCH_CHECK(n_valid >= 0 && n_adapt >= 0 && n_adapt <= n_valid, "n_adapt must lie in [0, n_valid]");
+  TORCH_CHECK(shard_elems > 0, "shard_elems");
+  lamb_check_planes(master, mom, var, n_valid);
+  fan::bf16_t* lpp = nullptr;
+  if (lp) {
+    FAN_T_CUDA_CONTIG((*lp));
+    TORCH_CHECK(lp->scalar_type() == at::kBFloat16 && lp->numel() >= n_valid, "bad lp weights");
+    lpp = reinterpret_cast<fan::bf16_t*>(lp->data_ptr());
+  }
+  const fan::LambParams p = fan_lamb_params(scalars, 1.0, var, n_valid);
+  fan::launch_wire_lamb_apply(master.data_ptr<float>(), lpp, mom.data_ptr<float>(), p, words.data_ptr<float>(),
+                              (size_t)shard_elems, (int)skip_shard, (int)skip_period, (size_t)n_valid, (size_t)n_adapt,
+                              fan_stream());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -191,6 +258,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("skip_period"), pybind11::arg("master"), pybind11::arg("lp"), pybind11::arg("mom"),
         pybind11::arg("var"), pybind11::arg("scalars"), pybind11::arg("grad_scale"), pybind11::arg("weight_decay"),
         pybind11::arg("n_valid"), pybind11::arg("codec"), pybind11::arg("shard_stride") = 0);
+  m.def("lamb_partials_for", [](int64_t n_s) { return (int64_t)fan::lamb_partials_for((size_t)n_s); },
+        "{S_w, S_r} pairs one wire_lamb_moments launch over shards of n_s elements writes");
+  m.def("wire_lamb_moments", &wire_lamb_moments,
+        "trust-ratio pass 1: decode + new moments + fp64 norm partials; returns the pairs written", pybind11::arg("wire"),
+        pybind11::arg("shard_elems"), pybind11::arg("n_shards"), pybind11::arg("skip_shard"),
+        pybind11::arg("skip_period"), pybind11::arg("master"), pybind11::arg("mom"), pybind11::arg("var"),
+        pybind11::arg("scalars"), pybind11::arg("grad_scale"), pybind11::arg("n_valid"), pybind11::arg("n_adapt"),
+        pybind11::arg("partials"), pybind11::arg("partials_base"), pybind11::arg("codec"),
+        pybind11::arg("shard_stride") = 0);
+  m.def("lamb_ratio", &lamb_ratio, "trust ratio of n_pairs norm partials -> words {lr * phi, lr, phi}",
+        pybind11::arg("partials"), pybind11::arg("n_pairs"), pybind11::arg("lr"), pybind11::arg("words"));
+  m.def("wire_lamb_apply", &wire_lamb_apply, "trust-ratio pass 2: the weight step from the stored moments",
+        pybind11::arg("master"), pybind11::arg("lp"), pybind11::arg("mom"), pybind11::arg("var"),
+        pybind11::arg("scalars"), pybind11::arg("words"), pybind11::arg("shard_elems"), pybind11::arg("skip_shard"),
+        pybind11::arg("skip_period"), pybind11::arg("n_valid"), pybind11::arg("n_adapt"));
   fan::register_gemm(m);
   fan::register_nn(m);
   fan::register_planner(m);

@@ -24,3 +24,14 @@ inline fan::AdamWParams fan_adamw_params(const std::vector<double>& s, double gr
   return fan::AdamWParams{(float)grad_scale, (float)s[0], (float)s[1], (float)s[2], (float)s[3], (float)s[4],
                           (float)s[5], (float)s[6], (float)weight_decay, (float)s[7], var.data_ptr<float>()};
 }
+
+// LambParams from bfp_oracle.lamb_scalars (already rounded to f32, in its order: beta1, omb1, beta2, omb2, rsbc2, eps,
+// rbc1, wd, lr) and the second-moment plane.
+inline fan::LambParams fan_lamb_params(const std::vector<double>& s, double grad_scale, const at::Tensor& var,
+                                       int64_t n_valid) {
+  TORCH_CHECK(s.size() == 9, "lamb: 9 scalars (beta1, omb1, beta2, omb2, rsbc2, eps, rbc1, wd, lr)");
+  FAN_T_CUDA_CONTIG(var);
+  TORCH_CHECK(var.scalar_type() == at::kFloat && var.numel() >= n_valid, "var: f32[n_valid]");
+  return fan::LambParams{(float)grad_scale, (float)s[0], (float)s[1], (float)s[2], (float)s[3], (float)s[4],
+                         (float)s[5], (float)s[6], (float)s[7], (float)s[8], var.data_ptr<float>()};
+}

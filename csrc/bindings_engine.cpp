@@ -250,7 +250,8 @@ void register_engine(pybind11::module_& m) {
               double momentum, bool nesterov, bool defer, bool update, c10::optional<at::Tensor> out_sum,
               c10::optional<at::Tensor> prepacked, int64_t prepacked_elems, int64_t layout_shard,
               int64_t layout_chunks, bool on_producer, int64_t opt, c10::optional<at::Tensor> var,
-              c10::optional<std::vector<double>> adamw) {
+              c10::optional<std::vector<double>> adamw, c10::optional<std::vector<double>> lamb, int64_t n_adapt,
+              c10::optional<at::Tensor> trust_out) {
              FAN_T_CUDA_CONTIG(grad);
              TORCH_CHECK(grad.scalar_type() == at::kFloat || grad.scalar_type() == at::kBFloat16,
                          "gradients must be f32 or bf16");
@@ -313,6 +314,18 @@ void register_engine(pybind11::module_& m) {
                  req.upd.adamw = fan_adamw_params(*adamw, grad_scale, wd, *var, n_valid);
                }
              }
+             if (lamb.has_value()) {  // the layer-wise trust ratio: AdamW's request with the two-pass epilogue
+               TORCH_CHECK(opt == kOptAdamW && update, "trust ratio: a flag of AdamW update requests");
+               TORCH_CHECK(n_adapt >= -1 && n_adapt <= n_valid, "trust ratio: n_adapt must lie in [0, n_valid]");
+               req.upd.trust = true;
+               req.upd.lamb = fan_lamb_params(*lamb, grad_scale, *var, n_valid);
+               req.n_adapt = n_adapt;
+               if (trust_out && trust_out->defined()) {
+                 FAN_T_CUDA_CONTIG(*trust_out);
+                 TORCH_CHECK(trust_out->scalar_type() == at::kFloat && trust_out->numel() >= 3, "trust_out: f32[3]");
+                 req.trust_out = trust_out->data_ptr<float>();
+               }
+             }
              return e.submit(req, fan_stream());
            },
            py::arg("grad"), py::arg("master"), py::arg("lp") = py::none(), py::arg("mom") = py::none(),
@@ -321,7 +334,8 @@ void register_engine(pybind11::module_& m) {
            py::arg("update") = true, py::arg("out_sum") = py::none(), py::arg("prepacked") = py::none(),
            py::arg("prepacked_elems") = 0, py::arg("layout_shard") = 0, py::arg("layout_chunks") = 0,
            py::arg("on_producer") = false, py::arg("opt") = 0, py::arg("var") = py::none(),
-           py::arg("adamw") = py::none(), py::call_guard<py::gil_scoped_release>())
+           py::arg("adamw") = py::none(), py::arg("lamb") = py::none(), py::arg("n_adapt") = -1,
+           py::arg("trust_out") = py::none(), py::call_guard<py::gil_scoped_release>())
       .def("prepack_shape", [](AllReduceEngine& e, int64_t n) {
         const auto s = e.prepack_shape(n);
         return py::make_tuple(s[0], s[1], s[2]);

@@ -245,6 +245,7 @@ uint8_t* AllReduceEngine::epi_scratch(const std::string& base, size_t bytes) {
 static void update_at(const EngineRequest& req, int codec, const void* wire, size_t n_s, int n_shards, int skip_shard,
                       int skip_period, int64_t off, size_t nv, hipStream_t st, size_t shard_stride = 0) {
   bf16_t* lp = req.lp ? req.lp + off : nullptr;
+  FAN_CHECK(!req.upd.trust, "a trust-ratio update is the two-pass epilogue (lamb_region), never a single launch");
   if (req.upd.kind == kOptAdamW) {
     AdamWParams a = req.upd.adamw;
     a.var += off;
@@ -280,10 +281,51 @@ static void epilogue(const EngineRequest& req, int codec, hipStream_t st, const 
   if (req.out_sum) launch_wire_unpack(codec, kF32, G, req.out_sum + off, (size_t)shard, n_shards, st);
 }
 
-EpiThunk AllReduceEngine::make_epilogue(const EngineRequest& req, const uint8_t* wire, int64_t shard_elems,
-                                        int n_shards, int64_t off, int64_t len, int skip_shard,
-                                        int skip_period) const {
+// The request's LambParams with the second-moment plane `off` elements into the bucket.
+static LambParams lamb_at(const EngineRequest& req, int64_t off) {
+  LambParams p = req.upd.lamb;
+  p.var = req.upd.adamw.var + off;
+  return p;
+}
+
+EpiThunk AllReduceEngine::lamb_region(const EngineRequest& req, const uint8_t* wire, int64_t shard_elems, int n_shards,
+                                      int64_t off, int64_t nv, int skip_shard, int skip_period, size_t shard_stride) {
   const int c = cfg_.codec;
+  // flat offsets: the adapted tensor ends n_adapt - off elements into this region (clamped, as valid_in does n_valid)
+  const int64_t n_adapt = req.n_adapt < 0 ? req.n_valid : req.n_adapt;
+  const size_t adapt_end = (size_t)std::min(std::max<int64_t>(n_adapt - off, 0), nv);
+  const int pairs = lamb_partials_for((size_t)shard_elems);
+  FAN_CHECK(cur_.partials != nullptr && cur_.pairs + pairs <= cur_.pairs_cap,
+            "trust ratio: more update regions than the request's partials buffer holds");
+  double* part = cur_.partials + 2 * (size_t)cur_.pairs;
+  cur_.pairs += pairs;
+  const float* words = cur_.words;
+  const LambParams p = lamb_at(req, off);
+  float* master = req.master + off;
+  float* mom = req.mom + off;
+  bf16_t* lp = req.lp ? req.lp + off : nullptr;
+  cur_.apply.push_back([=](hipStream_t es) {
+    launch_wire_lamb_apply(master, lp, mom, p, words, (size_t)shard_elems, skip_shard, skip_period, (size_t)nv,
+                           adapt_end, es);
+  });
+  return [=](hipStream_t es) {
+    launch_wire_lamb_moments(c, wire, (size_t)shard_elems, n_shards, skip_shard, skip_period, master, mom, p,
+                             (size_t)nv, adapt_end, part, es, shard_stride);
+  };
+}
+
+EpiThunk AllReduceEngine::make_epilogue(const EngineRequest& req, const uint8_t* wire, int64_t shard_elems,
+                                        int n_shards, int64_t off, int64_t len, int skip_shard, int skip_period) {
+  const int c = cfg_.codec;
+  const int64_t nv = valid_in(req.n_valid, off, len);
+  if (trust(req) && nv > 0) {
+    const EpiThunk pass1 = lamb_region(req, wire, shard_elems, n_shards, off, nv, skip_shard, skip_period);
+    float* out_sum = req.out_sum;
+    return [=](hipStream_t es) {
+      pass1(es);
+      if (out_sum) launch_wire_unpack(c, kF32, wire, out_sum + off, (size_t)shard_elems, n_shards, es);
+    };
+  }
   return [=](hipStream_t es) { epilogue(req, c, es, wire, shard_elems, n_shards, off, len, skip_shard, skip_period); };
 }
 
@@ -519,7 +561,14 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineL
   {
     RoctxRange rr("fan/mesh/direct_epilogue");
     const int64_t nv = valid_in(req.n_valid, 0, L.n_pad);
-    if (req.update && nv > 0) update_at(req, c, Gv, (size_t)s, N, -1, 0, 0, (size_t)nv, st, gstride);
+    // Trust ratio: pass 1 reads the arena in place, here on the comm stream before the slot is released; the ratio
+    // and pass 2 (dense, no wire) follow as submit()'s thunks on the epilogue stream, which waits for comm_done,
+    // recorded after this launch. kTpCommEnd is marked above, so a request trace counts all three launches in its
+    // epilogue phase (kTpCommEnd -> kTpEpiEnd), although pass 1 runs on this stream, like the plain update of this
+    // path, and the other two on the epilogue stream.
+    if (trust(req) && nv > 0)
+      lamb_region(req, Gv, s, N, 0, nv, -1, 0, gstride)(st);
+    else if (req.update && nv > 0) update_at(req, c, Gv, (size_t)s, N, -1, 0, 0, (size_t)nv, st, gstride);
     if (req.out_sum) launch_wire_unpack_strided(c, kF32, Gv, gstride, req.out_sum, (size_t)s, N, st);
   }
   d->release(r2, st);
@@ -996,6 +1045,16 @@ int AllReduceEngine::submit(const EngineRequest& req, hipStream_t producer) {
   cur_ = Current{};
   FAN_CHECK(req.upd.kind != kOptAdamW || !req.update || (req.mom != nullptr && req.upd.adamw.var != nullptr),
             "AdamW needs both moment planes");
+  if (trust(req)) {
+    // Every weight of the bucket waits for two norms over the whole bucket, so a schedule that updates part of it
+    // before the rest is reduced cannot carry the request (refused before the request takes a slot).
+    FAN_CHECK(!sharded(req), "trust ratio: not with the sharded update (shard_update), whose owners update their "
+                             "shard before the bucket is reduced");
+    FAN_CHECK(layout(req.n_valid, req.layout_shard, req.layout_chunks).chunks <= 1,
+              "trust ratio: not with a chunked layout (layout_chunks > 1, or a bucket above chunk_elems)");
+    FAN_CHECK(!(cfg_.compat_owner_fp32 && cfg_.algo == 1), "trust ratio: not with the ring's compat_owner_fp32");
+    FAN_CHECK(req.n_adapt >= -1 && req.n_adapt <= req.n_valid, "trust ratio: n_adapt must lie in [0, n_valid]");
+  }
   FAN_HIP_CHECK(hipSetDevice(device_));
   // slot state machine (slot_table.h): the next slot (a still-deferred occupant is committed first, ordered after
   // the producer: the NIC's 8-deep command queue never drops a request), ordering after anything that may still
@@ -1031,7 +1090,27 @@ int AllReduceEngine::submit(const EngineRequest& req, hipStream_t producer) {
     FAN_CHECK(cfg_.codec == kBfpTrunc || cfg_.codec == kBfpRne, "prepacked input needs a BFP codec");
     FAN_CHECK(req.prepacked_elems % 16 == 0 && req.prepacked_elems <= L.n_pad, "bad prepacked_elems");
   }
+  if (trust(req)) {
+    // one partials segment per region a schedule may hand to make_epilogue: one (mesh), or one per ring
+    const int cap = lamb_partials_for(~size_t(0) >> 1), regions = cfg_.algo == 1 ? std::max(1, L.rings) : 1;
+    cur_.pairs_cap = cap * regions;
+    cur_.partials = reinterpret_cast<double*>(epi_scratch("lamb_partials", (size_t)cur_.pairs_cap * 16));
+    cur_.words = req.trust_out ? req.trust_out : reinterpret_cast<float*>(epi_scratch("lamb_words", 16));
+  }
   std::vector<EpiThunk> thunks = cfg_.algo == 0 ? run_mesh(L, req) : run_ring(L, req);
+  if (trust(req)) {
+    // the regions' pass-1 launches are enqueued (direct mesh) or in `thunks`; then one ratio over every region's
+    // partials in region order, then the regions' pass 2 — all on the one stream the slot table runs a request's
+    // thunks on, in this order. A request without a valid element (n_valid == 0) has no region: its ratio launch
+    // sums nothing and writes {lr, lr, 1}, so the words are always this request's.
+    const double* partials = cur_.partials;
+    float* words = cur_.words;
+    const int pairs = cur_.pairs;
+    const float lr = req.upd.lamb.lr;
+    thunks.push_back([=](hipStream_t es) { launch_lamb_ratio(partials, pairs, lr, words, es); });
+    for (auto& t : cur_.apply) thunks.push_back(std::move(t));
+    cur_.apply.clear();
+  }
   FAN_HIP_CHECK(hipGetLastError());
   // phases this schedule does not have (ring hops, the world-1 local path) collapse onto the end of comm
   for (int tp = kTpPacked; tp <= kTpCommEnd; ++tp)

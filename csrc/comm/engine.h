@@ -131,11 +131,15 @@ enum VerifySite : uint32_t {
 // The weight update of one request: SGD (the default), or AdamW with its own scalars and second-moment plane
 // (adamw.var; the first moment travels where SGD's momentum does). One value through every schedule, so a site that
 // offsets the planes offsets adamw.var with them (update_at in engine.cpp).
+// trust (kOptAdamW only): the layer-wise trust ratio (LAMB) — the update is then the two-pass epilogue of
+// bfp_format.h (launch_wire_lamb_*) with `lamb`'s scalars, and adamw.var still names the second-moment plane.
 enum OptKind : int { kOptSgd = 0, kOptAdamW = 1 };
 struct UpdateParams {
   int kind = kOptSgd;
   SgdParams sgd{};
   AdamWParams adamw{};
+  bool trust = false;
+  LambParams lamb{};
 };
 
 // One all-reduce request, as submit() takes it and every schedule passes it on. grad: padded flat buffer (f32 or
@@ -156,6 +160,11 @@ struct EngineRequest {
   int64_t n_valid = 0;
   UpdateParams upd{};
   bool update = true;
+  // trust-ratio requests (upd.trust): flat elements [0, n_adapt) are the adapted tensor, the rest (a layer bucket's
+  // bias segment) take ratio 1 (-1: n_valid); trust_out: three f32 device words {lr * phi, lr, phi} the request
+  // writes (nullptr: a per-slot scratch of the engine holds them)
+  int64_t n_adapt = -1;
+  float* trust_out = nullptr;
   float* out_sum = nullptr;
   const uint8_t* prepacked = nullptr;
   int64_t prepacked_elems = 0;
@@ -313,14 +322,26 @@ class AllReduceEngine {
     uint32_t seq = 0;                  // its sequence number (what its messages' tags carry)
     int trace = -1;                    // its index into trace_pool_ (-1: not traced)
     unsigned marked = 1u << kTpStart;  // trace points its schedule has recorded
+    // trust-ratio request: the regions its schedule handed to make_epilogue (each a pass-1 launch with its own
+    // segment of `partials`, and a pass-2 launch submit() appends after the ratio), see lamb_region
+    double* partials = nullptr;
+    float* words = nullptr;
+    int pairs = 0, pairs_cap = 0;  // {S_w, S_r} pairs the regions so far write / the buffer holds
+    std::vector<EpiThunk> apply;
   } cur_;
+  bool trust(const EngineRequest& req) const { return req.update && req.upd.kind == kOptAdamW && req.upd.trust; }
+  // One gathered wire region of the trust-ratio request being built, covering nv > 0 valid elements from bucket
+  // element `off`: returns its pass-1 thunk (which writes the region's own segment of cur_.partials) and records its
+  // pass-2 thunk in cur_.apply; submit() appends the ratio thunk and those after the schedule's own thunks.
+  EpiThunk lamb_region(const EngineRequest& req, const uint8_t* wire, int64_t shard_elems, int n_shards, int64_t off,
+                       int64_t nv, int skip_shard, int skip_period, size_t shard_stride = 0);
   bool sharded(const EngineRequest& req) const {  // the request runs the sharded update (EngineConfig::shard_update)
     return shard_upd_ && req.update && req.out_sum == nullptr && req.lp != nullptr;
   }
   // Epilogue of `req` (captured by value) over the gathered wire region of n_shards shards that covers bucket
   // elements [off, off + len)
   EpiThunk make_epilogue(const EngineRequest& req, const uint8_t* wire, int64_t shard_elems, int n_shards, int64_t off,
-                         int64_t len, int skip_shard = -1, int skip_period = 0) const;
+                         int64_t len, int skip_shard = -1, int skip_period = 0);
   std::vector<EpiThunk> run_mesh(const EngineLayout& L, const EngineRequest& req);
   std::vector<EpiThunk> run_mesh_direct(P2PComm* d, const EngineLayout& L, const EngineRequest& req);
   std::vector<EpiThunk> run_mesh_chunked(const EngineLayout& L, const EngineRequest& req);

@@ -39,6 +39,7 @@ class TrainConfig:
     momentum: float = 0.0
     weight_decay: float = 0.0
     optimizer: str = "sgd"         # sgd | adamw
+    trust_ratio: bool = False      # adamw: layer-wise trust ratio (LAMB)
     beta1: float = 0.9
     beta2: float = 0.999
     eps: float = 1e-8
@@ -73,6 +74,8 @@ def add_named_flags(ap: argparse.ArgumentParser):
     ap.add_argument("--weight-decay", type=float, default=d.weight_decay)
     ap.add_argument("--optimizer", default=d.optimizer, choices=["sgd", "adamw"],
                     help="weight update fused into the all-reduce epilogue")
+    ap.add_argument("--trust-ratio", action="store_true",
+                    help="AdamW: scale each layer's step by ||w|| / ||update|| (LAMB; two-pass epilogue)")
     ap.add_argument("--beta1", type=float, default=d.beta1, help="AdamW first-moment decay")
     ap.add_argument("--beta2", type=float, default=d.beta2, help="AdamW second-moment decay")
     ap.add_argument("--eps", type=float, default=d.eps, help="AdamW denominator term")

@@ -17,6 +17,8 @@ multi-shard buffers are shards back to back.
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 GROUP = 16
@@ -236,3 +238,95 @@ def adamw(w: np.ndarray, g: np.ndarray, m: np.ndarray, v: np.ndarray, scalars: A
         base = (w * s.decay).astype(np.float32) if s.wd != 0 else w
         w2 = (f64(-s.step_size) * q.astype(f64) + base.astype(f64)).astype(np.float32)
     return w2, m2, v2
+
+
+class LambScalars(tuple):
+    """The per-step scalars of AdamW with the layer-wise trust ratio (``lamb_scalars``), each already rounded to f32:
+    AdamW's moment scalars, ``rbc1 = 1 / (1 - beta1^t)``, and ``wd`` / ``lr`` themselves (the step size is multiplied
+    by the trust ratio, so it is not folded into one scalar). A class of its own beside ``AdamWScalars``, not one of
+    them: it has no ``step_size`` or ``decay``, so the AdamW update fails on it instead of taking wrong scalars."""
+    FIELDS = ("beta1", "omb1", "beta2", "omb2", "rsbc2", "eps", "rbc1", "wd", "lr")
+
+    def __new__(cls, *vals):
+        assert len(vals) == len(cls.FIELDS)
+        return super().__new__(cls, (np.float32(x) for x in vals))
+
+    def __getattr__(self, name):
+        try:
+            return self[self.FIELDS.index(name)]
+        except ValueError:
+            raise AttributeError(name) from None
+
+    def kernel_args(self):
+        """The nine scalars the native launchers take, as Python floats holding the f32 values."""
+        return [float(x) for x in self]
+
+
+def lamb_scalars(lr: float, wd: float, beta1: float, beta2: float, eps: float, step: int) -> LambScalars:
+    """The trust-ratio update's scalars of update ``step`` (1-based): float64, rounded once to f32; beta1 .. eps are
+    exactly ``adamw_scalars``' values."""
+    a = adamw_scalars(lr, wd, beta1, beta2, eps, step)
+    return LambScalars(a.beta1, a.omb1, a.beta2, a.omb2, a.rsbc2, a.eps, 1.0 / (1.0 - float(beta1) ** int(step)),
+                       float(wd), float(lr))
+
+
+def _lamb_direction(w, m2, v2, s: LambScalars):
+    """r of csrc/bfp/bfp_format.h lamb_direction from the new moments and the old weights (all f32 arrays)."""
+    f64 = np.float64
+    r = np.sqrt(v2.astype(f64)).astype(np.float32)
+    d = (r.astype(f64) * f64(s.rsbc2) + f64(s.eps)).astype(np.float32)
+    u = (m2.astype(f64) / d.astype(f64)).astype(np.float32)
+    ub = (u * s.rbc1).astype(np.float32)
+    if s.wd != 0:
+        return (f64(s.wd) * w.astype(f64) + ub.astype(f64)).astype(np.float32)
+    return ub
+
+
+def lamb_moments(w: np.ndarray, g: np.ndarray, m: np.ndarray, v: np.ndarray, scalars: LambScalars,
+                 grad_scale: float = 1.0):
+    """Pass 1 of the trust-ratio update in the kernel's operation order (lamb_moments / lamb_direction of
+    csrc/bfp/bfp_format.h; fma, sqrt and division emulated in float64 and rounded, as ``adamw``): the new moments —
+    ``adamw``'s statements, the same bits — and the direction r. Returns (m', v', r); w is not changed."""
+    s = scalars
+    f64 = np.float64
+    w = np.asarray(w, np.float32)
+    m = np.asarray(m, np.float32)
+    v = np.asarray(v, np.float32)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore", under="ignore"):
+        g = (np.asarray(g, np.float32) * np.float32(grad_scale)).astype(np.float32)
+        t1 = (s.omb1 * g).astype(np.float32)
+        m2 = (f64(s.beta1) * m.astype(f64) + t1.astype(f64)).astype(np.float32)
+        t2 = ((s.omb2 * g).astype(np.float32) * g).astype(np.float32)
+        v2 = (f64(s.beta2) * v.astype(f64) + t2.astype(f64)).astype(np.float32)
+        r = _lamb_direction(w, m2, v2, s)
+    return m2, v2, r
+
+
+def lamb_ratio(w: np.ndarray, r: np.ndarray, n_adapt: int, lr: float) -> np.ndarray:
+    """The three f32 scale words {lr * phi, lr, phi}: phi = f32(sqrt(S_w / S_r)) over the first ``n_adapt`` elements,
+    the sums of the (exact) float64 squares taken with ``math.fsum``; 1 unless both sums are positive and finite."""
+    w64 = np.asarray(w, np.float32)[:n_adapt].astype(np.float64)
+    r64 = np.asarray(r, np.float32)[:n_adapt].astype(np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        sw, sr = math.fsum(w64 * w64) if np.isfinite(w64).all() else math.inf, \
+            math.fsum(r64 * r64) if np.isfinite(r64).all() else math.inf
+    return lamb_words(sw, sr, lr)
+
+
+def lamb_words(sw: float, sr: float, lr: float) -> np.ndarray:
+    """{lr * phi, lr, phi} in f32 from the two float64 sums (``lamb_ratio``); lr * phi is one f32 product."""
+    ok = sw > 0 and sr > 0 and math.isfinite(sw) and math.isfinite(sr)
+    phi = np.float32(math.sqrt(sw / sr)) if ok else np.float32(1.0)
+    lr32 = np.float32(lr)
+    return np.array([lr32 * phi, lr32, phi], np.float32)
+
+
+def lamb_apply(w: np.ndarray, m2: np.ndarray, v2: np.ndarray, scalars: LambScalars, words: np.ndarray,
+               n_adapt: int) -> np.ndarray:
+    """Pass 2: r recomputed from the stored moments and the untouched weights (pass 1's statements),
+    w' = fma(-(i < n_adapt ? words[0] : words[1]), r, w). Returns w'."""
+    w = np.asarray(w, np.float32)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore", under="ignore"):
+        r = _lamb_direction(w, np.asarray(m2, np.float32), np.asarray(v2, np.float32), scalars)
+        scale = np.where(np.arange(w.size) < n_adapt, np.float32(words[0]), np.float32(words[1])).astype(np.float32)
+        return (-scale.astype(np.float64) * r.astype(np.float64) + w.astype(np.float64)).astype(np.float32)

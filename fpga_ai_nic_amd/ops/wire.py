@@ -6,6 +6,8 @@ multi-process tests exercise exactly the same numerics as the GPU path.
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
 
@@ -123,6 +125,8 @@ def adamw(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Ten
     c = codec_id(codec)
     if mom is None or var is None:
         raise ValueError("AdamW needs both moment planes (mom, var)")
+    if not isinstance(scalars, O.AdamWScalars):
+        raise TypeError(f"wire.adamw takes bfp_oracle.adamw_scalars, got {type(scalars).__name__}")
     n_valid = master.numel() if n_valid is None else int(n_valid)
     if master.is_cuda:
         _ext.require().wire_adamw(wire, int(shard_elems), int(n_shards), int(skip_shard), int(skip_period), master,
@@ -146,5 +150,103 @@ def adamw(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Ten
         if hi <= lo:
             continue
         w[lo:hi], m[lo:hi], v[lo:hi] = O.adamw(w[lo:hi], g[lo:hi], m[lo:hi], v[lo:hi], scalars, grad_scale)
+        if lp is not None:
+            lp.view(-1)[lo:hi].copy_(master.view(-1)[lo:hi].to(lp.dtype))
+
+
+def _lamb_ranges(shard_elems, n_shards, n_valid, skip_shard, skip_period):
+    """The flat [lo, hi) ranges one trust-ratio launch covers: every shard but the skipped ones, cut at n_valid."""
+    period = skip_period if skip_period >= 1 else (1 << 30)
+    out = []
+    for s in range(n_shards):
+        if skip_shard >= 0 and s % period == skip_shard:
+            continue
+        lo, hi = s * shard_elems, min((s + 1) * shard_elems, n_valid)
+        if hi > lo:
+            out.append((lo, hi))
+    return out
+
+
+def _sum64(x: np.ndarray) -> float:
+    """Exactly rounded float64 sum (math.fsum); a non-finite term gives numpy's non-finite sum instead of an error."""
+    if np.isfinite(x).all():
+        return math.fsum(x)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return float(np.sum(x))
+
+
+def lamb_partials_for(master: torch.Tensor, shard_elems: int) -> int:
+    """{S_w, S_r} pairs one :func:`lamb_moments` launch over shards of ``shard_elems`` writes (CPU: one)."""
+    return int(_ext.require().lamb_partials_for(int(shard_elems))) if master.is_cuda else 1
+
+
+def lamb_moments(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Tensor, *, codec,
+                 mom: torch.Tensor, var: torch.Tensor, scalars: O.LambScalars, partials: torch.Tensor,
+                 partials_base: int = 0, grad_scale: float = 1.0, n_valid: int | None = None,
+                 n_adapt: int | None = None, skip_shard: int = -1, skip_period: int = 0, shard_stride: int = 0) -> int:
+    """Pass 1 of the trust-ratio (LAMB) update (``bfp_oracle.lamb_moments``): decode the wire, store the new moments
+    in ``mom`` / ``var``, leave ``master`` untouched, and write the launch's fp64 partial sums of w^2 and r^2 over the
+    flat elements below ``n_adapt`` (default ``n_valid``) as {S_w, S_r} pairs from pair ``partials_base`` of
+    ``partials`` (float64). Returns the pairs written (:func:`lamb_partials_for`); :func:`lamb_ratio` sums the pairs of
+    every launch of a request."""
+    c = codec_id(codec)
+    if mom is None or var is None:
+        raise ValueError("the trust-ratio update needs both moment planes (mom, var)")
+    n_valid = master.numel() if n_valid is None else int(n_valid)
+    n_adapt = n_valid if n_adapt is None else int(n_adapt)
+    if not 0 <= n_adapt <= n_valid:
+        raise ValueError(f"n_adapt must lie in [0, n_valid = {n_valid}], got {n_adapt}")
+    if master.is_cuda:
+        return int(_ext.require().wire_lamb_moments(wire, int(shard_elems), int(n_shards), int(skip_shard),
+                                                    int(skip_period), master, mom, var, scalars.kernel_args(),
+                                                    float(grad_scale), n_valid, n_adapt, partials,
+                                                    int(partials_base), c, int(shard_stride)))
+    sb = O.shard_bytes(c, shard_elems)
+    raw = _np_u8(wire)
+    if shard_stride:
+        raw = np.concatenate([raw[s * shard_stride: s * shard_stride + sb] for s in range(n_shards)])
+    g = O.unpack(raw, shard_elems * n_shards, shard_elems, c)
+    w, m, v = master.view(-1).numpy(), mom.view(-1).numpy(), var.view(-1).numpy()
+    sw, sr = [], []
+    for lo, hi in _lamb_ranges(shard_elems, n_shards, n_valid, skip_shard, skip_period):
+        m[lo:hi], v[lo:hi], r = O.lamb_moments(w[lo:hi], g[lo:hi], m[lo:hi], v[lo:hi], scalars, grad_scale)
+        k = max(0, min(n_adapt, hi) - lo)
+        sw.append(w[lo:lo + k].astype(np.float64) ** 2)
+        sr.append(r[:k].astype(np.float64) ** 2)
+    tot = [_sum64(np.concatenate(x)) if x else 0.0 for x in (sw, sr)]
+    partials.view(-1)[2 * partials_base: 2 * partials_base + 2] = torch.tensor(tot, dtype=torch.float64)
+    return 1
+
+
+def lamb_ratio(partials: torch.Tensor, n_pairs: int, lr: float, words: torch.Tensor):
+    """Sum ``n_pairs`` {S_w, S_r} pairs in float64 and write the three f32 words {lr * phi, lr, phi}
+    (``bfp_oracle.lamb_words``) into ``words``."""
+    if partials.is_cuda:
+        _ext.require().lamb_ratio(partials, int(n_pairs), float(lr), words)
+        return
+    p = partials.view(-1)[: 2 * n_pairs].numpy()
+    sums = [_sum64(x) for x in (p[0::2], p[1::2])]
+    words.view(-1)[:3] = torch.from_numpy(O.lamb_words(sums[0], sums[1], lr))
+
+
+def lamb_apply(master: torch.Tensor, shard_elems: int, *, mom: torch.Tensor, var: torch.Tensor,
+               scalars: O.LambScalars, words: torch.Tensor, lp: torch.Tensor | None = None,
+               n_valid: int | None = None, n_adapt: int | None = None, skip_shard: int = -1, skip_period: int = 0):
+    """Pass 2 (``bfp_oracle.lamb_apply``): master -= (i < n_adapt ? words[0] : words[1]) * r over [0, n_valid), r
+    recomputed from the moments pass 1 stored; lp = bf16(master). Shards (of ``shard_elems``) that pass 1 skipped
+    are skipped alike."""
+    n_valid = master.numel() if n_valid is None else int(n_valid)
+    n_adapt = n_valid if n_adapt is None else int(n_adapt)
+    if not 0 <= n_adapt <= n_valid:
+        raise ValueError(f"n_adapt must lie in [0, n_valid = {n_valid}], got {n_adapt}")
+    if master.is_cuda:
+        _ext.require().wire_lamb_apply(master, lp, mom, var, scalars.kernel_args(), words, int(shard_elems),
+                                       int(skip_shard), int(skip_period), n_valid, n_adapt)
+        return
+    w, m, v = master.view(-1).numpy(), mom.view(-1).numpy(), var.view(-1).numpy()
+    wd = words.view(-1)[:3].numpy()
+    n_shards = -(-n_valid // shard_elems)
+    for lo, hi in _lamb_ranges(shard_elems, n_shards, n_valid, skip_shard, skip_period):
+        w[lo:hi] = O.lamb_apply(w[lo:hi], m[lo:hi], v[lo:hi], scalars, wd, max(0, min(n_adapt, hi) - lo))
         if lp is not None:
             lp.view(-1)[lo:hi].copy_(master.view(-1)[lo:hi].to(lp.dtype))

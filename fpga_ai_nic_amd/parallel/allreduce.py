@@ -69,18 +69,28 @@ def _round_up(a, b):
 OPTIMIZERS = ("sgd", "adamw")
 
 
-def adamw_request(opt, mom, var, *, lr, weight_decay, momentum, nesterov, betas, eps, step):
+def adamw_request(opt, mom, var, *, lr, weight_decay, momentum, nesterov, betas, eps, step, trust_ratio=False,
+                  n_adapt=None, n_valid=None):
     """Validate one request's optimizer arguments; the step's ``bfp_oracle.AdamWScalars`` for ``opt="adamw"``
-    (``mom`` the first moment, ``var`` the second, ``step`` the bucket's 1-based update count), None for SGD."""
+    (``mom`` the first moment, ``var`` the second, ``step`` the bucket's 1-based update count), None for SGD.
+    ``trust_ratio`` (AdamW only): the layer-wise trust ratio (LAMB) over the bucket's first ``n_adapt`` of ``n_valid``
+    elements; the scalars are then ``bfp_oracle.LambScalars``."""
     if opt not in OPTIMIZERS:
         raise ValueError(f"unknown optimizer {opt!r} (one of {OPTIMIZERS})")
+    if trust_ratio and opt != "adamw":
+        raise ValueError("trust_ratio is a flag of opt='adamw' (LARS on the SGD path is not provided)")
+    if n_adapt is not None and not trust_ratio:
+        raise ValueError("n_adapt belongs to trust_ratio=True")
+    if trust_ratio and n_adapt is not None and not 0 <= int(n_adapt) <= int(n_valid):
+        raise ValueError(f"n_adapt must lie in [0, n_valid = {n_valid}], got {n_adapt}")
     if opt == "sgd":
         return None
     if momentum or nesterov:
         raise ValueError("momentum / nesterov belong to SGD: AdamW's first moment is governed by betas[0]")
     if step is None:
         raise ValueError("AdamW needs step, the 1-based update count of the bucket")
-    scalars = wire.O.adamw_scalars(lr, weight_decay, betas[0], betas[1], eps, step)
+    scalars = (wire.O.lamb_scalars if trust_ratio else wire.O.adamw_scalars)(lr, weight_decay, betas[0], betas[1],
+                                                                               eps, step)
     if mom is None or var is None:
         raise ValueError("AdamW needs both moment planes: mom (first) and var (second)")
     return scalars
@@ -303,21 +313,40 @@ class CompressedAllReduce:
                       grad_scale: float = 1.0, weight_decay: float = 0.0, momentum: float = 0.0,
                       nesterov: bool = False, update_after=None, defer: bool = False,
                       name: str = "bucket", opt: str = "sgd", var: torch.Tensor | None = None,
-                      betas=(0.9, 0.999), eps: float = 1e-8, step: int | None = None) -> Handle:
+                      betas=(0.9, 0.999), eps: float = 1e-8, step: int | None = None, trust_ratio: bool = False,
+                      n_adapt: int | None = None, trust_out: torch.Tensor | None = None) -> Handle:
         """All-reduce ``grad`` (flat, padded to ``layout(n).n_pad``) and apply SGD to ``master`` (+bf16 ``lp``).
         ``opt="adamw"``: AdamW instead, ``mom`` / ``var`` the first / second moment planes (both required), ``step``
-        the bucket's 1-based update count."""
-        scalars = adamw_request(opt, mom, var, lr=lr, weight_decay=weight_decay, momentum=momentum,
-                                nesterov=nesterov, betas=betas, eps=eps, step=step)
+        the bucket's 1-based update count. ``trust_ratio`` (AdamW): scale the step of the bucket's first ``n_adapt``
+        elements (default all ``n_valid``; the rest, a bias segment, take ratio 1) by ||w|| / ||update|| (LAMB): the
+        epilogue becomes two passes around one norm reduction, and ``trust_out`` (3 f32, optional) receives
+        {lr * phi, lr, phi}."""
         n_valid = int(n_valid if n_valid is not None else master.numel())
+        scalars = adamw_request(opt, mom, var, lr=lr, weight_decay=weight_decay, momentum=momentum,
+                                nesterov=nesterov, betas=betas, eps=eps, step=step, trust_ratio=trust_ratio,
+                                n_adapt=n_adapt, n_valid=n_valid)
+        lamb = isinstance(scalars, wire.O.LambScalars)
+        if lamb and self.compat_owner_fp32 and self.algo == "ring":
+            raise ValueError("trust_ratio: not with compat_owner_fp32 (the owner's slices would be updated from "
+                             "another gradient than the one the norms were taken over)")
+        n_adapt = n_valid if n_adapt is None else int(n_adapt)
         L = self.layout(n_valid)
         self._check(grad, L)
         sgd_kw = dict(lr=lr, grad_scale=grad_scale, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov)
+        tr = dict(pairs=0, regions=[])  # trust ratio: the regions pass 1 has run over, for the ratio and pass 2
 
         def update(G, shard, n_shards, off, length, nv, codec, skip=(-1, 0)):
             planes = dict(lp=None if lp is None else lp.view(-1)[off:off + length],
                           mom=None if mom is None else mom.view(-1)[off:off + length])
-            if scalars is not None:
+            if lamb:
+                adapt = max(0, min(n_adapt - off, nv))
+                tr["pairs"] += wire.lamb_moments(G, shard, n_shards, master.view(-1)[off:off + length], codec=codec,
+                                                 mom=planes["mom"], var=var.view(-1)[off:off + length],
+                                                 scalars=scalars, partials=tr["partials"], partials_base=tr["pairs"],
+                                                 grad_scale=grad_scale, n_valid=nv, n_adapt=adapt,
+                                                 skip_shard=skip[0], skip_period=skip[1])
+                tr["regions"].append((shard, off, length, nv, adapt, skip))
+            elif scalars is not None:
                 wire.adamw(G, shard, n_shards, master.view(-1)[off:off + length], codec=codec,
                            var=var.view(-1)[off:off + length], scalars=scalars, grad_scale=grad_scale, n_valid=nv,
                            skip_shard=skip[0], skip_period=skip[1], **planes)
@@ -336,7 +365,25 @@ class CompressedAllReduce:
             if nv:
                 update(buf, length, 1, off, length, nv, "raw_f32")
 
-        return self._launch(lambda: self._run(L, grad, finish, owner_fp32), name, L, defer, update_after)
+        def lamb_finish():  # after every region's pass 1: one ratio over all their partials, then their pass 2
+            wire.lamb_ratio(tr["partials"], tr["pairs"], lr, tr["words"])
+            for shard, off, length, nv, adapt, skip in tr["regions"]:
+                wire.lamb_apply(master.view(-1)[off:off + length], shard, mom=mom.view(-1)[off:off + length],
+                                var=var.view(-1)[off:off + length], scalars=scalars, words=tr["words"],
+                                lp=None if lp is None else lp.view(-1)[off:off + length], n_valid=nv, n_adapt=adapt,
+                                skip_shard=skip[0], skip_period=skip[1])
+
+        def comm():
+            if not lamb:
+                return self._run(L, grad, finish, owner_fp32)
+            # one partials segment per region a schedule hands to finish(): one (mesh), or one per ring
+            cap = wire.lamb_partials_for(master, 1 << 40)
+            tr["partials"] = self._buf(L, "lamb_partials", 16 * cap * max(1, self.rings), torch.float64, per_slot=True)
+            tr["words"] = trust_out.view(-1) if trust_out is not None else \
+                self._buf(L, "lamb_words", 12, torch.float32, per_slot=True)
+            return list(self._run(L, grad, finish, owner_fp32)) + [lamb_finish]
+
+        return self._launch(comm, name, L, defer, update_after)
 
     def allreduce(self, grad: torch.Tensor, out: torch.Tensor, *, n_valid: int | None = None,
                   name: str = "bucket") -> Handle:
@@ -577,9 +624,12 @@ class CompressedAllReduce:
 
 def uncompressed_allreduce_sgd(transport: Transport, grad, master, lp=None, mom=None, *, n_valid=None, lr,
                                grad_scale=1.0, weight_decay=0.0, momentum=0.0, nesterov=False, opt="sgd", var=None,
-                               betas=(0.9, 0.999), eps=1e-8, step=None):
+                               betas=(0.9, 0.999), eps=1e-8, step=None, trust_ratio=False):
     """Baseline: RCCL all-reduce (sum) of the raw gradients + a separate SGD (or AdamW) kernel (BASELINE config 2;
     the reference's commented MPI_Iallreduce + libxsmm opt path, sw:615-647)."""
+    if trust_ratio:
+        raise ValueError("trust_ratio belongs to the compressed engines' two-pass epilogue; the uncompressed baseline "
+                         "has a single update kernel")
     scalars = adamw_request(opt, mom, var, lr=lr, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov,
                             betas=betas, eps=eps, step=step)
     transport.all_reduce_(grad)

@@ -83,11 +83,14 @@ class DataParallelTrainer:
                  loss_scale: float = 1.0, average: bool = True, profile: bool = False, prepack: bool = True,
                  commit_at_end: bool | None = None, fused_update: bool | None = None,
                  gemm_inflight: str | None = None, wgrad_pair: bool | str | None = None, optimizer: str = "sgd",
-                 betas=(0.9, 0.999), eps: float = 1e-8):
+                 betas=(0.9, 0.999), eps: float = 1e-8, trust_ratio: bool = False):
         """``optimizer``: 'sgd' or 'adamw' (``betas``, ``eps``; the model must hold the second-moment planes,
         ``MLP(..., adam=True)``). AdamW runs in the engine's decode + update epilogue — not in the bwd-weight GEMM's,
         so ``fused_update`` is off with it — with ``opt_step``, the 1-based update count, advanced once per
-        ``backward_pass``.
+        ``backward_pass``. ``trust_ratio`` (AdamW): the layer-wise trust ratio (LAMB) — each layer's weight matrix
+        steps by lr * ||W|| / ||update||, its bias by lr — through the engines' two-pass epilogue; ``trust_ratios``
+        ([L, 3] f32 on the model's device) then holds every layer's {lr * phi, lr, phi} of the last step, written by
+        the requests themselves (no host sync). Not with a sharded-update engine.
 
         ``fused_update`` (default env FAN_FUSED_UPDATE, else on): with a single-rank engine (world 1, requests
         inline: the all-reduce of one rank is the identity) and the GEMM-encoded wire, the bwd-weight GEMM's epilogue
@@ -122,6 +125,15 @@ class DataParallelTrainer:
             wire.O.adamw_scalars(lr, weight_decay, self.betas[0], self.betas[1], self.eps, 1)  # validates
             if any(l.mom is None or l.var is None for l in model.layers):
                 raise ValueError("optimizer='adamw' needs a model with both moment planes: MLP(..., adam=True)")
+        self.trust_ratio = bool(trust_ratio)
+        if self.trust_ratio and optimizer != "adamw":
+            raise ValueError("trust_ratio is a flag of optimizer='adamw'")
+        if self.trust_ratio and bool(getattr(engine, "shard_update", False)):
+            raise ValueError("trust_ratio: not with a sharded-update engine (each owner updates its shard before the "
+                             "bucket is reduced)")
+        self.trust_ratios = (torch.zeros(model.L, 3, dtype=torch.float32, device=model.device)
+                             if self.trust_ratio else None)
+        self._trust_partials = None  # the engine-less update's norm partials
         self.loss_scale = loss_scale
         # gradients are of the LOCAL mean loss; the all-reduce sums over ranks -> average with 1/N
         self.grad_scale = (1.0 / self.world) if average else 1.0
@@ -182,9 +194,31 @@ class DataParallelTrainer:
         """The optimizer arguments of layer l's request in the step being enqueued."""
         if self.optimizer != "adamw":
             return {}
-        return dict(opt="adamw", var=l.var, betas=self.betas, eps=self.eps, step=self.opt_step)
+        kw = dict(opt="adamw", var=l.var, betas=self.betas, eps=self.eps, step=self.opt_step)
+        if self.trust_ratio:
+            kw.update(trust_ratio=True, n_adapt=self._n_adapt(l), trust_out=self._trust_row(l))
+        return kw
+
+    def _trust_row(self, l):
+        """Layer l's row of ``trust_ratios`` (found by identity: buckets of equal shape compare by their tensors)."""
+        return self.trust_ratios[next(i for i, x in enumerate(self.m.layers) if x is l)]
+
+    def _n_adapt(self, l):
+        """The adapted tensor of layer l's bucket: its weight matrix; the bias segment behind it takes ratio 1."""
+        return l.cin * l.cout if self.m.bias else l.n
 
     def _sgd_local(self, l):
+        if self.trust_ratio:
+            scalars = wire.O.lamb_scalars(self.lr, self.wd, self.betas[0], self.betas[1], self.eps, self.opt_step)
+            if self._trust_partials is None:
+                self._trust_partials = torch.zeros(2 * wire.lamb_partials_for(l.master, 1 << 40), dtype=torch.float64,
+                                                   device=l.master.device)
+            words, kw = self._trust_row(l), dict(n_valid=l.n, n_adapt=self._n_adapt(l))
+            k = wire.lamb_moments(wire.as_bytes(l.grad), l.n_pad, 1, l.master, codec="raw_f32", mom=l.mom, var=l.var,
+                                  scalars=scalars, partials=self._trust_partials, grad_scale=self.grad_scale, **kw)
+            wire.lamb_ratio(self._trust_partials, k, self.lr, words)
+            wire.lamb_apply(l.master, l.n_pad, mom=l.mom, var=l.var, scalars=scalars, words=words, lp=l.lp, **kw)
+            return
         if self.optimizer == "adamw":
             scalars = wire.O.adamw_scalars(self.lr, self.wd, self.betas[0], self.betas[1], self.eps, self.opt_step)
             wire.adamw(wire.as_bytes(l.grad), l.n_pad, 1, l.master, codec="raw_f32", lp=l.lp, mom=l.mom, var=l.var,

@@ -140,6 +140,7 @@ class NativeAllReduce:
             comm = transport.comm
         self.codec, self.codec_id, self.algo = codec, wire.codec_id(codec), algo
         self.timeout_s = timeout_s
+        self.compat_owner_fp32 = bool(compat_owner_fp32)
         if isinstance(links, str):
             links = None
             if algo == "ring" and self.world > 1 and not isinstance(comm, C.LoopbackComm):
@@ -246,20 +247,37 @@ class NativeAllReduce:
                       nesterov: bool = False, update_after=None, defer: bool = False,
                       name: str = "bucket", prepacked=None, layout=None, on_producer: bool = False,
                       opt: str = "sgd", var: torch.Tensor | None = None, betas=(0.9, 0.999), eps: float = 1e-8,
-                      step: int | None = None) -> NativeHandle:
+                      step: int | None = None, trust_ratio: bool = False, n_adapt: int | None = None,
+                      trust_out: torch.Tensor | None = None) -> NativeHandle:
         """``opt="adamw"``: AdamW instead of SGD, ``mom`` / ``var`` the first / second moment planes (both required),
-        ``step`` the bucket's 1-based update count (as :meth:`CompressedAllReduce.allreduce_sgd`).
+        ``step`` the bucket's 1-based update count (as :meth:`CompressedAllReduce.allreduce_sgd`). ``trust_ratio`` /
+        ``n_adapt`` / ``trust_out``: the layer-wise trust ratio (LAMB), as there; refused with the sharded update, a
+        chunked layout and ``compat_owner_fp32``, which update part of a bucket before the whole of it is reduced.
         ``prepacked=(wire_u8, elems)``: flat elements [0, elems) were already encoded into ``wire_u8``
         (from :meth:`prepack_target`); the engine encodes the rest and skips its pack pass. ``layout=(shard,
         chunks)``: an explicit chunked mesh layout (shard elements x world x chunks). ``on_producer``: run the request on the
         current (producer) stream instead of the engine's comm stream — the last request of a backward, which has
         nothing left to overlap with (saves two cross-stream hand-offs on the critical path)."""
-        scalars = adamw_request(opt, mom, var, lr=lr, weight_decay=weight_decay, momentum=momentum,
-                                nesterov=nesterov, betas=betas, eps=eps, step=step)
-        okw = {} if scalars is None else dict(opt=1, var=var.view(-1), adamw=scalars.kernel_args())
         n_valid = int(n_valid if n_valid is not None else master.numel())
+        scalars = adamw_request(opt, mom, var, lr=lr, weight_decay=weight_decay, momentum=momentum,
+                                nesterov=nesterov, betas=betas, eps=eps, step=step, trust_ratio=trust_ratio,
+                                n_adapt=n_adapt, n_valid=n_valid)
         pre, pre_n = (None, 0) if prepacked is None else prepacked
         ls, lc = (0, 0) if layout is None else (int(layout[0]), int(layout[1]))
+        okw = {} if scalars is None else dict(opt=1, var=var.view(-1), adamw=scalars.kernel_args())
+        if trust_ratio:
+            if self.shard_update:
+                raise ValueError("trust_ratio: not with a sharded-update engine (each owner updates its shard before "
+                                 "the bucket is reduced)")
+            if self.compat_owner_fp32 and self.algo == "ring":
+                raise ValueError("trust_ratio: not with compat_owner_fp32")
+            if self.C.layout(n_valid, ls, lc)["chunks"] > 1:
+                raise ValueError("trust_ratio: not with a chunked layout (the chunks' epilogues run before the whole "
+                                 "bucket is reduced)")
+            a = wire.O.adamw_scalars(lr, weight_decay, betas[0], betas[1], eps, step)
+            okw = dict(opt=1, var=var.view(-1), adamw=a.kernel_args(), lamb=scalars.kernel_args(),
+                       n_adapt=-1 if n_adapt is None else int(n_adapt),
+                       trust_out=None if trust_out is None else trust_out.view(-1))
         # an immediate request (no ordering after the producer's later work) is committed by the engine itself, so
         # a chunked bucket runs its per-chunk epilogues inside the pipeline (bounded scratch)
         eng_defer = defer or update_after is not None
