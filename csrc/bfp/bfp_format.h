@@ -36,6 +36,18 @@ struct SgdParams {
   int nesterov;
 };
 
+// One element's SGD step (weight decay, momentum, Nesterov), all f32. Every update path calls it (wire_sgd_kernel,
+// the merged reduce-and-update kernel, the GEMMs' fused-update epilogues), so their weights are bit-identical.
+__device__ __forceinline__ void sgd_update(const SgdParams& p, float g, float& w, float& m, bool has_mom) {
+  float gj = g * p.grad_scale;
+  if (p.weight_decay != 0.0f) gj = fmaf(p.weight_decay, w, gj);
+  if (has_mom) {
+    m = fmaf(p.momentum, m, gj);
+    gj = p.nesterov ? fmaf(p.momentum, m, gj) : m;
+  }
+  w = fmaf(-p.lr, gj, w);
+}
+
 // AdamW (decoupled decay, bias correction) of the update kernels. The per-step scalars are computed on the host in
 // float64 and rounded once to f32 (ops/bfp_oracle.py adamw_scalars): omb1 = 1 - beta1, omb2 = 1 - beta2,
 // step_size = lr / (1 - beta1^t), rsbc2 = 1 / sqrt(1 - beta2^t), decay = 1 - lr * wd. `var` is the second-moment
@@ -303,6 +315,120 @@ struct DenseLane16 {
   __device__ static __forceinline__ void store16(T* p, size_t e, const float v[16]) {
     DenseLane<T>::store8(p, e, v);
     DenseLane<T>::store8(p, e + 8, v + 8);
+  }
+};
+
+// ---------------------------------------------------------------- lane layouts of the reduce kernels
+// What a lane of wire_reduce / wire_reduce_to / wire_reduce_sgd (bfp_kernels.hip) holds per trip: a whole group
+// (Lanes16, every codec) or 4 values of one (Lanes4, BFP codecs). Same members, same operations per value, so a kernel
+// body written against them gives the same bits in either layout. `roundtrip` turns the lane's values into what every
+// rank decodes after the owner re-encodes them with codec C.
+
+// The value every rank decodes after `x` is encoded in a group of shared exponent E.
+template <int C>
+__device__ __forceinline__ float bfp_roundtrip(float x, uint32_t E) {
+  const int32_t q = (C == kBfpTrunc) ? bfp_encode_trunc(__float_as_uint(x), E) : bfp_encode_rne(x, E);
+  const int32_t q8 = (int32_t)(int8_t)(uint8_t)((uint32_t)q & 0xFFu);  // the stored byte, as the decoder reads it
+  return (C == kBfpTrunc) ? bfp_decode_trunc(q8, E) : bfp_decode_rne(q8, E);
+}
+
+template <int C>
+struct Lanes16 {
+  static constexpr int kVals = 16;
+  __device__ static __forceinline__ void load_wire(const uint8_t* shard, size_t n_s, size_t le, float v[16]) {
+    WireLane16<C>::load16(shard, n_s, le, v);
+  }
+  template <typename T>
+  __device__ static __forceinline__ void load_dense(const T* p, size_t e, float v[16]) {
+    DenseLane16<T>::load16(p, e, v);
+  }
+  __device__ static __forceinline__ void store_wire(uint8_t* shard, size_t n_s, size_t le, const float v[16]) {
+    WireLane16<C>::store16(shard, n_s, le, v);
+  }
+  __device__ static __forceinline__ void store_f32(float* p, size_t e, const float v[16]) {
+    DenseLane16<float>::store16(p, e, v);
+  }
+  __device__ static __forceinline__ void store_bf16(bf16_t* p, size_t e, const float v[16]) {
+    DenseLane16<bf16_t>::store16(p, e, v);
+  }
+  __device__ static __forceinline__ void roundtrip(float v[16]) {
+    if constexpr (C == kBfpTrunc || C == kBfpRne) {
+      uint32_t mx = 0;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) mx = max(mx, __float_as_uint(v[j]) & 0x7FFFFFFFu);
+      const uint32_t E = mx >> 23;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) v[j] = bfp_roundtrip<C>(v[j], E);
+    } else if constexpr (C == kRawBf16) {
+#pragma unroll
+      for (int j = 0; j < 16; j += 2) {
+        const uint32_t u = pack_bf16x2(v[j], v[j + 1]);
+        v[j] = __uint_as_float(u << 16);
+        v[j + 1] = __uint_as_float(u & 0xFFFF0000u);
+      }
+    }
+  }
+};
+
+// The shared exponent of the group whose 16 values a quad of lanes 4k..4k+3 holds 4 each (two xor shuffles: exact).
+// All four lanes must be active.
+__device__ __forceinline__ uint32_t bfp_quad_exponent(const float v[4]) {
+  uint32_t mx = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) mx = max(mx, __float_as_uint(v[j]) & 0x7FFFFFFFu);
+  mx = max(mx, (uint32_t)__shfl_xor((int)mx, 1));
+  mx = max(mx, (uint32_t)__shfl_xor((int)mx, 2));
+  return mx >> 23;
+}
+
+// The lane-contiguous form: a lane holds 4 consecutive values and a quad of lanes one group, so every load and store of
+// a wave covers contiguous bytes instead of striding a group per lane; a lane's mantissas are one dword, and the
+// group's exponent byte is read by all four lanes and stored by the first.
+// Requirements: n_s % 16 == 0 and a thread count that is a multiple of 4, so a quad's lanes are always all in or all
+// out of range, and they are all active at store_wire and roundtrip (bfp_quad_exponent).
+template <int C>
+struct Lanes4 {
+  static_assert(C == kBfpTrunc || C == kBfpRne, "BFP codecs");
+  static constexpr int kVals = 4;
+  __device__ static __forceinline__ void load_wire(const uint8_t* shard, size_t n_s, size_t le, float v[4]) {
+    const uint32_t m = *reinterpret_cast<const uint32_t*>(shard + le);
+    const uint32_t E = shard[n_s + (le >> 4)];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int32_t q = (int32_t)(int8_t)(uint8_t)(m >> (8 * j));
+      v[j] = (C == kBfpTrunc) ? bfp_decode_trunc(q, E) : bfp_decode_rne(q, E);
+    }
+  }
+  __device__ static __forceinline__ void load_dense(const float* p, size_t e, float v[4]) {
+    const float4 a = *reinterpret_cast<const float4*>(p + e);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+  }
+  __device__ static __forceinline__ void load_dense(const bf16_t* p, size_t e, float v[4]) {
+    const uint2 a = *reinterpret_cast<const uint2*>(p + e);
+    v[0] = __uint_as_float(a.x << 16); v[1] = __uint_as_float(a.x & 0xFFFF0000u);
+    v[2] = __uint_as_float(a.y << 16); v[3] = __uint_as_float(a.y & 0xFFFF0000u);
+  }
+  __device__ static __forceinline__ void store_wire(uint8_t* shard, size_t n_s, size_t le, const float v[4]) {
+    const uint32_t E = bfp_quad_exponent(v);
+    uint32_t w = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int32_t q = (C == kBfpTrunc) ? bfp_encode_trunc(__float_as_uint(v[j]), E) : bfp_encode_rne(v[j], E);
+      w |= ((uint32_t)q & 0xFFu) << (8 * j);
+    }
+    *reinterpret_cast<uint32_t*>(shard + le) = w;
+    if ((le & 15) == 0) shard[n_s + (le >> 4)] = (uint8_t)E;
+  }
+  __device__ static __forceinline__ void store_f32(float* p, size_t e, const float v[4]) {
+    *reinterpret_cast<float4*>(p + e) = make_float4(v[0], v[1], v[2], v[3]);
+  }
+  __device__ static __forceinline__ void store_bf16(bf16_t* p, size_t e, const float v[4]) {
+    *reinterpret_cast<uint2*>(p + e) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
+  }
+  __device__ static __forceinline__ void roundtrip(float v[4]) {
+    const uint32_t E = bfp_quad_exponent(v);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = bfp_roundtrip<C>(v[j], E);
   }
 };
 

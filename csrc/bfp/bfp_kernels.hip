@@ -4,7 +4,9 @@
 // 16-B mantissa store, and the group exponents of 16 consecutive lanes leave as one 16-B store, bfp_format.h
 // WireLane16) — except wire_pack_range (the short bias / padding tails at any 16-element offset), where a lane
 // PAIR owns a group. Grids are capped at 2048 blocks and grid-stride over every shard, so each lane runs the same
-// number of iterations per shard and 16-lane segments never split (group counts are multiples of 16).
+// number of iterations per shard and 16-lane segments never split (group counts are multiples of 16). The three
+// reduce kernels (wire_reduce, wire_reduce_to, wire_reduce_sgd) are one body each over a lane layout (bfp_format.h
+// Lanes16 / Lanes4): for the BFP codecs at up to two slots a lane owns 4 values and 4 lanes a group (with_lanes).
 //
 // Reference parity:
 //   wire_pack    = bfp_adapter TX (hw/bfp_adapter.sv:100-154, 279-379)
@@ -12,8 +14,9 @@
 //   wire_reduce  = the ring engine's 8-lane fadd stage + re-encode (hw/all_reduce.sv:1090-1183)
 //   wire_sgd     = weight_update FFMA w' = fma(-lr, g, w) (hw/weight_update.sv:433-452), fused
 //                  into the all-gather epilogue so weights never take an extra HBM round trip.
-//   AdamW        = no counterpart in the reference (its update unit is one FFMA): the same three update kernels
-//                  instantiated with AdamWParams run adamw_update (bfp_format.h) per value, with a second moment plane.
+//   AdamW        = no counterpart in the reference (its update unit is one FFMA): the update kernels (wire_sgd,
+//                  wire_reduce_sgd in both lane layouts) instantiated with AdamWParams run adamw_update
+//                  (bfp_format.h) per value, with a second moment plane.
 //   trust ratio  = AdamW scaled per bucket by ||w|| / ||update|| (LAMB): no element may move before two norms over
 //                  the whole bucket exist, so three launches — wire_lamb_moments (pass 1), lamb_ratio,
 //                  wire_lamb_apply (pass 2) — with a deterministic fp64 reduction in between (no atomics).
@@ -139,88 +142,38 @@ __global__ void __launch_bounds__(kBlock) wire_unpack_kernel(const uint8_t* __re
   }
 }
 
-template <typename TL, int C, bool HAS_LOCAL, bool OUT_WIRE, bool OUT_F32>
+// The three reduce kernels below are written once against a lane layout L (bfp_format.h: Lanes16<C>, a group per lane,
+// or Lanes4<C>, 4 values per lane and 4 lanes a group, BFP codecs): a lane's trip covers L::kVals values at element le.
+
+// acc = the sum of the n_slots slots' values at le, in slot order; slot self_pos comes from the dense local operand.
+template <typename L, typename TL, bool HAS_LOCAL = true>
+__device__ __forceinline__ void sum_slots(const uint8_t* __restrict__ slots, size_t slot_stride, int n_slots,
+                                          int self_pos, const TL* __restrict__ local, size_t n_s, size_t le,
+                                          float (&acc)[L::kVals]) {
+#pragma unroll
+  for (int j = 0; j < L::kVals; ++j) acc[j] = 0.0f;
+  for (int r = 0; r < n_slots; ++r) {
+    float v[L::kVals];
+    if (HAS_LOCAL && r == self_pos) L::load_dense(local, le, v);
+    else L::load_wire(slots + (size_t)r * slot_stride, n_s, le, v);
+#pragma unroll
+    for (int j = 0; j < L::kVals; ++j) acc[j] += v[j];
+  }
+}
+
+template <typename L, typename TL, bool HAS_LOCAL, bool OUT_WIRE, bool OUT_F32>
 __global__ void __launch_bounds__(kBlock)
     wire_reduce_kernel(const uint8_t* __restrict__ slots, size_t slot_stride, int n_slots, int self_pos,
                        const TL* __restrict__ local, uint8_t* __restrict__ out_wire, float* __restrict__ out_f32,
                        size_t n_s) {
-  const size_t tasks = n_s >> 4;
+  const size_t tasks = n_s / L::kVals;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
-    const size_t le = t << 4;
-    float acc[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0.0f;
-    for (int r = 0; r < n_slots; ++r) {
-      float v[16];
-      if (HAS_LOCAL && r == self_pos) {
-        DenseLane16<TL>::load16(local, le, v);
-      } else {
-        WireLane16<C>::load16(slots + (size_t)r * slot_stride, n_s, le, v);
-      }
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc[j] += v[j];
-    }
-    if (OUT_F32) DenseLane16<float>::store16(out_f32, le, acc);
-    if (OUT_WIRE) WireLane16<C>::store16(out_wire, n_s, le, acc);
-  }
-}
-
-// wire_reduce_kernel for the BFP codecs, lane-contiguous (as wire_reduce_to4_kernel): 4 values per lane, the group
-// exponent from quad xor shuffles; bit-identical (FAN_WIRE_REDUCE4).
-template <typename TL, int C, bool HAS_LOCAL, bool OUT_WIRE, bool OUT_F32>
-__global__ void __launch_bounds__(kBlock)
-    wire_reduce4_kernel(const uint8_t* __restrict__ slots, size_t slot_stride, int n_slots, int self_pos,
-                        const TL* __restrict__ local, uint8_t* __restrict__ out_wire, float* __restrict__ out_f32,
-                        size_t n_s) {
-  static_assert(C == kBfpTrunc || C == kBfpRne, "BFP codecs");
-  const size_t tasks = n_s >> 2;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
-    const size_t le = t << 2;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int r = 0; r < n_slots; ++r) {
-      float v[4];
-      if (HAS_LOCAL && r == self_pos) {
-        if constexpr (sizeof(TL) == 4) {
-          const float4 a = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(local) + le);
-          v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-        } else {
-          const uint2 a = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(local) + le);
-          v[0] = __uint_as_float(a.x << 16); v[1] = __uint_as_float(a.x & 0xFFFF0000u);
-          v[2] = __uint_as_float(a.y << 16); v[3] = __uint_as_float(a.y & 0xFFFF0000u);
-        }
-      } else {
-        const uint8_t* sh = slots + (size_t)r * slot_stride;
-        const uint32_t m = *reinterpret_cast<const uint32_t*>(sh + le);
-        const uint32_t E = sh[n_s + (le >> 4)];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int32_t q = (int32_t)(int8_t)(uint8_t)(m >> (8 * j));
-          v[j] = (C == kBfpTrunc) ? bfp_decode_trunc(q, E) : bfp_decode_rne(q, E);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] += v[j];
-    }
-    if (OUT_F32) *reinterpret_cast<float4*>(out_f32 + le) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    if (OUT_WIRE) {
-      uint32_t mx = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) mx = max(mx, __float_as_uint(acc[j]) & 0x7FFFFFFFu);
-      mx = max(mx, (uint32_t)__shfl_xor((int)mx, 1));
-      mx = max(mx, (uint32_t)__shfl_xor((int)mx, 2));
-      const uint32_t E = mx >> 23;
-      uint32_t w = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int32_t q =
-            (C == kBfpTrunc) ? bfp_encode_trunc(__float_as_uint(acc[j]), E) : bfp_encode_rne(acc[j], E);
-        w |= ((uint32_t)q & 0xFFu) << (8 * j);
-      }
-      *reinterpret_cast<uint32_t*>(out_wire + le) = w;
-      if ((le & 15) == 0) out_wire[n_s + (le >> 4)] = (uint8_t)E;
-    }
+    const size_t le = t * L::kVals;
+    float acc[L::kVals];
+    sum_slots<L, TL, HAS_LOCAL>(slots, slot_stride, n_slots, self_pos, local, n_s, le, acc);
+    if (OUT_F32) L::store_f32(out_f32, le, acc);
+    if (OUT_WIRE) L::store_wire(out_wire, n_s, le, acc);
   }
 }
 
@@ -244,258 +197,60 @@ __global__ void __launch_bounds__(kBlock) wire_pack_to_kernel(const TIN* __restr
   p2p_release(rel);
 }
 
-template <typename TL, int C>
+template <typename L, typename TL>
 __global__ void __launch_bounds__(kBlock)
     wire_reduce_to_kernel(const uint8_t* __restrict__ slots, size_t slot_stride, int n_slots, int self_pos,
                           const TL* __restrict__ local, WirePtrs dst, int n_dst, size_t n_s, int rel) {
-  const size_t tasks = n_s >> 4;
+  const size_t tasks = n_s / L::kVals;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
-    const size_t le = t << 4;
-    float acc[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0.0f;
-    for (int r = 0; r < n_slots; ++r) {
-      float v[16];
-      if (r == self_pos) DenseLane16<TL>::load16(local, le, v);
-      else WireLane16<C>::load16(slots + (size_t)r * slot_stride, n_s, le, v);
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc[j] += v[j];
-    }
-    for (int i = 0; i < n_dst; ++i)  // wave-uniform condition: every lane of a 16-lane segment stores
-      if (dst.p[i] != nullptr) WireLane16<C>::store16(dst.p[i], n_s, le, acc);
+    const size_t le = t * L::kVals;
+    float acc[L::kVals];
+    sum_slots<L>(slots, slot_stride, n_slots, self_pos, local, n_s, le, acc);
+    for (int i = 0; i < n_dst; ++i)  // wave-uniform condition: every lane of a group's segment stores
+      if (dst.p[i] != nullptr) L::store_wire(dst.p[i], n_s, le, acc);
   }
   p2p_release(rel);
 }
 
-// wire_reduce_to_kernel for the BFP codecs, lane-contiguous (as wire_reduce_sgd4_kernel below): 4 values per lane, 4
-// lanes a group, the group exponent from quad xor shuffles; each destination gets the lane's 4 mantissa bytes as one
-// dword and the group's exponent byte from its first lane. The same sums in slot order and the same encoding:
-// bit-identical (FAN_WIRE_REDUCE4).
-template <typename TL, int C>
-__global__ void __launch_bounds__(kBlock)
-    wire_reduce_to4_kernel(const uint8_t* __restrict__ slots, size_t slot_stride, int n_slots, int self_pos,
-                           const TL* __restrict__ local, WirePtrs dst, int n_dst, size_t n_s, int rel) {
-  static_assert(C == kBfpTrunc || C == kBfpRne, "BFP codecs");
-  const size_t tasks = n_s >> 2;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
-    const size_t le = t << 2;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int r = 0; r < n_slots; ++r) {
-      float v[4];
-      if (r == self_pos) {
-        if constexpr (sizeof(TL) == 4) {
-          const float4 a = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(local) + le);
-          v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-        } else {
-          const uint2 a = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(local) + le);
-          v[0] = __uint_as_float(a.x << 16); v[1] = __uint_as_float(a.x & 0xFFFF0000u);
-          v[2] = __uint_as_float(a.y << 16); v[3] = __uint_as_float(a.y & 0xFFFF0000u);
-        }
-      } else {
-        const uint8_t* sh = slots + (size_t)r * slot_stride;
-        const uint32_t m = *reinterpret_cast<const uint32_t*>(sh + le);
-        const uint32_t E = sh[n_s + (le >> 4)];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int32_t q = (int32_t)(int8_t)(uint8_t)(m >> (8 * j));
-          v[j] = (C == kBfpTrunc) ? bfp_decode_trunc(q, E) : bfp_decode_rne(q, E);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] += v[j];
-    }
-    uint32_t mx = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) mx = max(mx, __float_as_uint(acc[j]) & 0x7FFFFFFFu);
-    mx = max(mx, (uint32_t)__shfl_xor((int)mx, 1));
-    mx = max(mx, (uint32_t)__shfl_xor((int)mx, 2));
-    const uint32_t E = mx >> 23;
-    uint32_t w = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int32_t q = (C == kBfpTrunc) ? bfp_encode_trunc(__float_as_uint(acc[j]), E) : bfp_encode_rne(acc[j], E);
-      w |= ((uint32_t)q & 0xFFu) << (8 * j);
-    }
-    for (int i = 0; i < n_dst; ++i) {  // wave-uniform condition
-      uint8_t* d = dst.p[i];
-      if (d == nullptr) continue;
-      *reinterpret_cast<uint32_t*>(d + le) = w;
-      if ((le & 15) == 0) d[n_s + (le >> 4)] = (uint8_t)E;
-    }
-  }
-  p2p_release(rel);
-}
-
-// The value a rank decodes after the owner re-encodes `v` (one 16-value group) with codec C.
-template <int C>
-__device__ __forceinline__ void codec_roundtrip16(float v[16]) {
-  if constexpr (C == kBfpTrunc || C == kBfpRne) {
-    uint32_t mx = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) mx = max(mx, __float_as_uint(v[j]) & 0x7FFFFFFFu);
-    const uint32_t E = mx >> 23;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int32_t q = (C == kBfpTrunc) ? bfp_encode_trunc(__float_as_uint(v[j]), E) : bfp_encode_rne(v[j], E);
-      const int32_t q8 = (int32_t)(int8_t)(uint8_t)((uint32_t)q & 0xFFu);  // the stored byte, as the decoder reads it
-      v[j] = (C == kBfpTrunc) ? bfp_decode_trunc(q8, E) : bfp_decode_rne(q8, E);
-    }
-  } else if constexpr (C == kRawBf16) {
-#pragma unroll
-    for (int j = 0; j < 16; j += 2) {
-      const uint32_t u = pack_bf16x2(v[j], v[j + 1]);
-      v[j] = __uint_as_float(u << 16);
-      v[j + 1] = __uint_as_float(u & 0xFFFF0000u);
-    }
-  }
-}
-
-// P: SgdParams, or AdamWParams (HAS_MOM: mom is the first moment, p.var the second; adamw_update per value).
-template <typename TL, int C, bool HAS_MOM, typename P = SgdParams>
+// The merged reduce-and-update of the owner's shard: the slots' sum through the codec's round trip, then the update
+// per value (the same operations as wire_reduce's re-encode + wire_sgd_kernel, so the same bits), the new weights in
+// bf16 to every destination. P: SgdParams, or AdamWParams (HAS_MOM: mom is the first moment, p.var the second).
+template <typename L, typename TL, bool HAS_MOM, typename P = SgdParams>
 __global__ void __launch_bounds__(kBlock)
     wire_reduce_sgd_kernel(const uint8_t* __restrict__ slots, size_t slot_stride, int n_slots, int self_pos,
                            const TL* __restrict__ local, float* __restrict__ master, float* __restrict__ mom,
                            P p, size_t n_valid, WirePtrs dst, int n_dst, size_t n_s, int rel) {
   constexpr bool kAdam = std::is_same<P, AdamWParams>::value;
   static_assert(!kAdam || HAS_MOM, "AdamW needs both moment planes");
-  const size_t tasks = n_s >> 4;
+  const size_t tasks = n_s / L::kVals;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
-    const size_t le = t << 4;
-    float acc[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0.0f;
-    for (int r = 0; r < n_slots; ++r) {
-      float v[16];
-      if (r == self_pos) DenseLane16<TL>::load16(local, le, v);
-      else WireLane16<C>::load16(slots + (size_t)r * slot_stride, n_s, le, v);
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc[j] += v[j];
-    }
-    codec_roundtrip16<C>(acc);
-    float w[16], m[16];
-    DenseLane16<float>::load16(master, le, w);
-    if (HAS_MOM) DenseLane16<float>::load16(mom, le, m);
+    const size_t le = t * L::kVals;
+    float acc[L::kVals];
+    sum_slots<L>(slots, slot_stride, n_slots, self_pos, local, n_s, le, acc);
+    L::roundtrip(acc);
+    float w[L::kVals], m[L::kVals];
+    L::load_dense(master, le, w);
+    if (HAS_MOM) L::load_dense(mom, le, m);
     if constexpr (kAdam) {
-      float v2[16];
-      DenseLane16<float>::load16(p.var, le, v2);
+      float v2[L::kVals];
+      L::load_dense(p.var, le, v2);
 #pragma unroll
-      for (int j = 0; j < 16; ++j)
+      for (int j = 0; j < L::kVals; ++j)
         if (le + j < n_valid) adamw_update(p, acc[j], w[j], m[j], v2[j]);
-      if (le < n_valid) DenseLane16<float>::store16(p.var, le, v2);
+      if (le < n_valid) L::store_f32(p.var, le, v2);
     } else {
 #pragma unroll
-      for (int j = 0; j < 16; ++j) {  // wire_sgd_kernel's operations, in its order
-        if (le + j >= n_valid) continue;
-        float gj = acc[j] * p.grad_scale;
-        if (p.weight_decay != 0.0f) gj = fmaf(p.weight_decay, w[j], gj);
-        if (HAS_MOM) {
-          m[j] = fmaf(p.momentum, m[j], gj);
-          gj = p.nesterov ? fmaf(p.momentum, m[j], gj) : m[j];
-        }
-        w[j] = fmaf(-p.lr, gj, w[j]);
-      }
+      for (int j = 0; j < L::kVals; ++j)
+        if (le + j < n_valid) sgd_update(p, acc[j], w[j], m[j], HAS_MOM);
     }
     if (le < n_valid) {
-      DenseLane16<float>::store16(master, le, w);
-      if (HAS_MOM) DenseLane16<float>::store16(mom, le, m);
+      L::store_f32(master, le, w);
+      if (HAS_MOM) L::store_f32(mom, le, m);
     }
     for (int i = 0; i < n_dst; ++i)
-      if (dst.p[i] != nullptr) DenseLane16<bf16_t>::store16(reinterpret_cast<bf16_t*>(dst.p[i]), le, w);
-  }
-  if (rel >= 0) p2p_release(rel);
-}
-
-// wire_reduce_sgd_kernel for the BFP codecs, lane-contiguous: 4 consecutive values per lane, 4 lanes a 16-value group
-// (the group's exponent for the codec round trip from quad xor shuffles: exact), so every load and store of a wave
-// covers contiguous bytes instead of striding a group per lane — the same sums in slot order, the same round trip and
-// SGD per value: bit-identical (FAN_WIRE_REDUCE4, default on). n_s is a multiple of 16 and the grid's thread count a
-// multiple of 4, so a quad's lanes are always all in or all out of range.
-template <typename TL, int C, bool HAS_MOM, typename P = SgdParams>
-__global__ void __launch_bounds__(kBlock)
-    wire_reduce_sgd4_kernel(const uint8_t* __restrict__ slots, size_t slot_stride, int n_slots, int self_pos,
-                            const TL* __restrict__ local, float* __restrict__ master, float* __restrict__ mom,
-                            P p, size_t n_valid, WirePtrs dst, int n_dst, size_t n_s, int rel) {
-  static_assert(C == kBfpTrunc || C == kBfpRne, "BFP codecs");
-  constexpr bool kAdam = std::is_same<P, AdamWParams>::value;
-  static_assert(!kAdam || HAS_MOM, "AdamW needs both moment planes");
-  const size_t tasks = n_s >> 2;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
-    const size_t le = t << 2;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int r = 0; r < n_slots; ++r) {
-      float v[4];
-      if (r == self_pos) {
-        if constexpr (sizeof(TL) == 4) {
-          const float4 a = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(local) + le);
-          v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-        } else {
-          const uint2 a = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(local) + le);
-          v[0] = __uint_as_float(a.x << 16); v[1] = __uint_as_float(a.x & 0xFFFF0000u);
-          v[2] = __uint_as_float(a.y << 16); v[3] = __uint_as_float(a.y & 0xFFFF0000u);
-        }
-      } else {
-        const uint8_t* sh = slots + (size_t)r * slot_stride;
-        const uint32_t m = *reinterpret_cast<const uint32_t*>(sh + le);
-        const uint32_t E = sh[n_s + (le >> 4)];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int32_t q = (int32_t)(int8_t)(uint8_t)(m >> (8 * j));
-          v[j] = (C == kBfpTrunc) ? bfp_decode_trunc(q, E) : bfp_decode_rne(q, E);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] += v[j];
-    }
-    // codec_roundtrip16 on the quad's group
-    uint32_t mx = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) mx = max(mx, __float_as_uint(acc[j]) & 0x7FFFFFFFu);
-    mx = max(mx, (uint32_t)__shfl_xor((int)mx, 1));
-    mx = max(mx, (uint32_t)__shfl_xor((int)mx, 2));
-    const uint32_t E = mx >> 23;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int32_t q = (C == kBfpTrunc) ? bfp_encode_trunc(__float_as_uint(acc[j]), E) : bfp_encode_rne(acc[j], E);
-      const int32_t q8 = (int32_t)(int8_t)(uint8_t)((uint32_t)q & 0xFFu);
-      acc[j] = (C == kBfpTrunc) ? bfp_decode_trunc(q8, E) : bfp_decode_rne(q8, E);
-    }
-    float4 wv = *reinterpret_cast<const float4*>(master + le);
-    float w[4] = {wv.x, wv.y, wv.z, wv.w}, m[4] = {0.f, 0.f, 0.f, 0.f};
-    if (HAS_MOM) {
-      const float4 mv = *reinterpret_cast<const float4*>(mom + le);
-      m[0] = mv.x; m[1] = mv.y; m[2] = mv.z; m[3] = mv.w;
-    }
-    if constexpr (kAdam) {
-      const float4 vv = *reinterpret_cast<const float4*>(p.var + le);
-      float v2[4] = {vv.x, vv.y, vv.z, vv.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (le + j < n_valid) adamw_update(p, acc[j], w[j], m[j], v2[j]);
-      if (le < n_valid) *reinterpret_cast<float4*>(p.var + le) = make_float4(v2[0], v2[1], v2[2], v2[3]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {  // wire_sgd_kernel's operations, in its order
-        if (le + j >= n_valid) continue;
-        float gj = acc[j] * p.grad_scale;
-        if (p.weight_decay != 0.0f) gj = fmaf(p.weight_decay, w[j], gj);
-        if (HAS_MOM) {
-          m[j] = fmaf(p.momentum, m[j], gj);
-          gj = p.nesterov ? fmaf(p.momentum, m[j], gj) : m[j];
-        }
-        w[j] = fmaf(-p.lr, gj, w[j]);
-      }
-    }
-    if (le < n_valid) {
-      *reinterpret_cast<float4*>(master + le) = make_float4(w[0], w[1], w[2], w[3]);
-      if (HAS_MOM) *reinterpret_cast<float4*>(mom + le) = make_float4(m[0], m[1], m[2], m[3]);
-    }
-    const uint2 lp = make_uint2(pack_bf16x2(w[0], w[1]), pack_bf16x2(w[2], w[3]));
-    for (int i = 0; i < n_dst; ++i)
-      if (dst.p[i] != nullptr) *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(dst.p[i]) + le) = lp;
+      if (dst.p[i] != nullptr) L::store_bf16(reinterpret_cast<bf16_t*>(dst.p[i]), le, w);
   }
   if (rel >= 0) p2p_release(rel);
 }
@@ -554,15 +309,7 @@ __global__ void __launch_bounds__(kBlock)
         }
       } else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float gj = g[j] * p.grad_scale;
-          if (p.weight_decay != 0.0f) gj = fmaf(p.weight_decay, w[j], gj);
-          if (HAS_MOM) {
-            m[j] = fmaf(p.momentum, m[j], gj);
-            gj = p.nesterov ? fmaf(p.momentum, m[j], gj) : m[j];
-          }
-          w[j] = fmaf(-p.lr, gj, w[j]);
-        }
+        for (int j = 0; j < 8; ++j) sgd_update(p, g[j], w[j], m[j], HAS_MOM);
       }
       if (full) {
         DenseLane<float>::store8(master, e, w);
@@ -775,38 +522,40 @@ void launch_wire_unpack(int codec, int out_dtype, const void* in, void* out, siz
   FAN_HIP_CHECK(hipGetLastError());
 }
 
+// The lane layout and the grid of a reduce kernel: launch(L{}, grid) with L = Lanes4<C> (4 values per lane) for a BFP
+// codec when wire_reduce4_for(n_slots), else Lanes16<C> (a group per lane).
+template <int C, typename F>
+static void with_lanes(int n_slots, size_t n_s, int cap, F&& launch) {
+  if constexpr (C == kBfpTrunc || C == kBfpRne) {
+    if (wire_reduce4_for(n_slots)) return launch(Lanes4<C>{}, stream_grid(n_s / 4, kBlock, cap));
+  }
+  launch(Lanes16<C>{}, stream_grid(n_s / 16, kBlock, cap));
+}
+
 template <typename TL, int C>
 static void reduce_dispatch(const void* slots, size_t slot_stride, int n_slots, int self_pos, const void* local,
                             void* out_wire, float* out_f32, size_t n_s, hipStream_t stream) {
-  const bool q4 = (C == kBfpTrunc || C == kBfpRne) && wire_reduce4_for(n_slots);
-  const int grid = stream_grid(q4 ? n_s / 4 : n_s / 16, kBlock, wire_max_blocks());
   const uint8_t* sl = (const uint8_t*)slots;
   const TL* lo = (const TL*)local;
   uint8_t* ow = (uint8_t*)out_wire;
-#define FAN_RED(HL, OW, OF)                                                                                    \
-  do {                                                                                                         \
-    if constexpr (C == kBfpTrunc || C == kBfpRne) {                                                            \
-      if (q4) {                                                                                                \
-        hipLaunchKernelGGL((wire_reduce4_kernel<TL, C, HL, OW, OF>), grid, kBlock, 0, stream, sl, slot_stride, \
-                           n_slots, self_pos, lo, ow, out_f32, n_s);                                           \
-        break;                                                                                                 \
-      }                                                                                                        \
-    }                                                                                                          \
-    hipLaunchKernelGGL((wire_reduce_kernel<TL, C, HL, OW, OF>), grid, kBlock, 0, stream, sl, slot_stride,      \
-                       n_slots, self_pos, lo, ow, out_f32, n_s);                                               \
-  } while (0)
   const bool hl = local != nullptr, w = out_wire != nullptr, f = out_f32 != nullptr;
   FAN_CHECK(w || f, "wire_reduce needs an output");
-  if (hl) {
-    if (w && f) FAN_RED(true, true, true);
-    else if (w) FAN_RED(true, true, false);
-    else FAN_RED(true, false, true);
-  } else {
-    if (w && f) FAN_RED(false, true, true);
-    else if (w) FAN_RED(false, true, false);
-    else FAN_RED(false, false, true);
-  }
+  with_lanes<C>(n_slots, n_s, wire_max_blocks(), [&](auto lanes, int grid) {
+    using L = decltype(lanes);
+#define FAN_RED(HL, OW, OF)                                                                                  \
+  hipLaunchKernelGGL((wire_reduce_kernel<L, TL, HL, OW, OF>), grid, kBlock, 0, stream, sl, slot_stride, n_slots, \
+                     self_pos, lo, ow, out_f32, n_s)
+    if (hl) {
+      if (w && f) FAN_RED(true, true, true);
+      else if (w) FAN_RED(true, true, false);
+      else FAN_RED(true, false, true);
+    } else {
+      if (w && f) FAN_RED(false, true, true);
+      else if (w) FAN_RED(false, true, false);
+      else FAN_RED(false, false, true);
+    }
 #undef FAN_RED
+  });
 }
 
 void launch_wire_reduce(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots,
@@ -950,46 +699,22 @@ void launch_wire_pack_to(int codec, int in_dtype, const void* in, const WirePtrs
   FAN_HIP_CHECK(hipGetLastError());
 }
 
-// the lane-contiguous reduce-to-peers kernel for the BFP codecs (false: not launched — another codec, or the flag off)
-template <int C>
-static bool reduce_to4_dispatch(int grid4, int local_dtype, const void* slots, size_t slot_stride, int n_slots,
-                                int self_pos, const void* local, const WirePtrs& dst, int n_dst, size_t n_s,
-                                hipStream_t stream) {
-  if constexpr (C == kBfpTrunc || C == kBfpRne) {
-    if (grid4 <= 0) return false;
-    if (local_dtype == kF32)
-      hipLaunchKernelGGL((wire_reduce_to4_kernel<float, C>), grid4, kBlock, 0, stream, (const uint8_t*)slots,
-                         slot_stride, n_slots, self_pos, (const float*)local, dst, n_dst, n_s, p2p_release_mode());
-    else
-      hipLaunchKernelGGL((wire_reduce_to4_kernel<bf16_t, C>), grid4, kBlock, 0, stream, (const uint8_t*)slots,
-                         slot_stride, n_slots, self_pos, (const bf16_t*)local, dst, n_dst, n_s, p2p_release_mode());
-    return true;
-  } else {
-    return false;
-  }
-}
-
 void launch_wire_reduce_to(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
                            const void* local, const WirePtrs& dst, int n_dst, size_t n_s, hipStream_t stream) {
   check_ns(n_s);
   FAN_CHECK(n_dst <= kMaxPeers && local != nullptr, "reduce_to: local operand and at most 16 destinations");
   if (n_s == 0) return;
-  const int grid = stream_grid(n_s / 16, kBlock, std::min(wire_max_blocks(), p2p_grid_cap()));
-  const int grid4 =
-      wire_reduce4_for(n_slots) ? stream_grid(n_s / 4, kBlock, std::min(wire_max_blocks(), p2p_grid_cap())) : 0;
-  FAN_CODEC_SWITCH(codec, {
-    if (reduce_to4_dispatch<C>(grid4, local_dtype, slots, slot_stride, n_slots, self_pos, local, dst, n_dst, n_s,
-                               stream)) {
-      FAN_HIP_CHECK(hipGetLastError());
-      return;
-    }
+  const uint8_t* sl = (const uint8_t*)slots;
+  const int cap = std::min(wire_max_blocks(), p2p_grid_cap());
+  FAN_CODEC_SWITCH(codec, with_lanes<C>(n_slots, n_s, cap, [&](auto lanes, int grid) {
+    using L = decltype(lanes);
     if (local_dtype == kF32)
-      hipLaunchKernelGGL((wire_reduce_to_kernel<float, C>), grid, kBlock, 0, stream, (const uint8_t*)slots,
-                         slot_stride, n_slots, self_pos, (const float*)local, dst, n_dst, n_s, p2p_release_mode());
+      hipLaunchKernelGGL((wire_reduce_to_kernel<L, float>), grid, kBlock, 0, stream, sl, slot_stride, n_slots, self_pos,
+                         (const float*)local, dst, n_dst, n_s, p2p_release_mode());
     else
-      hipLaunchKernelGGL((wire_reduce_to_kernel<bf16_t, C>), grid, kBlock, 0, stream, (const uint8_t*)slots,
-                         slot_stride, n_slots, self_pos, (const bf16_t*)local, dst, n_dst, n_s, p2p_release_mode());
-  });
+      hipLaunchKernelGGL((wire_reduce_to_kernel<L, bf16_t>), grid, kBlock, 0, stream, sl, slot_stride, n_slots,
+                         self_pos, (const bf16_t*)local, dst, n_dst, n_s, p2p_release_mode());
+  }));
   FAN_HIP_CHECK(hipGetLastError());
 }
 
@@ -1003,52 +728,32 @@ static std::atomic<int>& reduce4_flag() {
 void set_wire_reduce4(int on) { reduce4_flag().store(on); }
 int wire_reduce4() { return reduce4_flag().load(std::memory_order_relaxed); }
 
-template <int C, typename P>
-static void reduce_sgd_dispatch(int local_dtype, int grid, const void* slots, size_t slot_stride, int n_slots,
-                                int self_pos, const void* local, float* master, float* mom, P p,
-                                size_t n_valid, const WirePtrs& dst, int n_dst, size_t n_s, int rel,
-                                hipStream_t stream, int grid4) {
-  constexpr bool kAdam = std::is_same<P, AdamWParams>::value;  // AdamW: both moment planes, always
-  const uint8_t* sl = (const uint8_t*)slots;
-#define FAN_RSGD(KERNEL, TL, MOM, G)                                                                                 \
-  hipLaunchKernelGGL((KERNEL<TL, C, MOM, P>), G, kBlock, 0, stream, sl, slot_stride, n_slots, self_pos,              \
-                     (const TL*)local, master, mom, p, n_valid, dst, n_dst, n_s, rel)
-  if constexpr (C == kBfpTrunc || C == kBfpRne) {
-    if (grid4 > 0) {
-      if (local_dtype == kF32) {
-        if (kAdam || mom) FAN_RSGD(wire_reduce_sgd4_kernel, float, true, grid4);
-        else if constexpr (!kAdam) FAN_RSGD(wire_reduce_sgd4_kernel, float, false, grid4);
-      } else {
-        if (kAdam || mom) FAN_RSGD(wire_reduce_sgd4_kernel, bf16_t, true, grid4);
-        else if constexpr (!kAdam) FAN_RSGD(wire_reduce_sgd4_kernel, bf16_t, false, grid4);
-      }
-      return;
-    }
-  }
-  if (local_dtype == kF32) {
-    if (kAdam || mom) FAN_RSGD(wire_reduce_sgd_kernel, float, true, grid);
-    else if constexpr (!kAdam) FAN_RSGD(wire_reduce_sgd_kernel, float, false, grid);
-  } else {
-    if (kAdam || mom) FAN_RSGD(wire_reduce_sgd_kernel, bf16_t, true, grid);
-    else if constexpr (!kAdam) FAN_RSGD(wire_reduce_sgd_kernel, bf16_t, false, grid);
-  }
-#undef FAN_RSGD
-}
-
 template <typename P>
 static void launch_reduce_update(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots,
                                  int self_pos, const void* local, float* master, float* mom, P p, size_t n_valid,
                                  const WirePtrs& dst, int n_dst, size_t n_s, bool peers, hipStream_t stream) {
+  constexpr bool kAdam = std::is_same<P, AdamWParams>::value;  // AdamW: both moment planes, always
   check_ns(n_s);
   FAN_CHECK(n_dst <= kMaxPeers && local != nullptr && master != nullptr,
             "reduce_sgd: local operand, master shard and at most 16 destinations");
   if (n_s == 0) return;
+  const uint8_t* sl = (const uint8_t*)slots;
   const int cap = peers ? std::min(wire_max_blocks(), p2p_grid_cap()) : wire_max_blocks();
-  const int grid = stream_grid(n_s / 16, kBlock, cap);
-  const int grid4 = wire_reduce4_for(n_slots) ? stream_grid(n_s / 4, kBlock, cap) : 0;
   const int rel = peers ? p2p_release_mode() : -1;
-  FAN_CODEC_SWITCH(codec, (reduce_sgd_dispatch<C, P>(local_dtype, grid, slots, slot_stride, n_slots, self_pos, local,
-                                                     master, mom, p, n_valid, dst, n_dst, n_s, rel, stream, grid4)));
+#define FAN_RSGD(TL, MOM)                                                                                         \
+  hipLaunchKernelGGL((wire_reduce_sgd_kernel<L, TL, MOM, P>), grid, kBlock, 0, stream, sl, slot_stride, n_slots, \
+                     self_pos, (const TL*)local, master, mom, p, n_valid, dst, n_dst, n_s, rel)
+  FAN_CODEC_SWITCH(codec, with_lanes<C>(n_slots, n_s, cap, [&](auto lanes, int grid) {
+    using L = decltype(lanes);
+    if (local_dtype == kF32) {
+      if (kAdam || mom) FAN_RSGD(float, true);
+      else if constexpr (!kAdam) FAN_RSGD(float, false);
+    } else {
+      if (kAdam || mom) FAN_RSGD(bf16_t, true);
+      else if constexpr (!kAdam) FAN_RSGD(bf16_t, false);
+    }
+  }));
+#undef FAN_RSGD
   FAN_HIP_CHECK(hipGetLastError());
 }
 

@@ -308,19 +308,6 @@ __device__ __forceinline__ float wire_roundtrip_rne(float x, uint32_t E) {
   return bfp_decode_rne(bfp_encode_rne(x, E), E);  // |q| <= 127: the stored byte decodes to q
 }
 
-// One element of the fused update: the same operations, in the same order, as wire_sgd_kernel (bfp_kernels.hip), so
-// the fused and the unfused single-rank step produce bit-identical weights.
-__device__ __forceinline__ float sgd_apply(float g, float& w, float& m, bool has_mom, const SgdParams& p) {
-  float gj = g * p.grad_scale;
-  if (p.weight_decay != 0.0f) gj = fmaf(p.weight_decay, w, gj);
-  if (has_mom) {
-    m = fmaf(p.momentum, m, gj);
-    gj = p.nesterov ? fmaf(p.momentum, m, gj) : m;
-  }
-  w = fmaf(-p.lr, gj, w);
-  return w;
-}
-
 // Fused update of the 16-value group at flat index f (shared exponent E already computed): 16-B master / mom
 // loads and stores, one 32-B bf16 store.
 // (PRE: the group's master values w[] were loaded ahead by the caller)
@@ -344,7 +331,7 @@ __device__ __forceinline__ void local_update16(const float v[16], uint32_t E, ui
     }
   }
 #pragma unroll
-  for (int u = 0; u < 16; ++u) sgd_apply(wire_roundtrip_rne(v[u], E), w[u], m[u], hm, wo.up);
+  for (int u = 0; u < 16; ++u) sgd_update(wo.up, wire_roundtrip_rne(v[u], E), w[u], m[u], hm);
 #pragma unroll
   for (int u = 0; u < 16; u += 4) {
     *reinterpret_cast<float4*>(wo.um + f + u) = make_float4(w[u], w[u + 1], w[u + 2], w[u + 3]);
@@ -432,7 +419,7 @@ __device__ __forceinline__ void colsum_finish(float (&cs)[NJ], int lane, int col
         if constexpr (EPI == kEpiWireUpd) {  // fused local update of the bias segment, one element per lane
           if (lane < 16) {
             float w = wo.um[f], m = wo.umom ? wo.umom[f] : 0.f;
-            sgd_apply(wire_roundtrip_rne(v, E), w, m, wo.umom != nullptr, wo.up);
+            sgd_update(wo.up, wire_roundtrip_rne(v, E), w, m, wo.umom != nullptr);
             wo.um[f] = w;
             if (wo.umom) wo.umom[f] = m;
             if (wo.ulp) wo.ulp[f] = f32_to_bf16(w);
@@ -1742,7 +1729,7 @@ __device__ __forceinline__ void local_update4(float v[4], uint32_t E, uint32_t f
     m[0] = b.x; m[1] = b.y; m[2] = b.z; m[3] = b.w;
   }
 #pragma unroll
-  for (int u = 0; u < 4; ++u) sgd_apply(wire_roundtrip_rne(v[u], E), w[u], m[u], hm, wo.up);
+  for (int u = 0; u < 4; ++u) sgd_update(wo.up, wire_roundtrip_rne(v[u], E), w[u], m[u], hm);
   *reinterpret_cast<float4*>(wo.um + f) = make_float4(w[0], w[1], w[2], w[3]);
   if (hm) *reinterpret_cast<float4*>(wo.umom + f) = make_float4(m[0], m[1], m[2], m[3]);
   if (wo.ulp) *reinterpret_cast<uint2*>(wo.ulp + f) = make_uint2(pack_bf16x2(w[0], w[1]), pack_bf16x2(w[2], w[3]));
@@ -1775,6 +1762,7 @@ __device__ __forceinline__ void splitk_reduce_wire4_run(const float* __restrict_
       a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
     }
     float v[4] = {a.x, a.y, a.z, a.w};
+    // bfp_quad_exponent (bfp_format.h), written out: through the call this kernel's registers are allocated differently
     uint32_t mx = 0;
 #pragma unroll
     for (int u = 0; u < 4; ++u) mx = max(mx, __float_as_uint(v[u]) & 0x7FFFFFFFu);

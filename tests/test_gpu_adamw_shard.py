@@ -1,6 +1,6 @@
 """Sharded weight update with AdamW (engine ``shard_update``): the owner of each mesh shard fuses its reduce with the
-codec round trip + AdamW of that shard (bfp_kernels.hip wire_reduce_sgd_kernel / wire_reduce_sgd4_kernel with
-AdamWParams) and the ranks all-gather the updated bf16 weights.
+codec round trip + AdamW of that shard (bfp_kernels.hip wire_reduce_sgd_kernel with AdamWParams, in the
+Lanes16 or Lanes4 lane layout) and the ranks all-gather the updated bf16 weights.
 
 As with SGD (test_gpu_shard_update.py) it must train bit-identically to the unsharded schedule: per rank, the weights
 it writes (``lp``) and, once gathered from their owners (``gather_owned``), its master and both moment planes equal the

@@ -132,6 +132,8 @@ def _child(world, algo, rings, mode):
     env = dict(os.environ, GPU_MAX_HW_QUEUES="32")
     if mode.startswith(("block", "thread")):  # the in-kernel release forms (cross-device peers default to "block")
         env["FAN_P2P_RELEASE"] = mode.split("_")[0]
+    if mode == "lanes16":  # the BFP reduce kernels with one 16-value group per lane, also at up to two slots
+        env["FAN_WIRE_REDUCE4"] = "0"
     try:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), str(world), algo, str(rings), mode], env=env,
                            capture_output=True, text=True, timeout=150)
@@ -150,6 +152,14 @@ def test_direct_p2p_schedules_bit_exact(world, algo, rings):
     rec = _child(world, algo, rings, "plain")
     if algo == "ring":
         assert rec["rings"] >= min(rings, 2)  # several arc-disjoint rings at once (N = 4 has 2, not 3)
+
+
+def test_direct_ring_group_per_lane_reduce_bit_exact():
+    """The direct ring reduces 2 slots per hop (the received partial sum + the local operand), which by default runs
+    the reduce-to-peers kernel with 4 values per lane: FAN_WIRE_REDUCE4=0 runs its one-group-per-lane form at 2 slots
+    (the mesh cases above run that form at 3 to 8 slots). The same bits as the simulator."""
+    rec = _child(3, "ring", 2, "lanes16")
+    assert rec["rings"] >= 2
 
 
 @pytest.mark.parametrize("world,algo,rings", [(4, "ring", 3), (4, "mesh", 1)])
