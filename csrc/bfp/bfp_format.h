@@ -487,11 +487,36 @@ void launch_wire_reduce(int codec, int local_dtype, const void* slots, size_t sl
 // wire read in place from a receive arena has its shards one arena slot pair apart.
 void launch_wire_sgd(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
                      float* master, bf16_t* lp, float* mom, SgdParams p, size_t n_valid, hipStream_t stream,
-                     size_t shard_stride = 0);
+                     size_t shard_stride = 0, const float* clip = nullptr);
 // launch_wire_sgd with the AdamW step: `mom` is the first moment, p.var the second, both required.
 void launch_wire_adamw(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
                        float* master, bf16_t* lp, float* mom, AdamWParams p, size_t n_valid, hipStream_t stream,
-                       size_t shard_stride = 0);
+                       size_t shard_stride = 0, const float* clip = nullptr);
+// Global-norm gradient clipping of a clip group (the update requests of one optimizer step), three kinds of launch
+// on one stream. The update launchers above and launch_wire_lamb_moments take `clip`, the group's four f32 device
+// words {coef, f32(total), f32(max_norm), nonfinite ? 1 : 0}: non-null, the kernel uses grad_scale * clip[0] (one f32
+// product, computed once per kernel from a uniform load) in place of grad_scale and changes nothing else, so a
+// coefficient of 1.0f gives the unclipped update's bits; nullptr is the unclipped code path itself (another kernel
+// instantiation that never reads the pointer). SgdParams is not grown: it is part of the GEMM kernels' argument block.
+// 1. launch_wire_sumsq, once per gathered wire region: a read-only pass with launch_wire_sgd's traversal (codecs,
+//    shard_stride, skipped shards, the n_valid tail inside a group; values at or past n_valid enter as 0) that sums
+//    the exact fp64 squares of the decoded values in a fixed order per lane, wave and block; block b stores its sum at
+//    partials[b]. sumsq_partials_for(n_s) blocks — a function of n_s and the grid cap alone. An empty region is refused.
+// 2. launch_clip_coef, once per group: one block sums up to kClipSegments segments of partials in segment order and
+//    index order (a segment of count 0 contributes nothing) into S and writes the four words:
+//    total = sqrt(S) * |grad_scale|, coef = min(1, max_norm / (total + 1e-6)) in fp64, rounded once to f32; S not
+//    finite: coef = NaN and words[3] = 1.
+// 3. the group's update launches with clip = words.
+constexpr int kClipSegments = 8;  // = the engine's request slots: a clip group holds at most that many requests
+struct ClipSegments {
+  const double* p[kClipSegments];
+  int n[kClipSegments];
+};
+int sumsq_partials_for(size_t n_s);
+void launch_wire_sumsq(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
+                       size_t n_valid, double* partials, hipStream_t stream, size_t shard_stride = 0);
+void launch_clip_coef(const ClipSegments& seg, int n_seg, double max_norm, float grad_scale, float* words,
+                      hipStream_t stream);
 // The trust-ratio (LAMB) epilogue: three launches on one stream.
 // Pass 1, launch_wire_lamb_moments: decode the wire as launch_wire_adamw does (codecs, shard_stride, skipped shards,
 // n_valid tail), store the new moments (`mom`, p.var) and leave `master` untouched; over the flat elements below
@@ -502,7 +527,8 @@ void launch_wire_adamw(int codec, const void* wire, size_t n_s, int n_shards, in
 int lamb_partials_for(size_t n_s);
 void launch_wire_lamb_moments(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
                               const float* master, float* mom, LambParams p, size_t n_valid, size_t adapt_end,
-                              double* partials, hipStream_t stream, size_t shard_stride = 0);
+                              double* partials, hipStream_t stream, size_t shard_stride = 0,
+                              const float* clip = nullptr);
 // One block: sums the n_pairs {S_w, S_r} pairs of every pass-1 launch of a request (each lane takes pairs
 // t, t + 256, ... in ascending order, the lanes' sums then combine in a fixed tree, all fp64) and writes the three f32
 // words {lr * phi, lr, phi}, phi = (float)sqrt(S_w / S_r) when both sums are positive and finite, else 1.

@@ -272,13 +272,17 @@ __global__ void __launch_bounds__(kBlock) wire_unpack_strided_kernel(const uint8
   }
 }
 
-template <int C, bool HAS_LP, bool HAS_MOM, typename P = SgdParams>
+// CLIP: the request belongs to a clip group — grad_scale is multiplied by the group's coefficient clip[0] (four f32
+// words clip_coef_kernel wrote earlier on the stream), one f32 product per kernel from a uniform load; nothing else in
+// the update changes, and a coefficient of 1.0f leaves grad_scale's bits. !CLIP: `clip` is not read.
+template <int C, bool HAS_LP, bool HAS_MOM, typename P = SgdParams, bool CLIP = false>
 __global__ void __launch_bounds__(kBlock)
     wire_sgd_kernel(const uint8_t* __restrict__ wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
                     float* __restrict__ master, bf16_t* __restrict__ lp, float* __restrict__ mom, P p,
-                    size_t n_valid, size_t sb) {
+                    size_t n_valid, size_t sb, const float* __restrict__ clip) {
   constexpr bool kAdam = std::is_same<P, AdamWParams>::value;
   static_assert(!kAdam || HAS_MOM, "AdamW needs both moment planes");
+  if constexpr (CLIP) p.grad_scale = p.grad_scale * clip[0];
   // 8 elements per lane here (a read-only wire: the 16-per-lane store layout buys nothing, and the smaller
   // register footprint streams master / lp faster: 33.5 vs 42.5 us on a 16.8 M bucket in the flagship step)
   const size_t tasks = n_s >> 3;
@@ -354,11 +358,13 @@ __device__ __forceinline__ void lamb_block_sum(double& a, double& b) {
 
 // Pass 1: wire_sgd_kernel's traversal (8 values per lane, shards, skipped shards, the n_valid tail); stores the new
 // moments, reads master only. The lane's fp64 sums grow in its own iteration order, which the grid alone decides.
-template <int C>
+template <int C, bool CLIP = false>
 __global__ void __launch_bounds__(kBlock)
     wire_lamb_moments_kernel(const uint8_t* __restrict__ wire, size_t n_s, int n_shards, int skip_shard,
                              int skip_period, const float* __restrict__ master, float* __restrict__ mom, LambParams p,
-                             size_t n_valid, size_t adapt_end, size_t sb, double* __restrict__ partials) {
+                             size_t n_valid, size_t adapt_end, size_t sb, double* __restrict__ partials,
+                             const float* __restrict__ clip) {
+  if constexpr (CLIP) p.grad_scale = p.grad_scale * clip[0];  // (as wire_sgd_kernel)
   const size_t tasks = n_s >> 3;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   double sw = 0.0, sr = 0.0;
@@ -455,6 +461,81 @@ __global__ void __launch_bounds__(kBlock)
         if (HAS_LP) lp[e + j] = f32_to_bf16(w[j]);
       }
     }
+  }
+}
+
+// ---------------------------------------------------------------- global-norm clipping
+// lamb_block_sum for one value: the same fixed order (lanes by shuffles 32 .. 1, then the waves in wave order by
+// thread 0). Every thread of the block must call it; the result is valid in thread 0.
+__device__ __forceinline__ void clip_block_sum(double& a) {
+  __shared__ double red[kBlock / 64];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) a += __shfl_down(a, off);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a = red[0];
+#pragma unroll
+    for (int i = 1; i < kBlock / 64; ++i) a += red[i];
+  }
+}
+
+// The norm pass of a clip group over one gathered wire region: wire_sgd_kernel's traversal (shards, shard stride,
+// skipped shards, the n_valid tail inside a group), read-only. A lane owns a whole 16-value group per trip — the BFP
+// codecs' 17 bytes per 16 values arrive as ONE 16-B mantissa load plus the exponent byte, half the load instructions
+// of the update kernels' 8 values per lane, and there are no dense planes whose register footprint made 8 the better
+// choice there (this kernel holds 16 decoded values and one fp64 sum). g^2 is exact in fp64, the lane's sum grows in
+// its own iteration order (the grid alone decides it), then the block sum: one double per block, no atomics.
+template <int C>
+__global__ void __launch_bounds__(kBlock)
+    wire_sumsq_kernel(const uint8_t* __restrict__ wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
+                      size_t n_valid, size_t sb, double* __restrict__ partials) {
+  const size_t tasks = n_s >> 4;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  double sum = 0.0;
+  for (int s = 0; s < n_shards; ++s) {
+    if (skip_shard >= 0 && (s % skip_period) == skip_shard) continue;
+    const uint8_t* src = wire + (size_t)s * sb;
+    const size_t base = (size_t)s * n_s;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
+      const size_t e = base + (t << 4);
+      if (e >= n_valid) continue;
+      float g[16];
+      WireLane16<C>::load16(src, n_s, t << 4, g);
+      // branch-free per value: a value at or past n_valid enters as 0, and s + 0.0 is s bit for bit
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const double ga = e + j < n_valid ? (double)g[j] : 0.0;
+        sum = fma(ga, ga, sum);
+      }
+    }
+  }
+  clip_block_sum(sum);
+  if (threadIdx.x == 0) partials[blockIdx.x] = sum;
+}
+
+// One block: S = the sum of every segment's partials — each lane takes, segment by segment in the order given,
+// indices t, t + 256, ... in ascending order; the lanes' sums then combine in the fixed tree — and the group's four
+// words {coef, f32(total), f32(max_norm), nonfinite}: total = sqrt(S) * gs_abs, coef = min(1, max_norm / (total +
+// 1e-6)), all fp64, rounded once to f32 (torch.nn.utils.clip_grad_norm_'s formula). A non-finite S (raw codecs only)
+// gives a NaN coefficient, which the updates propagate.
+__global__ void __launch_bounds__(kBlock)
+    clip_coef_kernel(ClipSegments seg, int n_seg, double max_norm, double gs_abs, float* __restrict__ words) {
+  double sum = 0.0;
+  for (int k = 0; k < n_seg; ++k) {
+    const double* __restrict__ p = seg.p[k];
+    const int n = seg.n[k];
+    for (int i = threadIdx.x; i < n; i += kBlock) sum += p[i];
+  }
+  clip_block_sum(sum);
+  if (threadIdx.x == 0) {
+    const bool finite = sum < __builtin_huge_val();  // (false for NaN too; the squares' sum is never negative)
+    const double total = sqrt(sum) * gs_abs;
+    const double coef = finite ? fmin(1.0, max_norm / (total + 1e-6)) : __builtin_nan("");
+    words[0] = (float)coef;
+    words[1] = (float)total;
+    words[2] = (float)max_norm;
+    words[3] = finite ? 0.0f : 1.0f;
   }
 }
 
@@ -574,48 +655,52 @@ void launch_wire_reduce(int codec, int local_dtype, const void* slots, size_t sl
 
 void launch_wire_sgd(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
                      float* master, bf16_t* lp, float* mom, SgdParams p, size_t n_valid, hipStream_t stream,
-                     size_t shard_stride) {
+                     size_t shard_stride, const float* clip) {
   if (skip_period < 1) skip_period = 1 << 30;
   check_ns(n_s);
   if (n_s == 0 || n_shards == 0) return;
   const int grid = stream_grid(n_s / 8, kBlock, wire_max_blocks());
   const uint8_t* w = (const uint8_t*)wire;
+#define FAN_SGD(LP, MOM)                                                                                          \
+  do {                                                                                                            \
+    if (clip)                                                                                                     \
+      hipLaunchKernelGGL((wire_sgd_kernel<C, LP, MOM, SgdParams, true>), grid, kBlock, 0, stream, w, n_s, n_shards, \
+                         skip_shard, skip_period, master, lp, mom, p, n_valid, sb, clip);                         \
+    else                                                                                                          \
+      hipLaunchKernelGGL((wire_sgd_kernel<C, LP, MOM>), grid, kBlock, 0, stream, w, n_s, n_shards, skip_shard,    \
+                         skip_period, master, lp, mom, p, n_valid, sb, clip);                                     \
+  } while (0)
   FAN_CODEC_SWITCH(codec, {
     const size_t sb = shard_stride ? shard_stride : wire_shard_bytes(C, n_s);
-    if (lp && mom)
-      hipLaunchKernelGGL((wire_sgd_kernel<C, true, true>), grid, kBlock, 0, stream, w, n_s, n_shards, skip_shard, skip_period,
-                         master, lp, mom, p, n_valid, sb);
-    else if (lp)
-      hipLaunchKernelGGL((wire_sgd_kernel<C, true, false>), grid, kBlock, 0, stream, w, n_s, n_shards,
-                         skip_shard, skip_period, master, lp, mom, p, n_valid, sb);
-    else if (mom)
-      hipLaunchKernelGGL((wire_sgd_kernel<C, false, true>), grid, kBlock, 0, stream, w, n_s, n_shards,
-                         skip_shard, skip_period, master, lp, mom, p, n_valid, sb);
-    else
-      hipLaunchKernelGGL((wire_sgd_kernel<C, false, false>), grid, kBlock, 0, stream, w, n_s, n_shards,
-                         skip_shard, skip_period, master, lp, mom, p, n_valid, sb);
+    if (lp && mom) FAN_SGD(true, true);
+    else if (lp) FAN_SGD(true, false);
+    else if (mom) FAN_SGD(false, true);
+    else FAN_SGD(false, false);
   });
+#undef FAN_SGD
   FAN_HIP_CHECK(hipGetLastError());
 }
 
 void launch_wire_adamw(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
                        float* master, bf16_t* lp, float* mom, AdamWParams p, size_t n_valid, hipStream_t stream,
-                       size_t shard_stride) {
+                       size_t shard_stride, const float* clip) {
   FAN_CHECK(master != nullptr && mom != nullptr && p.var != nullptr, "wire_adamw: master and both moment planes");
   if (skip_period < 1) skip_period = 1 << 30;
   check_ns(n_s);
   if (n_s == 0 || n_shards == 0) return;
   const int grid = stream_grid(n_s / 8, kBlock, wire_max_blocks());
   const uint8_t* w = (const uint8_t*)wire;
+#define FAN_ADAMW(LP, CLIP)                                                                                      \
+  hipLaunchKernelGGL((wire_sgd_kernel<C, LP, true, AdamWParams, CLIP>), grid, kBlock, 0, stream, w, n_s, n_shards, \
+                     skip_shard, skip_period, master, lp, mom, p, n_valid, sb, clip)
   FAN_CODEC_SWITCH(codec, {
     const size_t sb = shard_stride ? shard_stride : wire_shard_bytes(C, n_s);
-    if (lp)
-      hipLaunchKernelGGL((wire_sgd_kernel<C, true, true, AdamWParams>), grid, kBlock, 0, stream, w, n_s, n_shards,
-                         skip_shard, skip_period, master, lp, mom, p, n_valid, sb);
-    else
-      hipLaunchKernelGGL((wire_sgd_kernel<C, false, true, AdamWParams>), grid, kBlock, 0, stream, w, n_s, n_shards,
-                         skip_shard, skip_period, master, lp, mom, p, n_valid, sb);
+    if (lp && clip) FAN_ADAMW(true, true);
+    else if (lp) FAN_ADAMW(true, false);
+    else if (clip) FAN_ADAMW(false, true);
+    else FAN_ADAMW(false, false);
   });
+#undef FAN_ADAMW
   FAN_HIP_CHECK(hipGetLastError());
 }
 
@@ -623,7 +708,7 @@ int lamb_partials_for(size_t n_s) { return stream_grid(n_s / 8, kBlock, wire_max
 
 void launch_wire_lamb_moments(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
                               const float* master, float* mom, LambParams p, size_t n_valid, size_t adapt_end,
-                              double* partials, hipStream_t stream, size_t shard_stride) {
+                              double* partials, hipStream_t stream, size_t shard_stride, const float* clip) {
   FAN_CHECK(master != nullptr && mom != nullptr && p.var != nullptr && partials != nullptr,
             "wire_lamb_moments: master, both moment planes and the partials buffer");
   if (skip_period < 1) skip_period = 1 << 30;
@@ -635,9 +720,43 @@ void launch_wire_lamb_moments(int codec, const void* wire, size_t n_s, int n_sha
   const uint8_t* w = (const uint8_t*)wire;
   FAN_CODEC_SWITCH(codec, {
     const size_t sb = shard_stride ? shard_stride : wire_shard_bytes(C, n_s);
-    hipLaunchKernelGGL((wire_lamb_moments_kernel<C>), grid, kBlock, 0, stream, w, n_s, n_shards, skip_shard,
-                       skip_period, master, mom, p, n_valid, adapt_end, sb, partials);
+    if (clip)
+      hipLaunchKernelGGL((wire_lamb_moments_kernel<C, true>), grid, kBlock, 0, stream, w, n_s, n_shards, skip_shard,
+                         skip_period, master, mom, p, n_valid, adapt_end, sb, partials, clip);
+    else
+      hipLaunchKernelGGL((wire_lamb_moments_kernel<C>), grid, kBlock, 0, stream, w, n_s, n_shards, skip_shard,
+                         skip_period, master, mom, p, n_valid, adapt_end, sb, partials, clip);
   });
+  FAN_HIP_CHECK(hipGetLastError());
+}
+
+int sumsq_partials_for(size_t n_s) { return stream_grid(n_s / 16, kBlock, wire_max_blocks()); }
+
+void launch_wire_sumsq(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
+                       size_t n_valid, double* partials, hipStream_t stream, size_t shard_stride) {
+  FAN_CHECK(wire != nullptr && partials != nullptr, "wire_sumsq: the wire and the partials buffer");
+  if (skip_period < 1) skip_period = 1 << 30;
+  check_ns(n_s);
+  // (an empty launch would leave its partials unwritten for launch_clip_coef to read)
+  FAN_CHECK(n_s > 0 && n_shards > 0, "wire_sumsq: empty wire");
+  const int grid = sumsq_partials_for(n_s);
+  const uint8_t* w = (const uint8_t*)wire;
+  FAN_CODEC_SWITCH(codec, {
+    const size_t sb = shard_stride ? shard_stride : wire_shard_bytes(C, n_s);
+    hipLaunchKernelGGL((wire_sumsq_kernel<C>), grid, kBlock, 0, stream, w, n_s, n_shards, skip_shard, skip_period,
+                       n_valid, sb, partials);
+  });
+  FAN_HIP_CHECK(hipGetLastError());
+}
+
+void launch_clip_coef(const ClipSegments& seg, int n_seg, double max_norm, float grad_scale, float* words,
+                      hipStream_t stream) {
+  FAN_CHECK(words != nullptr && n_seg >= 0 && n_seg <= kClipSegments, "clip_coef: the four output words and at most "
+                                                                      "8 partial segments");
+  FAN_CHECK(max_norm > 0.0 && max_norm < __builtin_huge_val(), "clip_coef: max_norm must be finite and positive");
+  for (int k = 0; k < n_seg; ++k)
+    FAN_CHECK(seg.n[k] >= 0 && (seg.n[k] == 0 || seg.p[k] != nullptr), "clip_coef: a segment without its partials");
+  hipLaunchKernelGGL(clip_coef_kernel, 1, kBlock, 0, stream, seg, n_seg, max_norm, fabs((double)grad_scale), words);
   FAN_HIP_CHECK(hipGetLastError());
 }
 

@@ -112,10 +112,19 @@ void wire_reduce(const at::Tensor& slots, int64_t n_slots, int64_t self_pos, con
                           (size_t)shard_elems, fan_stream());
 }
 
+// the four f32 device words of a clip group (bfp_format.h launch_clip_coef), or nullptr
+const float* clip_words_ptr(const c10::optional<at::Tensor>& clip) {
+  if (!clip) return nullptr;
+  FAN_T_CUDA_CONTIG((*clip));
+  TORCH_CHECK(clip->scalar_type() == at::kFloat && clip->numel() >= 4, "clip: f32[4]");
+  return clip->data_ptr<float>();
+}
+
 void wire_sgd(const at::Tensor& wire, int64_t shard_elems, int64_t n_shards, int64_t skip_shard, int64_t skip_period,
               at::Tensor& master,
               const c10::optional<at::Tensor>& lp, const c10::optional<at::Tensor>& mom, double lr, double grad_scale,
-              double weight_decay, double momentum, bool nesterov, int64_t n_valid, int64_t codec) {
+              double weight_decay, double momentum, bool nesterov, int64_t n_valid, int64_t codec,
+              const c10::optional<at::Tensor>& clip) {
   FAN_T_CUDA_CONTIG(wire);
   FAN_T_CUDA_CONTIG(master);
   TORCH_CHECK(master.scalar_type() == at::kFloat, "master weights must be float32");
@@ -136,13 +145,13 @@ void wire_sgd(const at::Tensor& wire, int64_t shard_elems, int64_t n_shards, int
   }
   fan::SgdParams p{(float)lr, (float)grad_scale, (float)weight_decay, (float)momentum, nesterov ? 1 : 0};
   fan::launch_wire_sgd((int)codec, wire.data_ptr(), (size_t)shard_elems, (int)n_shards, (int)skip_shard, (int)skip_period,
-                       master.data_ptr<float>(), lpp, mp, p, (size_t)n_valid, fan_stream());
+                       master.data_ptr<float>(), lpp, mp, p, (size_t)n_valid, fan_stream(), 0, clip_words_ptr(clip));
 }
 
 void wire_adamw(const at::Tensor& wire, int64_t shard_elems, int64_t n_shards, int64_t skip_shard, int64_t skip_period,
                 at::Tensor& master, const c10::optional<at::Tensor>& lp, at::Tensor& mom, at::Tensor& var,
                 const std::vector<double>& scalars, double grad_scale, double weight_decay, int64_t n_valid,
-                int64_t codec, int64_t shard_stride) {
+                int64_t codec, int64_t shard_stride, const c10::optional<at::Tensor>& clip) {
   FAN_T_CUDA_CONTIG(wire);
   FAN_T_CUDA_CONTIG(master);
   FAN_T_CUDA_CONTIG(mom);
@@ -163,7 +172,7 @@ void wire_adamw(const at::Tensor& wire, int64_t shard_elems, int64_t n_shards, i
   const fan::AdamWParams p = fan_adamw_params(scalars, grad_scale, weight_decay, var, n_valid);
   fan::launch_wire_adamw((int)codec, wire.data_ptr(), (size_t)shard_elems, (int)n_shards, (int)skip_shard,
                          (int)skip_period, master.data_ptr<float>(), lpp, mom.data_ptr<float>(), p, (size_t)n_valid,
-                         fan_stream(), (size_t)shard_stride);
+                         fan_stream(), (size_t)shard_stride, clip_words_ptr(clip));
 }
 
 // the planes of the trust-ratio passes: f32, whole lanes readable (8 values in pass 1, 4 in pass 2)
@@ -181,7 +190,8 @@ static void lamb_check_planes(const at::Tensor& master, const at::Tensor& mom, c
 int64_t wire_lamb_moments(const at::Tensor& wire, int64_t shard_elems, int64_t n_shards, int64_t skip_shard,
                           int64_t skip_period, const at::Tensor& master, at::Tensor& mom, at::Tensor& var,
                           const std::vector<double>& scalars, double grad_scale, int64_t n_valid, int64_t n_adapt,
-                          at::Tensor& partials, int64_t partials_base, int64_t codec, int64_t shard_stride) {
+                          at::Tensor& partials, int64_t partials_base, int64_t codec, int64_t shard_stride,
+                          const c10::optional<at::Tensor>& clip) {
   FAN_T_CUDA_CONTIG(wire);
   FAN_T_CUDA_CONTIG(partials);
   TORCH_CHECK(shard_elems > 0 && n_shards > 0 && n_valid >= 0 && n_valid <= shard_elems * n_shards, "bad shape");
@@ -200,8 +210,50 @@ int64_t wire_lamb_moments(const at::Tensor& wire, int64_t shard_elems, int64_t n
   fan::launch_wire_lamb_moments((int)codec, wire.data_ptr(), (size_t)shard_elems, (int)n_shards, (int)skip_shard,
                                 (int)skip_period, master.data_ptr<float>(), mom.data_ptr<float>(), p, (size_t)n_valid,
                                 (size_t)n_adapt, partials.data_ptr<double>() + 2 * partials_base, fan_stream(),
-                                (size_t)shard_stride);
+                                (size_t)shard_stride, clip_words_ptr(clip));
   return pairs;
+}
+
+// the norm pass of a clip group over one gathered wire region; returns the partials written from partials_base
+int64_t wire_sumsq(const at::Tensor& wire, int64_t shard_elems, int64_t n_shards, int64_t skip_shard,
+                   int64_t skip_period, int64_t n_valid, at::Tensor& partials, int64_t partials_base, int64_t codec,
+                   int64_t shard_stride) {
+  FAN_T_CUDA_CONTIG(wire);
+  FAN_T_CUDA_CONTIG(partials);
+  TORCH_CHECK(shard_elems > 0 && n_shards > 0 && n_valid >= 0 && n_valid <= shard_elems * n_shards, "bad shape");
+  const size_t sb = fan::wire_shard_bytes((int)codec, shard_elems);
+  TORCH_CHECK(shard_stride == 0 || (size_t)shard_stride >= sb, "shard_stride below the packed shard size");
+  TORCH_CHECK(shard_stride % 16 == 0, "shard_stride must keep 16-byte alignment");
+  const size_t need = shard_stride ? (size_t)shard_stride * (n_shards - 1) + sb : sb * n_shards;
+  TORCH_CHECK((size_t)wire.numel() * wire.element_size() >= need, "wire buffer too small");
+  const int64_t blocks = fan::sumsq_partials_for((size_t)shard_elems);
+  TORCH_CHECK(partials.scalar_type() == at::kDouble && partials_base >= 0 &&
+                  partials.numel() >= partials_base + blocks,
+              "partials: f64[partials_base + ", blocks, "]");
+  fan::launch_wire_sumsq((int)codec, wire.data_ptr(), (size_t)shard_elems, (int)n_shards, (int)skip_shard,
+                         (int)skip_period, (size_t)n_valid, partials.data_ptr<double>() + partials_base, fan_stream(),
+                         (size_t)shard_stride);
+  return blocks;
+}
+
+// the coefficient of a clip group from its members' partial segments (tensor, first partial, count), in order
+void clip_coef(const std::vector<at::Tensor>& partials, const std::vector<int64_t>& bases,
+               const std::vector<int64_t>& counts, double max_norm, double grad_scale, at::Tensor& words) {
+  FAN_T_CUDA_CONTIG(words);
+  TORCH_CHECK(words.scalar_type() == at::kFloat && words.numel() >= 4, "words: f32[4]");
+  const size_t n = partials.size();
+  TORCH_CHECK(n <= (size_t)fan::kClipSegments && bases.size() == n && counts.size() == n, "clip_coef: at most ",
+              fan::kClipSegments, " segments, one (partials, base, count) each");
+  fan::ClipSegments seg{};
+  for (size_t k = 0; k < n; ++k) {
+    FAN_T_CUDA_CONTIG(partials[k]);
+    TORCH_CHECK(partials[k].scalar_type() == at::kDouble && bases[k] >= 0 && counts[k] >= 0 &&
+                    counts[k] <= (int64_t)INT32_MAX && partials[k].numel() >= bases[k] + counts[k],
+                "clip_coef: segment ", k, ": f64[base + count]");
+    seg.p[k] = partials[k].data_ptr<double>() + bases[k];
+    seg.n[k] = (int)counts[k];
+  }
+  fan::launch_clip_coef(seg, (int)n, max_norm, (float)grad_scale, words.data_ptr<float>(), fan_stream());
 }
 
 void lamb_ratio(const at::Tensor& partials, int64_t n_pairs, double lr, at::Tensor& words) {
@@ -252,12 +304,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wire_reduce", &wire_reduce, "sum wire slots (+ dense local) -> wire and/or f32", pybind11::arg("slots"),
         pybind11::arg("n_slots"), pybind11::arg("self_pos"), pybind11::arg("local"), pybind11::arg("out_wire"),
         pybind11::arg("out_f32"), pybind11::arg("shard_elems"), pybind11::arg("codec"));
-  m.def("wire_sgd", &wire_sgd, "fused decode + SGD weight update in place");
+  m.def("wire_sgd", &wire_sgd, "fused decode + SGD weight update in place", pybind11::arg("wire"),
+        pybind11::arg("shard_elems"), pybind11::arg("n_shards"), pybind11::arg("skip_shard"),
+        pybind11::arg("skip_period"), pybind11::arg("master"), pybind11::arg("lp"), pybind11::arg("mom"),
+        pybind11::arg("lr"), pybind11::arg("grad_scale"), pybind11::arg("weight_decay"), pybind11::arg("momentum"),
+        pybind11::arg("nesterov"), pybind11::arg("n_valid"), pybind11::arg("codec"),
+        pybind11::arg("clip") = pybind11::none());
   m.def("wire_adamw", &wire_adamw, "fused decode + AdamW weight update in place", pybind11::arg("wire"),
         pybind11::arg("shard_elems"), pybind11::arg("n_shards"), pybind11::arg("skip_shard"),
         pybind11::arg("skip_period"), pybind11::arg("master"), pybind11::arg("lp"), pybind11::arg("mom"),
         pybind11::arg("var"), pybind11::arg("scalars"), pybind11::arg("grad_scale"), pybind11::arg("weight_decay"),
-        pybind11::arg("n_valid"), pybind11::arg("codec"), pybind11::arg("shard_stride") = 0);
+        pybind11::arg("n_valid"), pybind11::arg("codec"), pybind11::arg("shard_stride") = 0,
+        pybind11::arg("clip") = pybind11::none());
+  m.def("sumsq_partials_for", [](int64_t n_s) { return (int64_t)fan::sumsq_partials_for((size_t)n_s); },
+        "fp64 partials one wire_sumsq launch over shards of n_s elements writes");
+  m.def("wire_sumsq", &wire_sumsq, "clip group norm pass: fp64 partial sums of squares of a gathered wire region",
+        pybind11::arg("wire"), pybind11::arg("shard_elems"), pybind11::arg("n_shards"), pybind11::arg("skip_shard"),
+        pybind11::arg("skip_period"), pybind11::arg("n_valid"), pybind11::arg("partials"),
+        pybind11::arg("partials_base"), pybind11::arg("codec"), pybind11::arg("shard_stride") = 0);
+  m.def("clip_coef", &clip_coef, "clip group coefficient -> words {coef, total, max_norm, nonfinite}",
+        pybind11::arg("partials"), pybind11::arg("bases"), pybind11::arg("counts"), pybind11::arg("max_norm"),
+        pybind11::arg("grad_scale"), pybind11::arg("words"));
   m.def("lamb_partials_for", [](int64_t n_s) { return (int64_t)fan::lamb_partials_for((size_t)n_s); },
         "{S_w, S_r} pairs one wire_lamb_moments launch over shards of n_s elements writes");
   m.def("wire_lamb_moments", &wire_lamb_moments,
@@ -266,7 +333,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("skip_period"), pybind11::arg("master"), pybind11::arg("mom"), pybind11::arg("var"),
         pybind11::arg("scalars"), pybind11::arg("grad_scale"), pybind11::arg("n_valid"), pybind11::arg("n_adapt"),
         pybind11::arg("partials"), pybind11::arg("partials_base"), pybind11::arg("codec"),
-        pybind11::arg("shard_stride") = 0);
+        pybind11::arg("shard_stride") = 0, pybind11::arg("clip") = pybind11::none());
   m.def("lamb_ratio", &lamb_ratio, "trust ratio of n_pairs norm partials -> words {lr * phi, lr, phi}",
         pybind11::arg("partials"), pybind11::arg("n_pairs"), pybind11::arg("lr"), pybind11::arg("words"));
   m.def("wire_lamb_apply", &wire_lamb_apply, "trust-ratio pass 2: the weight step from the stored moments",

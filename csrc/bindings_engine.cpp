@@ -251,7 +251,7 @@ void register_engine(pybind11::module_& m) {
               c10::optional<at::Tensor> prepacked, int64_t prepacked_elems, int64_t layout_shard,
               int64_t layout_chunks, bool on_producer, int64_t opt, c10::optional<at::Tensor> var,
               c10::optional<std::vector<double>> adamw, c10::optional<std::vector<double>> lamb, int64_t n_adapt,
-              c10::optional<at::Tensor> trust_out) {
+              c10::optional<at::Tensor> trust_out, c10::optional<at::Tensor> clip) {
              FAN_T_CUDA_CONTIG(grad);
              TORCH_CHECK(grad.scalar_type() == at::kFloat || grad.scalar_type() == at::kBFloat16,
                          "gradients must be f32 or bf16");
@@ -326,6 +326,11 @@ void register_engine(pybind11::module_& m) {
                  req.trust_out = trust_out->data_ptr<float>();
                }
              }
+             if (clip && clip->defined()) {  // member of a clip group: its four f32 words
+               FAN_T_CUDA_CONTIG(*clip);
+               TORCH_CHECK(clip->scalar_type() == at::kFloat && clip->numel() >= 4, "clip: f32[4]");
+               req.clip_words = clip->data_ptr<float>();
+             }
              return e.submit(req, fan_stream());
            },
            py::arg("grad"), py::arg("master"), py::arg("lp") = py::none(), py::arg("mom") = py::none(),
@@ -335,7 +340,8 @@ void register_engine(pybind11::module_& m) {
            py::arg("prepacked_elems") = 0, py::arg("layout_shard") = 0, py::arg("layout_chunks") = 0,
            py::arg("on_producer") = false, py::arg("opt") = 0, py::arg("var") = py::none(),
            py::arg("adamw") = py::none(), py::arg("lamb") = py::none(), py::arg("n_adapt") = -1,
-           py::arg("trust_out") = py::none(), py::call_guard<py::gil_scoped_release>())
+           py::arg("trust_out") = py::none(), py::arg("clip") = py::none(),
+           py::call_guard<py::gil_scoped_release>())
       .def("prepack_shape", [](AllReduceEngine& e, int64_t n) {
         const auto s = e.prepack_shape(n);
         return py::make_tuple(s[0], s[1], s[2]);
@@ -348,6 +354,16 @@ void register_engine(pybind11::module_& m) {
           },
           py::arg("slot"), py::arg("after_current") = true, py::arg("seq") = 0u,
           py::call_guard<py::gil_scoped_release>())
+      .def(
+          "commit_group",
+          [](AllReduceEngine& e, const std::vector<int>& slots, const std::vector<uint32_t>& seqs, double max_norm,
+             double grad_scale, bool after_current) {
+            e.commit_group(slots, seqs, max_norm, (float)grad_scale, after_current,
+                           after_current ? fan_stream() : nullptr);
+          },
+          py::arg("slots"), py::arg("seqs"), py::arg("max_norm"), py::arg("grad_scale") = 1.0,
+          py::arg("after_current") = true, py::call_guard<py::gil_scoped_release>(),
+          "commit a clip group: one coefficient launch over the members' norm partials, then each member's update")
       .def(
           "wait_stream", [](AllReduceEngine& e, int slot, uint32_t seq) { e.wait_stream(slot, fan_stream(), seq); },
           py::arg("slot"), py::arg("seq") = 0u)

@@ -250,10 +250,10 @@ static void update_at(const EngineRequest& req, int codec, const void* wire, siz
     AdamWParams a = req.upd.adamw;
     a.var += off;
     launch_wire_adamw(codec, wire, n_s, n_shards, skip_shard, skip_period, req.master + off, lp, req.mom + off, a, nv,
-                      st, shard_stride);
+                      st, shard_stride, req.clip_words);
   } else {
     launch_wire_sgd(codec, wire, n_s, n_shards, skip_shard, skip_period, req.master + off, lp,
-                    req.mom ? req.mom + off : nullptr, req.upd.sgd, nv, st, shard_stride);
+                    req.mom ? req.mom + off : nullptr, req.upd.sgd, nv, st, shard_stride, req.clip_words);
   }
 }
 
@@ -304,13 +304,14 @@ EpiThunk AllReduceEngine::lamb_region(const EngineRequest& req, const uint8_t* w
   float* master = req.master + off;
   float* mom = req.mom + off;
   bf16_t* lp = req.lp ? req.lp + off : nullptr;
+  const float* clip = req.clip_words;  // pass 1 takes the clipped gradient; the ratio and pass 2 are as ever
   cur_.apply.push_back([=](hipStream_t es) {
     launch_wire_lamb_apply(master, lp, mom, p, words, (size_t)shard_elems, skip_shard, skip_period, (size_t)nv,
                            adapt_end, es);
   });
   return [=](hipStream_t es) {
     launch_wire_lamb_moments(c, wire, (size_t)shard_elems, n_shards, skip_shard, skip_period, master, mom, p,
-                             (size_t)nv, adapt_end, part, es, shard_stride);
+                             (size_t)nv, adapt_end, part, es, shard_stride, clip);
   };
 }
 
@@ -318,6 +319,17 @@ EpiThunk AllReduceEngine::make_epilogue(const EngineRequest& req, const uint8_t*
                                         int n_shards, int64_t off, int64_t len, int skip_shard, int skip_period) {
   const int c = cfg_.codec;
   const int64_t nv = valid_in(req.n_valid, off, len);
+  if (req.clip_words && nv > 0) {
+    // the norm pass of this region, now: the gathered wire is complete in the order of cur_.run at every call site
+    // (a clipped request is deferred, so the direct mesh has copied it out of the arena), and the launch runs beside
+    // the backward's remaining GEMMs; only the group's coefficient launch waits for the end of the backward
+    const int blocks = sumsq_partials_for((size_t)shard_elems);
+    FAN_CHECK(cur_.clip_partials != nullptr && cur_.clip_count + blocks <= cur_.clip_cap,
+              "clip: more update regions than the request's partials buffer holds");
+    launch_wire_sumsq(c, wire, (size_t)shard_elems, n_shards, skip_shard, skip_period, (size_t)nv,
+                      cur_.clip_partials + cur_.clip_count, cur_.run);
+    cur_.clip_count += blocks;
+  }
   if (trust(req) && nv > 0) {
     const EpiThunk pass1 = lamb_region(req, wire, shard_elems, n_shards, off, nv, skip_shard, skip_period);
     float* out_sum = req.out_sum;
@@ -1055,6 +1067,25 @@ int AllReduceEngine::submit(const EngineRequest& req, hipStream_t producer) {
     FAN_CHECK(!(cfg_.compat_owner_fp32 && cfg_.algo == 1), "trust ratio: not with the ring's compat_owner_fp32");
     FAN_CHECK(req.n_adapt >= -1 && req.n_adapt <= req.n_valid, "trust ratio: n_adapt must lie in [0, n_valid]");
   }
+  if (req.clip_words) {
+    // No weight of any request of the group moves before the norm over all of them exists: the same refusals as the
+    // trust ratio's, one level up (before the request takes a slot).
+    FAN_CHECK(req.update, "clip: update requests only (a sum-only request has no gradient scale to clip)");
+    FAN_CHECK(req.defer, "clip: a clipped request must be deferred (its update waits for the group's coefficient; the "
+                         "direct mesh's immediate path updates inside the communication phase)");
+    FAN_CHECK(!sharded(req), "clip: not with the sharded update (shard_update), whose owners update their shard before "
+                             "the bucket is reduced");
+    FAN_CHECK(layout(req.n_valid, req.layout_shard, req.layout_chunks).chunks <= 1,
+              "clip: not with a chunked layout (layout_chunks > 1, or a bucket above chunk_elems)");
+    FAN_CHECK(!(cfg_.compat_owner_fp32 && cfg_.algo == 1), "clip: not with the ring's compat_owner_fp32");
+  }
+  {
+    // the slot this request takes still holds a clipped request: its forced commit would update with a coefficient
+    // that does not exist yet (refused before the slot table moves on)
+    const int next = table_->next_slot();
+    FAN_CHECK(!clip_pending(next, 0), "a clip group holds at most 8 deferred requests (slot " + std::to_string(next) +
+                                          " still holds a clipped request: commit_group it first)");
+  }
   FAN_HIP_CHECK(hipSetDevice(device_));
   // slot state machine (slot_table.h): the next slot (a still-deferred occupant is committed first, ordered after
   // the producer: the NIC's 8-deep command queue never drops a request), ordering after anything that may still
@@ -1097,7 +1128,18 @@ int AllReduceEngine::submit(const EngineRequest& req, hipStream_t producer) {
     cur_.partials = reinterpret_cast<double*>(epi_scratch("lamb_partials", (size_t)cur_.pairs_cap * 16));
     cur_.words = req.trust_out ? req.trust_out : reinterpret_cast<float*>(epi_scratch("lamb_words", 16));
   }
+  x.clip_words = nullptr;
+  if (req.clip_words) {
+    const int cap = sumsq_partials_for(~size_t(0) >> 1), regions = cfg_.algo == 1 ? std::max(1, L.rings) : 1;
+    cur_.clip_cap = cap * regions;
+    cur_.clip_partials = reinterpret_cast<double*>(epi_scratch("clip_partials", (size_t)cur_.clip_cap * 8));
+  }
   std::vector<EpiThunk> thunks = cfg_.algo == 0 ? run_mesh(L, req) : run_ring(L, req);
+  if (req.clip_words) {
+    x.clip_words = req.clip_words;
+    x.clip_partials = cur_.clip_partials;
+    x.clip_count = cur_.clip_count;  // (0: a request without a valid element contributes nothing)
+  }
   if (trust(req)) {
     // the regions' pass-1 launches are enqueued (direct mesh) or in `thunks`; then one ratio over every region's
     // partials in region order, then the regions' pass 2 — all on the one stream the slot table runs a request's
@@ -1123,12 +1165,63 @@ int AllReduceEngine::submit(const EngineRequest& req, hipStream_t producer) {
   return b.slot;
 }
 
+bool AllReduceEngine::clip_pending(int slot, uint32_t seq) const {
+  const auto& sl = table_->slot(slot);
+  return sl.pending && (seq == 0 || seq == sl.seq) && extra_.at(slot).clip_words != nullptr;
+}
+
+static const char* const kClipAlone =
+    "a clipped request commits with its clip group only (commit_group): a clip group holds at most 8 deferred "
+    "requests, and none updates before the group's coefficient exists";
+
 void AllReduceEngine::commit(int slot, bool after_producer, hipStream_t producer, uint32_t seq) {
   RoctxRange rr("fan/allreduce/epilogue");
+  FAN_CHECK(!clip_pending(slot, seq), kClipAlone);
   table_->commit(slot, after_producer, producer, seq);
 }
 
-void AllReduceEngine::wait_stream(int slot, hipStream_t s, uint32_t seq) { table_->wait_stream(slot, s, seq); }
+void AllReduceEngine::commit_group(const std::vector<int>& slots, const std::vector<uint32_t>& seqs, double max_norm,
+                                   float grad_scale, bool after_producer, hipStream_t producer) {
+  RoctxRange rr("fan/allreduce/clip_group");
+  const size_t n = slots.size();
+  FAN_CHECK(n >= 1 && seqs.size() == n, "commit_group: one sequence number per slot, at least one request");
+  FAN_CHECK(n <= (size_t)kSlots, "commit_group: a clip group holds at most 8 deferred requests");
+  FAN_CHECK(max_norm > 0.0 && max_norm < __builtin_huge_val(), "commit_group: max_norm must be finite and positive");
+  const float* words = nullptr;
+  hipStream_t es = nullptr;
+  ClipSegments seg{};
+  for (size_t i = 0; i < n; ++i) {
+    const int s = slots[i];
+    FAN_CHECK(s >= 0 && s < kSlots, "commit_group: bad slot");
+    for (size_t j = 0; j < i; ++j) FAN_CHECK(slots[j] != s, "commit_group: a slot named twice");
+    const auto& sl = table_->slot(s);
+    FAN_CHECK(sl.pending && seqs[i] != 0 && sl.seq == seqs[i],
+              "commit_group: request " + std::to_string(i) + " (slot " + std::to_string(s) +
+                  ") is not pending any more, or its slot holds another request");
+    const SlotExtra& x = extra_[s];
+    FAN_CHECK(x.clip_words != nullptr, "commit_group: request " + std::to_string(i) + " was not submitted with clip words");
+    FAN_CHECK(i == 0 || x.clip_words == words, "commit_group: every request of a clip group names the same clip words");
+    const hipStream_t e = table_->epilogue_stream(s, after_producer, producer);
+    FAN_CHECK(i == 0 || e == es, "commit_group: the requests' epilogues would run on different streams (an on-producer "
+                                 "request beside comm-stream epilogues): one coefficient launch cannot precede them all");
+    words = x.clip_words;
+    es = e;
+    seg.p[i] = x.clip_partials;
+    seg.n[i] = x.clip_count;
+  }
+  FAN_HIP_CHECK(hipSetDevice(device_));
+  for (size_t i = 0; i < n; ++i) table_->wait_comm(slots[i], es, seqs[i]);
+  launch_clip_coef(seg, (int)n, max_norm, grad_scale, const_cast<float*>(words), es);
+  for (size_t i = 0; i < n; ++i) {
+    extra_[slots[i]].clip_words = nullptr;  // (the update thunks hold the pointer)
+    table_->commit(slots[i], after_producer, producer, seqs[i]);
+  }
+}
+
+void AllReduceEngine::wait_stream(int slot, hipStream_t s, uint32_t seq) {
+  FAN_CHECK(!clip_pending(slot, seq), kClipAlone);
+  table_->wait_stream(slot, s, seq);
+}
 
 bool AllReduceEngine::query(int slot, uint32_t seq) { return table_->query(slot, seq); }
 
@@ -1259,6 +1352,7 @@ std::string AllReduceEngine::diagnostics(int slot) const {
 }
 
 void AllReduceEngine::synchronize(int slot, double timeout_s, uint32_t seq) {
+  FAN_CHECK(!clip_pending(slot, seq), kClipAlone);
   table_->commit_for_host_wait(slot, seq);
   const double t0 = now_s();
   const double tmo = timeout_s > 0 ? timeout_s : cfg_.timeout_s;

@@ -165,6 +165,11 @@ struct EngineRequest {
   // writes (nullptr: a per-slot scratch of the engine holds them)
   int64_t n_adapt = -1;
   float* trust_out = nullptr;
+  // global-norm clipping: the four f32 device words {coef, total, max_norm, nonfinite} of the request's clip group
+  // (bfp_format.h launch_clip_coef). Non-null: an update request that must be deferred; its communication phase ends
+  // with the norm pass over its gathered wire, and commit_group() — never commit() — enqueues its update, which
+  // scales grad_scale by words[0].
+  const float* clip_words = nullptr;
   float* out_sum = nullptr;
   const uint8_t* prepacked = nullptr;
   int64_t prepacked_elems = 0;
@@ -235,6 +240,12 @@ class AllReduceEngine {
   // request never commits or waits on that newer request's behalf (its own epilogue was committed when the
   // slot was reused, see submit()).
   void commit(int slot, bool after_producer, hipStream_t producer, uint32_t seq = 0);
+  // Commit a clip group: the pending requests (slots[i], seqs[i]) submitted with one clip_words, at most kSlots, all of
+  // one optimizer step. Orders the members' common epilogue stream after every member's communication phase (which
+  // ended with its norm pass), launches the coefficient over the members' partials in the order given
+  // (total = ||g|| * |grad_scale|, grad_scale the members' common value), then commits each member as commit() would.
+  void commit_group(const std::vector<int>& slots, const std::vector<uint32_t>& seqs, double max_norm,
+                    float grad_scale, bool after_producer, hipStream_t producer);
   void wait_stream(int slot, hipStream_t s, uint32_t seq = 0);  // GPU-side wait
   bool query(int slot, uint32_t seq = 0);                       // host: request done?
   // the slot's host-mapped done word: the last completed sequence number, written only when done words are on
@@ -311,8 +322,14 @@ class AllReduceEngine {
     bool counted = false;   // device time already added to counters_
     double t_issue = 0.0;
     int trace = -1;  // index into trace_pool_ (-1: not traced)
+    // the slot's request is a member of a clip group (while it is pending): the group's words, its norm partials
+    const float* clip_words = nullptr;
+    const double* clip_partials = nullptr;
+    int clip_count = 0;
   };
   std::array<SlotExtra, kSlots> extra_;
+  // a clipped request is still pending in `slot` (as `seq`, or whoever holds the slot): only commit_group commits it
+  bool clip_pending(int slot, uint32_t seq) const;
 
   // The request being built: reset at the top of submit(), read only by submit() and the schedules it calls.
   struct Current {
@@ -328,6 +345,10 @@ class AllReduceEngine {
     float* words = nullptr;
     int pairs = 0, pairs_cap = 0;  // {S_w, S_r} pairs the regions so far write / the buffer holds
     std::vector<EpiThunk> apply;
+    // clipped request: each region handed to make_epilogue runs its norm pass on `run` right away and writes its own
+    // segment of clip_partials (one region for mesh, one per ring), as the trust ratio's pass 1 does `partials`
+    double* clip_partials = nullptr;
+    int clip_count = 0, clip_cap = 0;
   } cur_;
   bool trust(const EngineRequest& req) const { return req.update && req.upd.kind == kOptAdamW && req.upd.trust; }
   // One gathered wire region of the trust-ratio request being built, covering nv > 0 valid elements from bucket

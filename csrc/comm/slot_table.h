@@ -69,6 +69,8 @@ class SlotTable {
     bool on_producer = false;    // multi-rank request that ran on its producer stream (begin(.., true))
     uint64_t comm_done_mark = 0; // comm-stream order of the last comm_done / done record (0: not on the comm stream)
     uint64_t done_mark = 0;
+    bool comm_waited = false;    // wait_comm() already ordered comm_waited_on after this request's communication phase
+    Stream comm_waited_on{};
     std::vector<Thunk> thunks;
   };
 
@@ -147,6 +149,7 @@ class SlotTable {
     Slot& sl = slots_.at(s);
     if (!cfg_.inline_mode) sl.comm_done_mark = record_m(sl.comm_done, sl.stream);
     sl.thunks = std::move(thunks);
+    sl.comm_waited = false;
     sl.pending = true;
     sl.used = true;
     sl.seq = seq_ = following(seq_);
@@ -160,6 +163,30 @@ class SlotTable {
     Slot& sl = slots_.at(s);
     if (seq != 0 && seq != sl.seq) return;
     commit_slot(s, after_producer, producer);
+  }
+
+  // The stream commit(s, after_producer, producer) would enqueue the pending epilogue of slot s on (commit_slot's
+  // choice, without committing anything).
+  Stream epilogue_stream(int s, bool after_producer, Stream producer) const {
+    const Slot& sl = slots_.at(s);
+    if (cfg_.epi_on_producer && !cfg_.inline_mode && after_producer && !(producer == sl.stream)) return producer;
+    if (cfg_.side_epi && after_producer) return cfg_.side;
+    return sl.stream;
+  }
+
+  // GPU-side: stream `st` waits for the communication phase of the pending request in slot s (not for its epilogue,
+  // which is not enqueued yet) — what a launch over several deferred requests' communication results needs before
+  // the requests themselves are committed (the coefficient of a clip group). `seq` as in commit(). Nothing to do
+  // when `st` is the stream the phase ran on (inline requests, ordinarily); a wait on comm_done otherwise, subject to
+  // the wait elision, and commit_slot does not repeat it on the same stream.
+  void wait_comm(int s, Stream st, uint32_t seq = 0) {
+    Slot& sl = slots_.at(s);
+    if ((seq != 0 && seq != sl.seq) || !sl.pending) return;
+    if (st == sl.stream) return;
+    if (cfg_.inline_mode) sl.comm_done_mark = record_m(sl.comm_done, sl.stream);  // (no comm_done record at end())
+    wait_m(st, sl.comm_done, sl.comm_done_mark);
+    sl.comm_waited = true;
+    sl.comm_waited_on = st;
   }
 
   // GPU-side: stream `st` waits for the request.
@@ -238,7 +265,7 @@ class SlotTable {
     if (cfg_.epi_on_producer && !cfg_.inline_mode && after_producer && !(producer == sl.stream)) {
       // epilogue on the producer (compute) stream, after the request's communication phase: it runs after
       // everything already enqueued there and never concurrently with the producer's GEMMs
-      wait_m(producer, sl.comm_done, sl.comm_done_mark);
+      if (!(sl.comm_waited && sl.comm_waited_on == producer)) wait_m(producer, sl.comm_done, sl.comm_done_mark);
       sl.epi_stream = producer;
       on_producer = true;
     } else if (cfg_.side_epi && after_producer) {
@@ -246,7 +273,7 @@ class SlotTable {
       // after the request's own inline work (on the stream it was submitted from, when another stream commits)
       dev_.record(sl.update, producer);
       dev_.wait(cfg_.side, sl.update);
-      if (!(producer == sl.stream)) {
+      if (!(producer == sl.stream) && !(sl.comm_waited && sl.comm_waited_on == cfg_.side)) {
         sl.comm_done_mark = record_m(sl.comm_done, sl.stream);
         dev_.wait(cfg_.side, sl.comm_done);
       }

@@ -116,7 +116,8 @@ def run(argv=None, out=sys.stdout):
             opt_step = int(info.get("opt_step", 0))
     trainer = DataParallelTrainer(model, engine, lr=cfg.lr, weight_decay=cfg.weight_decay, momentum=cfg.momentum,
                                   loss_scale=cfg.loss_scale, profile=cfg.profile, optimizer=cfg.optimizer,
-                                  betas=(cfg.beta1, cfg.beta2), eps=cfg.eps, trust_ratio=cfg.trust_ratio)
+                                  betas=(cfg.beta1, cfg.beta2), eps=cfg.eps, trust_ratio=cfg.trust_ratio,
+                                  max_grad_norm=cfg.clip_grad_norm if cfg.clip_grad_norm > 0 else None)
     trainer.opt_step = opt_step
     x, y = make_data(mb, sizes[0], sizes[-1], rank, cfg.seed, device, dtype)
     threads = int(os.environ.get("OMP_NUM_THREADS", "1"))

@@ -40,6 +40,7 @@ class TrainConfig:
     weight_decay: float = 0.0
     optimizer: str = "sgd"         # sgd | adamw
     trust_ratio: bool = False      # adamw: layer-wise trust ratio (LAMB)
+    clip_grad_norm: float = 0.0    # > 0: clip the reduced gradient of all layers to this 2-norm (0: off)
     beta1: float = 0.9
     beta2: float = 0.999
     eps: float = 1e-8
@@ -76,6 +77,9 @@ def add_named_flags(ap: argparse.ArgumentParser):
                     help="weight update fused into the all-reduce epilogue")
     ap.add_argument("--trust-ratio", action="store_true",
                     help="AdamW: scale each layer's step by ||w|| / ||update|| (LAMB; two-pass epilogue)")
+    ap.add_argument("--clip-grad-norm", type=float, default=d.clip_grad_norm,
+                    help="clip the step's reduced gradient (all layers, one vector) to this 2-norm (0: off; at most 8 "
+                         "layers)")
     ap.add_argument("--beta1", type=float, default=d.beta1, help="AdamW first-moment decay")
     ap.add_argument("--beta2", type=float, default=d.beta2, help="AdamW second-moment decay")
     ap.add_argument("--eps", type=float, default=d.eps, help="AdamW denominator term")

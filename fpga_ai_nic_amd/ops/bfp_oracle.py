@@ -183,6 +183,38 @@ def sgd(w: np.ndarray, g: np.ndarray, lr: float, grad_scale: float = 1.0, weight
     return w, new_mom
 
 
+def clip_sumsq(g: np.ndarray) -> float:
+    """S of a clip group's norm: the exactly rounded float64 sum (``math.fsum``) of the exact float64 squares of the
+    f32 values ``g``; a non-finite value gives numpy's non-finite sum."""
+    g64 = np.asarray(g, np.float32).reshape(-1).astype(np.float64)
+    if np.isfinite(g64).all():
+        return math.fsum(g64 * g64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return float(np.sum(g64 * g64))
+
+
+def clip_words(S: float, grad_scale: float, max_norm: float) -> np.ndarray:
+    """The four f32 words {coef, f32(total), f32(max_norm), nonfinite} of a clip group from S = sum g^2 over all its
+    requests: total = sqrt(S) * |f32(grad_scale)| (the scale the update kernels apply), coef = min(1, max_norm /
+    (total + 1e-6)) (``torch.nn.utils.clip_grad_norm_``), all float64, rounded once to f32. A non-finite S gives a NaN
+    coef (it propagates through the update, as torch's with ``error_if_nonfinite=False``) and sets the flag."""
+    max_norm = float(max_norm)
+    if not (max_norm > 0 and math.isfinite(max_norm)):
+        raise ValueError(f"max_norm must be finite and positive, got {max_norm}")
+    S = float(S)
+    finite = math.isfinite(S)
+    with np.errstate(invalid="ignore", over="ignore"):
+        total = np.sqrt(np.float64(S)) * abs(np.float64(np.float32(grad_scale)))
+        coef = min(1.0, max_norm / (float(total) + 1e-6)) if finite else math.nan
+        return np.array([coef, total, max_norm, 0.0 if finite else 1.0], np.float64).astype(np.float32)
+
+
+def clip_scale(grad_scale: float, words) -> float:
+    """The grad_scale a clipped update uses: the one f32 product f32(grad_scale) * words[0]."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        return float(np.float32(grad_scale) * np.float32(np.asarray(words, np.float32).reshape(-1)[0]))
+
+
 class AdamWScalars(tuple):
     """The per-step AdamW scalars, each already rounded to f32 (``adamw_scalars``); ``wd`` rides along because the
     update tests it against 0."""

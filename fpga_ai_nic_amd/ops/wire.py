@@ -86,15 +86,19 @@ def reduce(slots: torch.Tensor, n_slots: int, self_pos: int, local: torch.Tensor
 def sgd(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Tensor, *, codec,
         lp: torch.Tensor | None = None, mom: torch.Tensor | None = None, lr: float, grad_scale: float = 1.0,
         weight_decay: float = 0.0, momentum: float = 0.0, nesterov: bool = False, n_valid: int | None = None,
-        skip_shard: int = -1, skip_period: int = 0):
-    """Fused decode + SGD in place: master -= lr * (scale * g [+ wd * w], momentum); lp = bf16(master)."""
+        skip_shard: int = -1, skip_period: int = 0, clip: torch.Tensor | None = None):
+    """Fused decode + SGD in place: master -= lr * (scale * g [+ wd * w], momentum); lp = bf16(master).
+    ``clip``: a clip group's four f32 words (:func:`clip_coef`); the update then uses the one f32 product
+    ``grad_scale * clip[0]`` (``bfp_oracle.clip_scale``) in place of ``grad_scale``."""
     c = codec_id(codec)
     n_valid = master.numel() if n_valid is None else int(n_valid)
     if master.is_cuda:
         _ext.require().wire_sgd(wire, int(shard_elems), int(n_shards), int(skip_shard), int(skip_period), master,
                                 lp, mom, float(lr), float(grad_scale), float(weight_decay), float(momentum),
-                                bool(nesterov), n_valid, c)
+                                bool(nesterov), n_valid, c, clip)
         return
+    if clip is not None:
+        grad_scale = O.clip_scale(grad_scale, _np_f32(clip))
     n = shard_elems * n_shards
     g = O.unpack(_np_u8(wire), n, shard_elems, c)
     w = master.view(-1).numpy()
@@ -118,10 +122,10 @@ def sgd(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Tenso
 def adamw(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Tensor, *, codec,
           mom: torch.Tensor, var: torch.Tensor, scalars: O.AdamWScalars, lp: torch.Tensor | None = None,
           grad_scale: float = 1.0, n_valid: int | None = None, skip_shard: int = -1, skip_period: int = 0,
-          shard_stride: int = 0):
+          shard_stride: int = 0, clip: torch.Tensor | None = None):
     """Fused decode + AdamW in place (``bfp_oracle.adamw``'s arithmetic): ``mom`` / ``var`` are the first / second
     moment planes, ``scalars`` the step's ``bfp_oracle.adamw_scalars``; lp = bf16(master). ``shard_stride``: bytes
-    between consecutive wire shards (0: packed)."""
+    between consecutive wire shards (0: packed). ``clip``: as :func:`sgd`."""
     c = codec_id(codec)
     if mom is None or var is None:
         raise ValueError("AdamW needs both moment planes (mom, var)")
@@ -131,8 +135,10 @@ def adamw(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Ten
     if master.is_cuda:
         _ext.require().wire_adamw(wire, int(shard_elems), int(n_shards), int(skip_shard), int(skip_period), master,
                                   lp, mom, var, scalars.kernel_args(), float(grad_scale), float(scalars.wd), n_valid,
-                                  c, int(shard_stride))
+                                  c, int(shard_stride), clip)
         return
+    if clip is not None:
+        grad_scale = O.clip_scale(grad_scale, _np_f32(clip))
     sb = O.shard_bytes(c, shard_elems)
     raw = _np_u8(wire)
     if shard_stride:
@@ -183,12 +189,13 @@ def lamb_partials_for(master: torch.Tensor, shard_elems: int) -> int:
 def lamb_moments(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Tensor, *, codec,
                  mom: torch.Tensor, var: torch.Tensor, scalars: O.LambScalars, partials: torch.Tensor,
                  partials_base: int = 0, grad_scale: float = 1.0, n_valid: int | None = None,
-                 n_adapt: int | None = None, skip_shard: int = -1, skip_period: int = 0, shard_stride: int = 0) -> int:
+                 n_adapt: int | None = None, skip_shard: int = -1, skip_period: int = 0, shard_stride: int = 0,
+                 clip: torch.Tensor | None = None) -> int:
     """Pass 1 of the trust-ratio (LAMB) update (``bfp_oracle.lamb_moments``): decode the wire, store the new moments
     in ``mom`` / ``var``, leave ``master`` untouched, and write the launch's fp64 partial sums of w^2 and r^2 over the
     flat elements below ``n_adapt`` (default ``n_valid``) as {S_w, S_r} pairs from pair ``partials_base`` of
     ``partials`` (float64). Returns the pairs written (:func:`lamb_partials_for`); :func:`lamb_ratio` sums the pairs of
-    every launch of a request."""
+    every launch of a request. ``clip``: as :func:`sgd` (the moments take the clipped gradient)."""
     c = codec_id(codec)
     if mom is None or var is None:
         raise ValueError("the trust-ratio update needs both moment planes (mom, var)")
@@ -200,7 +207,9 @@ def lamb_moments(wire: torch.Tensor, shard_elems: int, n_shards: int, master: to
         return int(_ext.require().wire_lamb_moments(wire, int(shard_elems), int(n_shards), int(skip_shard),
                                                     int(skip_period), master, mom, var, scalars.kernel_args(),
                                                     float(grad_scale), n_valid, n_adapt, partials,
-                                                    int(partials_base), c, int(shard_stride)))
+                                                    int(partials_base), c, int(shard_stride), clip))
+    if clip is not None:
+        grad_scale = O.clip_scale(grad_scale, _np_f32(clip))
     sb = O.shard_bytes(c, shard_elems)
     raw = _np_u8(wire)
     if shard_stride:
@@ -250,3 +259,51 @@ def lamb_apply(master: torch.Tensor, shard_elems: int, *, mom: torch.Tensor, var
         w[lo:hi] = O.lamb_apply(w[lo:hi], m[lo:hi], v[lo:hi], scalars, wd, max(0, min(n_adapt, hi) - lo))
         if lp is not None:
             lp.view(-1)[lo:hi].copy_(master.view(-1)[lo:hi].to(lp.dtype))
+
+
+def sumsq_partials_for(ref: torch.Tensor, shard_elems: int) -> int:
+    """fp64 partials one :func:`sumsq` launch over shards of ``shard_elems`` writes (CPU: one); ``ref``: any tensor
+    on the device the launch runs on."""
+    return int(_ext.require().sumsq_partials_for(int(shard_elems))) if ref.is_cuda else 1
+
+
+def sumsq(wire: torch.Tensor, shard_elems: int, n_shards: int, *, codec, partials: torch.Tensor,
+          partials_base: int = 0, n_valid: int | None = None, skip_shard: int = -1, skip_period: int = 0,
+          shard_stride: int = 0) -> int:
+    """The norm pass of a clip group over one gathered wire region (``bfp_oracle.clip_sumsq``): float64 partial sums
+    of the squares of the decoded values over the flat elements [0, n_valid) (:func:`sgd`'s traversal: skipped shards,
+    ``shard_stride``), written from ``partials[partials_base]``. Returns the partials written
+    (:func:`sumsq_partials_for`); :func:`clip_coef` sums the segments of every request of the group."""
+    c = codec_id(codec)
+    n_valid = shard_elems * n_shards if n_valid is None else int(n_valid)
+    if wire.is_cuda:
+        return int(_ext.require().wire_sumsq(wire, int(shard_elems), int(n_shards), int(skip_shard),
+                                             int(skip_period), n_valid, partials, int(partials_base), c,
+                                             int(shard_stride)))
+    sb = O.shard_bytes(c, shard_elems)
+    raw = _np_u8(wire)
+    if shard_stride:
+        raw = np.concatenate([raw[s * shard_stride: s * shard_stride + sb] for s in range(n_shards)])
+    g = O.unpack(raw, shard_elems * n_shards, shard_elems, c)
+    parts = [g[lo:hi] for lo, hi in _lamb_ranges(shard_elems, n_shards, n_valid, skip_shard, skip_period)]
+    partials.view(-1)[partials_base] = O.clip_sumsq(np.concatenate(parts)) if parts else 0.0
+    return 1
+
+
+def clip_coef(segments, max_norm: float, grad_scale: float, words: torch.Tensor):
+    """The coefficient of a clip group: sum the ``segments`` — (partials, base, count) triples, one per request, at
+    most 8, in order — in float64 and write the four f32 words {coef, f32(total), f32(max_norm), nonfinite}
+    (``bfp_oracle.clip_words``) into ``words``."""
+    segments = [(p, int(b), int(k)) for p, b, k in segments]
+    max_norm = float(max_norm)
+    if not (max_norm > 0 and math.isfinite(max_norm)):
+        raise ValueError(f"max_norm must be finite and positive, got {max_norm}")
+    if len(segments) > 8:
+        raise ValueError(f"a clip group holds at most 8 partial segments, got {len(segments)}")
+    if words.is_cuda:
+        _ext.require().clip_coef([p for p, _, _ in segments], [b for _, b, _ in segments],
+                                 [k for _, _, k in segments], max_norm, float(grad_scale), words)
+        return
+    terms = [p.view(-1)[b:b + k].numpy() for p, b, k in segments if k]
+    S = _sum64(np.concatenate(terms)) if terms else 0.0
+    words.view(-1)[:4] = torch.from_numpy(O.clip_words(S, grad_scale, max_norm))

@@ -67,6 +67,46 @@ def _round_up(a, b):
 
 
 OPTIMIZERS = ("sgd", "adamw")
+CLIP_GROUP_LIMIT = f"a clip group holds at most {NUM_SLOTS} deferred requests"
+
+
+def clip_request(clip, defer, device=None):
+    """Validate one request's ``clip=`` words (global-norm clipping, see ``commit_group``)."""
+    if clip is None:
+        return
+    if not (isinstance(clip, torch.Tensor) and clip.dtype == torch.float32 and clip.numel() >= 4
+            and clip.is_contiguous()):
+        raise ValueError("clip: the group's four f32 words (a contiguous float32 tensor of 4 elements)")
+    if device is not None and clip.device.type != torch.device(device).type:
+        raise ValueError(f"clip: the words live on {clip.device}, the engine runs on {device}")
+    if not defer:
+        raise ValueError("a clipped request must be deferred (defer=True): no weight may move before the norm over "
+                         "every request of the group exists")
+
+
+def clip_group_check(handles, max_norm):
+    """The checks of ``commit_group`` both engines share; returns the group's words tensor."""
+    handles = list(handles)
+    if not handles:
+        raise ValueError("commit_group: no request")
+    if len(handles) > NUM_SLOTS:
+        raise ValueError(f"commit_group: {len(handles)} requests: {CLIP_GROUP_LIMIT}")
+    max_norm = float(max_norm)
+    if not (max_norm > 0 and math.isfinite(max_norm)):
+        raise ValueError(f"commit_group: max_norm must be finite and positive, got {max_norm}")
+    if len({id(h) for h in handles}) != len(handles):
+        raise ValueError("commit_group: a request named twice")
+    for h in handles:
+        if getattr(h, "_clip", None) is None:
+            raise ValueError(f"commit_group: request '{h.name}' was not submitted with clip=")
+        if not h.pending:
+            raise ValueError(f"commit_group: request '{h.name}' (slot {h.slot}) is not pending any more")
+    words = handles[0]._clip["words"]
+    for h in handles[1:]:
+        w = h._clip["words"]
+        if w.data_ptr() != words.data_ptr() or w.device != words.device:
+            raise ValueError("commit_group: every request of a clip group names the same clip words")
+    return words
 
 
 def adamw_request(opt, mom, var, *, lr, weight_decay, momentum, nesterov, betas, eps, step, trust_ratio=False,
@@ -171,12 +211,17 @@ class Handle:
         self.name = name
         self.t_issue = time.time()
         self._pending = pending  # deferred epilogue thunks (see CompressedAllReduce.allreduce_sgd(defer=True))
+        self._clip = None  # member of a clip group: dict(words, partials, count), see allreduce_sgd(clip=)
 
     def commit(self, update_after=None):
         """Enqueue the deferred weight-update epilogue, after ``update_after`` (an event on the producer
         stream marking the last read of the old weights, e.g. the bwd-data GEMM)."""
         if self._pending is None:
             return self
+        if self._clip is not None:
+            # its update needs the group's coefficient, which only commit_group computes: never a stale one
+            raise ValueError(f"all-reduce '{self.name}' (slot {self.slot}) is a clipped request: it commits with its "
+                             f"group through engine.commit_group ({CLIP_GROUP_LIMIT})")
         thunks, self._pending = self._pending, None
         self.event = self.engine._run_thunks(thunks, update_after)
         return self
@@ -188,6 +233,11 @@ class Handle:
             ev = self.engine._event()
             ev.record()
         return self.commit(update_after=ev)
+
+    @property
+    def pending(self) -> bool:
+        """The deferred epilogue is not committed yet."""
+        return self._pending is not None
 
     def done(self) -> bool:
         if self._pending is not None:
@@ -314,13 +364,20 @@ class CompressedAllReduce:
                       nesterov: bool = False, update_after=None, defer: bool = False,
                       name: str = "bucket", opt: str = "sgd", var: torch.Tensor | None = None,
                       betas=(0.9, 0.999), eps: float = 1e-8, step: int | None = None, trust_ratio: bool = False,
-                      n_adapt: int | None = None, trust_out: torch.Tensor | None = None) -> Handle:
+                      n_adapt: int | None = None, trust_out: torch.Tensor | None = None,
+                      clip: torch.Tensor | None = None) -> Handle:
         """All-reduce ``grad`` (flat, padded to ``layout(n).n_pad``) and apply SGD to ``master`` (+bf16 ``lp``).
         ``opt="adamw"``: AdamW instead, ``mom`` / ``var`` the first / second moment planes (both required), ``step``
         the bucket's 1-based update count. ``trust_ratio`` (AdamW): scale the step of the bucket's first ``n_adapt``
         elements (default all ``n_valid``; the rest, a bias segment, take ratio 1) by ||w|| / ||update|| (LAMB): the
         epilogue becomes two passes around one norm reduction, and ``trust_out`` (3 f32, optional) receives
-        {lr * phi, lr, phi}."""
+        {lr * phi, lr, phi}. ``clip`` (four f32 words on the engine's device; ``defer=True`` required): the request
+        joins the clip group of those words — its communication phase ends with the norm pass over its reduced
+        gradient, and ``commit_group`` computes the group's coefficient and commits its members."""
+        clip_request(clip, defer, self.device)
+        if clip is not None and self.compat_owner_fp32 and self.algo == "ring":
+            raise ValueError("clip: not with compat_owner_fp32 (the owner's slices would be updated from another "
+                             "gradient than the one the norm was taken over)")
         n_valid = int(n_valid if n_valid is not None else master.numel())
         scalars = adamw_request(opt, mom, var, lr=lr, weight_decay=weight_decay, momentum=momentum,
                                 nesterov=nesterov, betas=betas, eps=eps, step=step, trust_ratio=trust_ratio,
@@ -334,17 +391,24 @@ class CompressedAllReduce:
         self._check(grad, L)
         sgd_kw = dict(lr=lr, grad_scale=grad_scale, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov)
         tr = dict(pairs=0, regions=[])  # trust ratio: the regions pass 1 has run over, for the ratio and pass 2
+        cl = None if clip is None else dict(words=clip.view(-1), partials=None, count=0, norm=True)
 
         def update(G, shard, n_shards, off, length, nv, codec, skip=(-1, 0)):
+            if cl is not None and cl["norm"]:  # the norm pass over this region (at the tail of the comm phase)
+                cl["count"] += wire.sumsq(G, shard, n_shards, codec=codec, partials=cl["partials"],
+                                          partials_base=cl["count"], n_valid=nv, skip_shard=skip[0],
+                                          skip_period=skip[1])
+                return
             planes = dict(lp=None if lp is None else lp.view(-1)[off:off + length],
-                          mom=None if mom is None else mom.view(-1)[off:off + length])
+                          mom=None if mom is None else mom.view(-1)[off:off + length],
+                          clip=None if cl is None else cl["words"])
             if lamb:
                 adapt = max(0, min(n_adapt - off, nv))
                 tr["pairs"] += wire.lamb_moments(G, shard, n_shards, master.view(-1)[off:off + length], codec=codec,
                                                  mom=planes["mom"], var=var.view(-1)[off:off + length],
                                                  scalars=scalars, partials=tr["partials"], partials_base=tr["pairs"],
                                                  grad_scale=grad_scale, n_valid=nv, n_adapt=adapt,
-                                                 skip_shard=skip[0], skip_period=skip[1])
+                                                 skip_shard=skip[0], skip_period=skip[1], clip=planes["clip"])
                 tr["regions"].append((shard, off, length, nv, adapt, skip))
             elif scalars is not None:
                 wire.adamw(G, shard, n_shards, master.view(-1)[off:off + length], codec=codec,
@@ -373,17 +437,62 @@ class CompressedAllReduce:
                                 lp=None if lp is None else lp.view(-1)[off:off + length], n_valid=nv, n_adapt=adapt,
                                 skip_shard=skip[0], skip_period=skip[1])
 
+        def clipped(thunks):
+            # the region thunks run once now, as norm passes (one partials segment per region: one for mesh, one per
+            # ring), on the stream of the communication phase; at commit they run again as the update
+            cap = wire.sumsq_partials_for(master, 1 << 40)
+            cl["partials"] = self._buf(L, "clip_partials", 8 * cap * max(1, self.rings), torch.float64, per_slot=True)
+            for t in thunks:
+                t()
+            cl["norm"] = False
+            return thunks
+
         def comm():
-            if not lamb:
+            if cl is not None:
+                thunks = clipped(list(self._run(L, grad, finish, owner_fp32)))
+                if not lamb:
+                    return thunks
+            elif not lamb:
                 return self._run(L, grad, finish, owner_fp32)
             # one partials segment per region a schedule hands to finish(): one (mesh), or one per ring
             cap = wire.lamb_partials_for(master, 1 << 40)
             tr["partials"] = self._buf(L, "lamb_partials", 16 * cap * max(1, self.rings), torch.float64, per_slot=True)
             tr["words"] = trust_out.view(-1) if trust_out is not None else \
                 self._buf(L, "lamb_words", 12, torch.float32, per_slot=True)
+            if cl is not None:
+                return thunks + [lamb_finish]
             return list(self._run(L, grad, finish, owner_fp32)) + [lamb_finish]
 
-        return self._launch(comm, name, L, defer, update_after)
+        h = self._launch(comm, name, L, defer, update_after)
+        h._clip = cl
+        return h
+
+    def commit_group(self, handles, *, max_norm: float, grad_scale: float = 1.0, update_after=None):
+        """Commit the clip group ``handles`` (deferred requests submitted with the same ``clip=`` words, at most 8,
+        all of one optimizer step): one coefficient launch over the members' norm partials in the order given —
+        ``words = {min(1, max_norm / (||g|| * |grad_scale| + 1e-6)), ||g|| * |grad_scale|, max_norm, nonfinite}`` with
+        ||g|| the 2-norm of the reduced gradient over every member (``bfp_oracle.clip_words``) — then each member's
+        update with ``grad_scale * words[0]``, after ``update_after`` (default: after everything enqueued so far on the
+        current stream). ``grad_scale``: the members' common value."""
+        handles = list(handles)
+        words = clip_group_check(handles, max_norm)
+        for h in handles:
+            if h.engine is not self:
+                raise ValueError("commit_group: a request of another engine")
+        segments = [(h._clip["partials"], 0, h._clip["count"]) for h in handles]
+        if update_after is None and self.cuda and not self.inline:
+            # after everything enqueued so far on the current stream (the bwd-data GEMMs that still read the weights)
+            update_after = self._event()
+            update_after.record()
+
+        def coef():
+            wire.clip_coef(segments, max_norm, grad_scale, words)
+
+        for i, h in enumerate(handles):
+            thunks, h._pending = h._pending, None
+            # one stream runs every member: the coefficient first, then the members in order
+            h.event = self._run_thunks(([coef] if i == 0 else []) + list(thunks), update_after if i == 0 else None)
+        return handles
 
     def allreduce(self, grad: torch.Tensor, out: torch.Tensor, *, n_valid: int | None = None,
                   name: str = "bucket") -> Handle:
@@ -415,6 +524,10 @@ class CompressedAllReduce:
         if prev is not None and prev._pending is not None:
             # more than NUM_SLOTS requests deferred: the slot's previous request must commit before its per-slot
             # scratch is reused (ordered after everything enqueued so far on the producer stream)
+            if prev._clip is not None:  # (its coefficient does not exist yet: never update with a stale one)
+                self._slot = slot
+                raise ValueError(f"all-reduce '{name}': slot {slot} still holds the clipped request '{prev.name}': "
+                                 f"{CLIP_GROUP_LIMIT}")
             prev.commit_after_current()
             self.stats["forced_commits"] = self.stats.get("forced_commits", 0) + 1
         self._cur_slot = slot  # per-slot scratch of the request comm_fn builds

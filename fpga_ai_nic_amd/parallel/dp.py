@@ -12,6 +12,7 @@ backward runs. MI355X mapping:
 """
 from __future__ import annotations
 
+import math
 import os
 import time
 
@@ -21,7 +22,7 @@ from ..models.mlp import MLP
 from ..ops import gemm as G
 from ..ops import gemm_tune, wire
 from ..utils import tracing
-from .allreduce import OPTIMIZERS, CompressedAllReduce, Handle, _round_up
+from .allreduce import NUM_SLOTS, OPTIMIZERS, CompressedAllReduce, Handle, _round_up
 from .transport import Transport
 
 
@@ -83,8 +84,18 @@ class DataParallelTrainer:
                  loss_scale: float = 1.0, average: bool = True, profile: bool = False, prepack: bool = True,
                  commit_at_end: bool | None = None, fused_update: bool | None = None,
                  gemm_inflight: str | None = None, wgrad_pair: bool | str | None = None, optimizer: str = "sgd",
-                 betas=(0.9, 0.999), eps: float = 1e-8, trust_ratio: bool = False):
-        """``optimizer``: 'sgd' or 'adamw' (``betas``, ``eps``; the model must hold the second-moment planes,
+                 betas=(0.9, 0.999), eps: float = 1e-8, trust_ratio: bool = False,
+                 max_grad_norm: float | None = None):
+        """``max_grad_norm``: clip the step's reduced gradient — every layer's, as one vector, after the all-reduce and
+        through the wire codec, times ``grad_scale`` — to this 2-norm (``torch.nn.utils.clip_grad_norm_``'s
+        coefficient). The layers' requests form one clip group: each ends its communication phase with a norm pass
+        over its gathered wire, and the step commits through ``engine.commit_group`` in the order L-1..0, whatever
+        ``commit_at_end`` says; ``grad_norm`` (f32[4] on the model's device) holds the last step's {coef, total norm,
+        max_grad_norm, nonfinite}, written on the device (no host sync). A group holds at most 8 requests, so at most
+        8 layers; ``fused_update`` is off (the GEMM epilogue cannot wait for the group); not with a sharded-update
+        engine. With any ``optimizer`` and with ``trust_ratio``.
+
+        ``optimizer``: 'sgd' or 'adamw' (``betas``, ``eps``; the model must hold the second-moment planes,
         ``MLP(..., adam=True)``). AdamW runs in the engine's decode + update epilogue — not in the bwd-weight GEMM's,
         so ``fused_update`` is off with it — with ``opt_step``, the 1-based update count, advanced once per
         ``backward_pass``. ``trust_ratio`` (AdamW): the layer-wise trust ratio (LAMB) — each layer's weight matrix
@@ -134,6 +145,19 @@ class DataParallelTrainer:
         self.trust_ratios = (torch.zeros(model.L, 3, dtype=torch.float32, device=model.device)
                              if self.trust_ratio else None)
         self._trust_partials = None  # the engine-less update's norm partials
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.grad_norm = None
+        self._clip_partials = None  # the engine-less update's norm partials, one segment per layer
+        if self.max_grad_norm is not None:
+            if not (self.max_grad_norm > 0 and math.isfinite(self.max_grad_norm)):
+                raise ValueError(f"max_grad_norm must be finite and positive, got {max_grad_norm}")
+            if model.L > NUM_SLOTS:
+                raise ValueError(f"max_grad_norm: the model has {model.L} layers; a clip group holds at most "
+                                 f"{NUM_SLOTS} deferred requests (one per layer)")
+            if bool(getattr(engine, "shard_update", False)):
+                raise ValueError("max_grad_norm: not with a sharded-update engine (each owner updates its shard before "
+                                 "the bucket is reduced)")
+            self.grad_norm = torch.zeros(4, dtype=torch.float32, device=model.device)
         self.loss_scale = loss_scale
         # gradients are of the LOCAL mean loss; the all-reduce sums over ranks -> average with 1/N
         self.grad_scale = (1.0 / self.world) if average else 1.0
@@ -151,9 +175,11 @@ class DataParallelTrainer:
         self.prepack = (prepack and engine is not None and getattr(engine, "prepack", False) and self.cuda
                         and model.dtype == torch.bfloat16)
         fu = os.environ.get("FAN_FUSED_UPDATE", "1") != "0" if fused_update is None else bool(fused_update)
-        # (the GEMM epilogue's update is SGD: AdamW takes the engine's decode + update pass)
+        # (the GEMM epilogue's update is SGD: AdamW takes the engine's decode + update pass; nor can it wait for a
+        # clip group's coefficient)
         self.fused_update = (fu and self.prepack and bool(getattr(engine, "inline", False))
-                             and getattr(engine, "codec", "") == "bfp_rne" and optimizer == "sgd")
+                             and getattr(engine, "codec", "") == "bfp_rne" and optimizer == "sgd"
+                             and self.max_grad_norm is None)
         self.fused_updates = 0
         # fused update: the layers' bias-gradient reduces of unsplit bwd-weight plans are queued and run by the next
         # split-K wire reduce of the backward, or all in one grouped launch after it (FAN_DEFER_COLSUM=0: one launch
@@ -189,12 +215,17 @@ class DataParallelTrainer:
         # (FAN_LAST_ON_PRODUCER=0: on the comm stream like the others)
         self.last_on_producer = (self.cuda and engine is not None and not getattr(engine, "inline", True)
                                  and hasattr(engine, "C") and os.environ.get("FAN_LAST_ON_PRODUCER", "1") != "0")
+        if self.max_grad_norm is not None and not bool(getattr(engine, "epilogue_on_producer", False)):
+            # an on-producer request's epilogue runs on the compute stream; with the others' on the comm stream the
+            # group's one coefficient launch could not precede them all
+            self.last_on_producer = False
 
     def _opt_kw(self, l):
         """The optimizer arguments of layer l's request in the step being enqueued."""
+        clip = {} if self.grad_norm is None else dict(clip=self.grad_norm)
         if self.optimizer != "adamw":
-            return {}
-        kw = dict(opt="adamw", var=l.var, betas=self.betas, eps=self.eps, step=self.opt_step)
+            return clip
+        kw = dict(clip, opt="adamw", var=l.var, betas=self.betas, eps=self.eps, step=self.opt_step)
         if self.trust_ratio:
             kw.update(trust_ratio=True, n_adapt=self._n_adapt(l), trust_out=self._trust_row(l))
         return kw
@@ -207,7 +238,21 @@ class DataParallelTrainer:
         """The adapted tensor of layer l's bucket: its weight matrix; the bias segment behind it takes ratio 1."""
         return l.cin * l.cout if self.m.bias else l.n
 
+    def _clip_local(self):
+        """The engine-less clip group: every layer's norm pass over its f32 gradient, then the coefficient."""
+        if self._clip_partials is None:
+            self._clip_partials = [torch.zeros(wire.sumsq_partials_for(l.master, l.n_pad), dtype=torch.float64,
+                                               device=l.master.device) for l in self.m.layers]
+        segs = []
+        for i in reversed(range(self.m.L)):
+            l = self.m.layers[i]
+            k = wire.sumsq(wire.as_bytes(l.grad), l.n_pad, 1, codec="raw_f32", partials=self._clip_partials[i],
+                           n_valid=l.n)
+            segs.append((self._clip_partials[i], 0, k))
+        wire.clip_coef(segs, self.max_grad_norm, self.grad_scale, self.grad_norm)
+
     def _sgd_local(self, l):
+        clip = self.grad_norm
         if self.trust_ratio:
             scalars = wire.O.lamb_scalars(self.lr, self.wd, self.betas[0], self.betas[1], self.eps, self.opt_step)
             if self._trust_partials is None:
@@ -215,18 +260,19 @@ class DataParallelTrainer:
                                                    device=l.master.device)
             words, kw = self._trust_row(l), dict(n_valid=l.n, n_adapt=self._n_adapt(l))
             k = wire.lamb_moments(wire.as_bytes(l.grad), l.n_pad, 1, l.master, codec="raw_f32", mom=l.mom, var=l.var,
-                                  scalars=scalars, partials=self._trust_partials, grad_scale=self.grad_scale, **kw)
+                                  scalars=scalars, partials=self._trust_partials, grad_scale=self.grad_scale,
+                                  clip=clip, **kw)
             wire.lamb_ratio(self._trust_partials, k, self.lr, words)
             wire.lamb_apply(l.master, l.n_pad, mom=l.mom, var=l.var, scalars=scalars, words=words, lp=l.lp, **kw)
             return
         if self.optimizer == "adamw":
             scalars = wire.O.adamw_scalars(self.lr, self.wd, self.betas[0], self.betas[1], self.eps, self.opt_step)
             wire.adamw(wire.as_bytes(l.grad), l.n_pad, 1, l.master, codec="raw_f32", lp=l.lp, mom=l.mom, var=l.var,
-                       scalars=scalars, grad_scale=self.grad_scale, n_valid=l.n)
+                       scalars=scalars, grad_scale=self.grad_scale, n_valid=l.n, clip=clip)
             return
         wire.sgd(wire.as_bytes(l.grad), l.n_pad, 1, l.master, codec="raw_f32", lp=l.lp, mom=l.mom, lr=self.lr,
                  grad_scale=self.grad_scale, weight_decay=self.wd, momentum=self.momentum, nesterov=self.nesterov,
-                 n_valid=l.n)
+                 n_valid=l.n, clip=clip)
 
     def step(self, x: torch.Tensor, labels: torch.Tensor):
         """One training iteration (reference type 'A': FWD + loss + BWD + all-reduce/UPD)."""
@@ -346,9 +392,10 @@ class DataParallelTrainer:
                             self._gemm_grid(True)
                         m.backward_data(i)
                         if h is not None:
-                            self.pending[i] = h if self.commit_at_end else h.commit_after_current()
+                            clipped = self.grad_norm is not None  # (commits with its group, below)
+                            self.pending[i] = h if self.commit_at_end or clipped else h.commit_after_current()
                             self.last_handle = self.pending[i]
-                        else:
+                        elif self.grad_norm is None:
                             self._sgd_local(l)
                 if prof and i == m.L - 1:
                     self._sync()
@@ -376,7 +423,15 @@ class DataParallelTrainer:
         if self.shard:  # this step's requests write lp_next: it holds the weights the next forward uses
             for i, l in enumerate(m.layers):
                 l.lp, self.lp_next[i] = self.lp_next[i], l.lp
-        if self.commit_at_end:  # issue order L-1..0: the epilogues run in the order their all-reduces finish
+        if self.grad_norm is not None and self.engine is None:
+            # no weight moves before the norm over every layer exists: the updates wait for the end of the backward
+            self._clip_local()
+            for i in reversed(range(m.L)):
+                self._sgd_local(m.layers[i])
+        elif self.grad_norm is not None:
+            self.engine.commit_group([self.pending[i] for i in reversed(range(m.L))], max_norm=self.max_grad_norm,
+                                     grad_scale=self.grad_scale)
+        elif self.commit_at_end:  # issue order L-1..0: the epilogues run in the order their all-reduces finish
             for i in reversed(range(m.L)):
                 h = self.pending[i]
                 for x in (h if isinstance(h, list) else [] if h is None else [h]):

@@ -23,7 +23,8 @@ import torch
 
 from .. import _ext
 from ..ops import wire
-from .allreduce import NUM_SLOTS, BucketLayout, ChecksumError, CommTimeoutError, adamw_request
+from .allreduce import (CLIP_GROUP_LIMIT, NUM_SLOTS, BucketLayout, ChecksumError, CommTimeoutError, adamw_request,
+                        clip_group_check, clip_request)
 from .transport import NativeTransport, Transport
 
 _ALGOS = {"mesh": 0, "ring": 1}
@@ -37,6 +38,7 @@ class NativeHandle:
         self.name = name
         self.t_issue = time.time()
         self._pending = pending
+        self._clip = None  # member of a clip group: dict(words=...), see NativeAllReduce.allreduce_sgd(clip=)
 
     def _superseded(self) -> bool:
         return self.engine.C.slot_seq(self.slot) != self.seq
@@ -52,12 +54,20 @@ class NativeHandle:
         """Enqueue the deferred epilogue; with ``update_after`` (any truthy value, e.g. an event recorded on
         the current stream) it is ordered after everything enqueued so far on the current stream."""
         if self.pending:
+            self._not_alone()
             self.engine.C.commit(self.slot, update_after is not None, self.seq)
             self._pending = False
         return self
 
+    def _not_alone(self):
+        if self._clip is not None:
+            # its update needs the group's coefficient, which only commit_group computes: never a stale one
+            raise ValueError(f"all-reduce '{self.name}' (slot {self.slot}) is a clipped request: it commits with its "
+                             f"group through engine.commit_group ({CLIP_GROUP_LIMIT})")
+
     def commit_after_current(self):
         if self.pending:
+            self._not_alone()
             self.engine.C.commit(self.slot, True, self.seq)
             self._pending = False
         return self
@@ -248,7 +258,7 @@ class NativeAllReduce:
                       name: str = "bucket", prepacked=None, layout=None, on_producer: bool = False,
                       opt: str = "sgd", var: torch.Tensor | None = None, betas=(0.9, 0.999), eps: float = 1e-8,
                       step: int | None = None, trust_ratio: bool = False, n_adapt: int | None = None,
-                      trust_out: torch.Tensor | None = None) -> NativeHandle:
+                      trust_out: torch.Tensor | None = None, clip: torch.Tensor | None = None) -> NativeHandle:
         """``opt="adamw"``: AdamW instead of SGD, ``mom`` / ``var`` the first / second moment planes (both required),
         ``step`` the bucket's 1-based update count (as :meth:`CompressedAllReduce.allreduce_sgd`). ``trust_ratio`` /
         ``n_adapt`` / ``trust_out``: the layer-wise trust ratio (LAMB), as there; refused with the sharded update, a
@@ -257,8 +267,11 @@ class NativeAllReduce:
         (from :meth:`prepack_target`); the engine encodes the rest and skips its pack pass. ``layout=(shard,
         chunks)``: an explicit chunked mesh layout (shard elements x world x chunks). ``on_producer``: run the request on the
         current (producer) stream instead of the engine's comm stream — the last request of a backward, which has
-        nothing left to overlap with (saves two cross-stream hand-offs on the critical path)."""
+        nothing left to overlap with (saves two cross-stream hand-offs on the critical path). ``clip`` (four f32 device
+        words, ``defer=True`` required): the request joins the clip group of those words and commits through
+        :meth:`commit_group` (as :meth:`CompressedAllReduce.allreduce_sgd`); refused where the trust ratio is."""
         n_valid = int(n_valid if n_valid is not None else master.numel())
+        clip_request(clip, defer, self.device)
         scalars = adamw_request(opt, mom, var, lr=lr, weight_decay=weight_decay, momentum=momentum,
                                 nesterov=nesterov, betas=betas, eps=eps, step=step, trust_ratio=trust_ratio,
                                 n_adapt=n_adapt, n_valid=n_valid)
@@ -278,15 +291,53 @@ class NativeAllReduce:
             okw = dict(opt=1, var=var.view(-1), adamw=a.kernel_args(), lamb=scalars.kernel_args(),
                        n_adapt=-1 if n_adapt is None else int(n_adapt),
                        trust_out=None if trust_out is None else trust_out.view(-1))
+        if clip is not None:
+            if self.shard_update:
+                raise ValueError("clip: not with a sharded-update engine (each owner updates its shard before the "
+                                 "bucket is reduced)")
+            if self.compat_owner_fp32 and self.algo == "ring":
+                raise ValueError("clip: not with compat_owner_fp32")
+            if self.C.layout(n_valid, ls, lc)["chunks"] > 1:
+                raise ValueError("clip: not with a chunked layout (the chunks' epilogues run before the whole bucket "
+                                 "is reduced)")
+            okw = dict(okw, clip=clip.view(-1))
         # an immediate request (no ordering after the producer's later work) is committed by the engine itself, so
         # a chunked bucket runs its per-chunk epilogues inside the pipeline (bounded scratch)
         eng_defer = defer or update_after is not None
-        slot = self.C.submit(grad.view(-1), master.view(-1), None if lp is None else lp.view(-1),
-                             None if mom is None else mom.view(-1), n_valid, lr, grad_scale, weight_decay, momentum,
-                             nesterov, eng_defer, True, None, pre, int(pre_n), ls, lc, bool(on_producer), **okw)
+        try:
+            slot = self.C.submit(grad.view(-1), master.view(-1), None if lp is None else lp.view(-1),
+                                 None if mom is None else mom.view(-1), n_valid, lr, grad_scale, weight_decay,
+                                 momentum, nesterov, eng_defer, True, None, pre, int(pre_n), ls, lc, bool(on_producer),
+                                 **okw)
+        except RuntimeError as e:
+            if CLIP_GROUP_LIMIT in str(e):  # the slot this request needs still holds a clipped request
+                raise ValueError(f"all-reduce '{name}': {e}") from e
+            raise
         h = NativeHandle(self, slot, self.C.slot_seq(slot), name, pending=eng_defer)
+        if clip is not None:
+            h._clip = dict(words=clip.view(-1))
         self._account(n_valid)
         return h if defer else h.commit(update_after)
+
+    def commit_group(self, handles, *, max_norm: float, grad_scale: float = 1.0, update_after=None):
+        """Commit the clip group ``handles`` (as :meth:`CompressedAllReduce.commit_group`): C++ orders the epilogue
+        stream after every member's communication phase, launches the coefficient over the members' norm partials in
+        the order given, then commits each member, after everything enqueued so far on the current stream."""
+        handles = list(handles)
+        clip_group_check(handles, max_norm)
+        for h in handles:
+            if h.engine is not self:
+                raise ValueError("commit_group: a request of another engine")
+        try:
+            self.C.commit_group([h.slot for h in handles], [h.seq for h in handles], float(max_norm),
+                                float(grad_scale), True)
+        except RuntimeError as e:
+            if "commit_group:" in str(e):
+                raise ValueError(str(e)) from e
+            raise
+        for h in handles:
+            h._pending = False
+        return handles
 
     def allreduce(self, grad: torch.Tensor, out: torch.Tensor, *, n_valid: int | None = None,
                   name: str = "bucket", prepacked=None) -> NativeHandle:
