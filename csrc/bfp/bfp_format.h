@@ -549,6 +549,25 @@ void launch_wire_pack_to(int codec, int in_dtype, const void* in, const WirePtrs
 // release at the end (the owner's reduced shard goes straight into every peer's receive slot).
 void launch_wire_reduce_to(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
                            const void* local, const WirePtrs& dst, int n_dst, size_t n_s, hipStream_t stream);
+// Error feedback (residual compensation) for the two encoders of the mesh schedule, BFP codecs only. `residual` is the
+// bucket's f32 plane on this rank (16-B aligned, zeroed by the caller before the bucket's first request), updated in
+// place; ops/bfp_oracle.py ef_pack / ef_reduce define the bits.
+// Sender stage: launch_wire_pack_to over x = f32(in) + residual (one f32 add; the group exponent comes from x) with
+// residual' = x - dec(enc(x)) (one f32 subtract; dec is the decoder's real output). Shard self_shard (-1: none) is
+// encoded from `in` alone and its residual is left alone; a null destination skips its shard entirely (neither encoded
+// nor fed back). peers: the destinations are peers' receive slots (the P2P grid cap and release of
+// launch_wire_pack_to); otherwise a local buffer, the ordinary grid and no release.
+void launch_wire_pack_ef(int codec, int in_dtype, const void* in, float* residual, const WirePtrs& dst, size_t n_s,
+                         int n_shards, int self_shard, bool peers, hipStream_t stream);
+// Owner stage: launch_wire_reduce_to (local operand required) over y = (the slots' sum) + residual, the add after the
+// slot sum; residual' = y - dec(enc(y)). `residual` is the owner shard's n_s elements of the plane. Both lane layouts
+// (set_wire_reduce4), the same bits. The output goes to every non-null dst.p[i] (i < n_dst; `peers` as above) or, in
+// the second form, to the one local buffer out_wire.
+void launch_wire_reduce_ef(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
+                           const void* local, float* residual, const WirePtrs& dst, int n_dst, size_t n_s, bool peers,
+                           hipStream_t stream);
+void launch_wire_reduce_ef(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
+                           const void* local, float* residual, void* out_wire, size_t n_s, hipStream_t stream);
 // Sharded update of the owner's shard (engine shard_update mode, ZeRO-1 style): sum the N received wire shards
 // (slot self_pos replaced by the dense local operand), take the sum through the wire codec's round trip in registers
 // (exactly the values every rank would decode from the re-encoded owner shard in the unsharded schedule), apply SGD to

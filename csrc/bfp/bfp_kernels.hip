@@ -20,6 +20,8 @@
 //   trust ratio  = AdamW scaled per bucket by ||w|| / ||update|| (LAMB): no element may move before two norms over
 //                  the whole bucket exist, so three launches — wire_lamb_moments (pass 1), lamb_ratio,
 //                  wire_lamb_apply (pass 2) — with a deterministic fp64 reduction in between (no atomics).
+//   error feedback = no counterpart in the reference (what its adapter drops is gone): wire_pack_ef and wire_reduce_ef,
+//                  the mesh schedule's two encoders with a per-rank f32 residual plane beside the unchanged wire.
 #include "bfp/bfp_format.h"
 
 #include <algorithm>
@@ -251,6 +253,80 @@ __global__ void __launch_bounds__(kBlock)
     }
     for (int i = 0; i < n_dst; ++i)
       if (dst.p[i] != nullptr) L::store_bf16(reinterpret_cast<bf16_t*>(dst.p[i]), le, w);
+  }
+  if (rel >= 0) p2p_release(rel);
+}
+
+// ---------------------------------------------------------------- error feedback (bfp_oracle.ef_pack / ef_reduce)
+// Both encoders of the mesh schedule keep what they drop: the f32 residual plane of the bucket enters the encoder's
+// input with one f32 add, and x - dec(enc(x)) (one f32 subtract; dec is the decoder's real output, Lanes*::roundtrip)
+// is stored back at the same elements. A lane reads and writes only its own elements of the plane, the two kernels
+// cover disjoint shards of it, and neither uses atomics or LDS.
+
+// Sender stage: wire_pack_to_kernel's traversal (a group per lane, destination table, release mode; rel < 0: a local
+// output, no release). Shard self_shard is encoded from `in` alone and its residual is neither read nor written; a
+// null destination skips its shard entirely.
+template <typename TIN, int C>
+__global__ void __launch_bounds__(kBlock)
+    wire_pack_ef_kernel(const TIN* __restrict__ in, float* __restrict__ resid, WirePtrs dst, size_t n_s, int n_shards,
+                        int self_shard, int rel) {
+  const size_t tasks = n_s >> 4;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (int s = 0; s < n_shards; ++s) {
+    uint8_t* d = dst.p[s];
+    if (d == nullptr) continue;
+    const TIN* src = in + (size_t)s * n_s;
+    float* e = resid + (size_t)s * n_s;
+    const bool fed = s != self_shard;  // (uniform over the grid)
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
+      float v[16];
+      DenseLane16<TIN>::load16(src, t << 4, v);
+      if (fed) {
+        float r[16];
+        DenseLane16<float>::load16(e, t << 4, r);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = v[j] + r[j];
+      }
+      WireLane16<C>::store16(d, n_s, t << 4, v);
+      if (fed) {
+        float q[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) q[j] = v[j];
+        Lanes16<C>::roundtrip(q);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) q[j] = v[j] - q[j];
+        DenseLane16<float>::store16(e, t << 4, q);
+      }
+    }
+  }
+  if (rel >= 0) p2p_release(rel);
+}
+
+// Owner stage: wire_reduce_to_kernel's body with y = (the slots' sum) + residual encoded to every destination and
+// y - roundtrip(y) stored back, in either lane layout (same operations per value, so the same bits). `resid` is the
+// owner shard's part of the plane.
+template <typename L, typename TL>
+__global__ void __launch_bounds__(kBlock)
+    wire_reduce_ef_kernel(const uint8_t* __restrict__ slots, size_t slot_stride, int n_slots, int self_pos,
+                          const TL* __restrict__ local, float* __restrict__ resid, WirePtrs dst, int n_dst, size_t n_s,
+                          int rel) {
+  const size_t tasks = n_s / L::kVals;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
+    const size_t le = t * L::kVals;
+    float acc[L::kVals], e[L::kVals];
+    sum_slots<L>(slots, slot_stride, n_slots, self_pos, local, n_s, le, acc);
+    L::load_dense(resid, le, e);
+#pragma unroll
+    for (int j = 0; j < L::kVals; ++j) acc[j] = acc[j] + e[j];
+    for (int i = 0; i < n_dst; ++i)  // wave-uniform condition: every lane of a group's segment stores
+      if (dst.p[i] != nullptr) L::store_wire(dst.p[i], n_s, le, acc);
+#pragma unroll
+    for (int j = 0; j < L::kVals; ++j) e[j] = acc[j];
+    L::roundtrip(e);
+#pragma unroll
+    for (int j = 0; j < L::kVals; ++j) e[j] = acc[j] - e[j];
+    L::store_f32(resid, le, e);
   }
   if (rel >= 0) p2p_release(rel);
 }
@@ -835,6 +911,81 @@ void launch_wire_reduce_to(int codec, int local_dtype, const void* slots, size_t
                          self_pos, (const bf16_t*)local, dst, n_dst, n_s, p2p_release_mode());
   }));
   FAN_HIP_CHECK(hipGetLastError());
+}
+
+static void check_ef(int codec, const float* residual) {
+  FAN_CHECK(codec == kBfpTrunc || codec == kBfpRne, "error feedback: BFP codecs only (a raw codec drops nothing)");
+  FAN_CHECK(residual != nullptr && (reinterpret_cast<uintptr_t>(residual) & 15) == 0,
+            "error feedback: a 16-B aligned f32 residual plane");
+}
+
+void launch_wire_pack_ef(int codec, int in_dtype, const void* in, float* residual, const WirePtrs& dst, size_t n_s,
+                         int n_shards, int self_shard, bool peers, hipStream_t stream) {
+  check_ns(n_s);
+  check_ef(codec, residual);
+  FAN_CHECK(n_shards <= kMaxPeers, "pack_ef: at most 16 destinations");
+  if (n_s == 0 || n_shards == 0) return;
+  const int cap = peers ? std::min(wire_max_blocks(), p2p_grid_cap()) : wire_max_blocks();
+  const int rel = peers ? p2p_release_mode() : -1;
+  const int grid = stream_grid(n_s / 16, kBlock, cap);
+#define FAN_PACK_EF(C)                                                                                              \
+  do {                                                                                                              \
+    if (in_dtype == kF32)                                                                                           \
+      hipLaunchKernelGGL((wire_pack_ef_kernel<float, C>), grid, kBlock, 0, stream, (const float*)in, residual, dst, \
+                         n_s, n_shards, self_shard, rel);                                                           \
+    else                                                                                                            \
+      hipLaunchKernelGGL((wire_pack_ef_kernel<bf16_t, C>), grid, kBlock, 0, stream, (const bf16_t*)in, residual,    \
+                         dst, n_s, n_shards, self_shard, rel);                                                      \
+  } while (0)
+  if (codec == kBfpTrunc) FAN_PACK_EF(kBfpTrunc);
+  else FAN_PACK_EF(kBfpRne);
+#undef FAN_PACK_EF
+  FAN_HIP_CHECK(hipGetLastError());
+}
+
+template <int C>
+static void reduce_ef_dispatch(int local_dtype, const uint8_t* sl, size_t slot_stride, int n_slots, int self_pos,
+                               const void* local, float* residual, const WirePtrs& dst, int n_dst, size_t n_s, int cap,
+                               int rel, hipStream_t stream) {
+  with_lanes<C>(n_slots, n_s, cap, [&](auto lanes, int grid) {
+    using L = decltype(lanes);
+    if (local_dtype == kF32)
+      hipLaunchKernelGGL((wire_reduce_ef_kernel<L, float>), grid, kBlock, 0, stream, sl, slot_stride, n_slots, self_pos,
+                         (const float*)local, residual, dst, n_dst, n_s, rel);
+    else
+      hipLaunchKernelGGL((wire_reduce_ef_kernel<L, bf16_t>), grid, kBlock, 0, stream, sl, slot_stride, n_slots,
+                         self_pos, (const bf16_t*)local, residual, dst, n_dst, n_s, rel);
+  });
+}
+
+void launch_wire_reduce_ef(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
+                           const void* local, float* residual, const WirePtrs& dst, int n_dst, size_t n_s, bool peers,
+                           hipStream_t stream) {
+  check_ns(n_s);
+  check_ef(codec, residual);
+  FAN_CHECK(n_dst >= 1 && n_dst <= kMaxPeers && local != nullptr,
+            "reduce_ef: local operand and 1 to 16 destinations");
+  FAN_CHECK(self_pos >= 0 && self_pos < n_slots, "reduce_ef: self_pos names the slot the local operand stands for");
+  if (n_s == 0) return;
+  const int cap = peers ? std::min(wire_max_blocks(), p2p_grid_cap()) : wire_max_blocks();
+  const int rel = peers ? p2p_release_mode() : -1;
+  const uint8_t* sl = (const uint8_t*)slots;
+  if (codec == kBfpTrunc)
+    reduce_ef_dispatch<kBfpTrunc>(local_dtype, sl, slot_stride, n_slots, self_pos, local, residual, dst, n_dst, n_s,
+                                  cap, rel, stream);
+  else
+    reduce_ef_dispatch<kBfpRne>(local_dtype, sl, slot_stride, n_slots, self_pos, local, residual, dst, n_dst, n_s, cap,
+                                rel, stream);
+  FAN_HIP_CHECK(hipGetLastError());
+}
+
+void launch_wire_reduce_ef(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
+                           const void* local, float* residual, void* out_wire, size_t n_s, hipStream_t stream) {
+  WirePtrs dst{};
+  dst.p[0] = (uint8_t*)out_wire;
+  FAN_CHECK(out_wire != nullptr, "reduce_ef needs an output");
+  launch_wire_reduce_ef(codec, local_dtype, slots, slot_stride, n_slots, self_pos, local, residual, dst, 1, n_s, false,
+                        stream);
 }
 
 static std::atomic<int>& reduce4_flag() {

@@ -251,7 +251,8 @@ void register_engine(pybind11::module_& m) {
               c10::optional<at::Tensor> prepacked, int64_t prepacked_elems, int64_t layout_shard,
               int64_t layout_chunks, bool on_producer, int64_t opt, c10::optional<at::Tensor> var,
               c10::optional<std::vector<double>> adamw, c10::optional<std::vector<double>> lamb, int64_t n_adapt,
-              c10::optional<at::Tensor> trust_out, c10::optional<at::Tensor> clip) {
+              c10::optional<at::Tensor> trust_out, c10::optional<at::Tensor> clip,
+              c10::optional<at::Tensor> residual) {
              FAN_T_CUDA_CONTIG(grad);
              TORCH_CHECK(grad.scalar_type() == at::kFloat || grad.scalar_type() == at::kBFloat16,
                          "gradients must be f32 or bf16");
@@ -331,6 +332,13 @@ void register_engine(pybind11::module_& m) {
                TORCH_CHECK(clip->scalar_type() == at::kFloat && clip->numel() >= 4, "clip: f32[4]");
                req.clip_words = clip->data_ptr<float>();
              }
+             if (residual && residual->defined()) {  // error feedback: the bucket's f32 residual plane
+               FAN_T_CUDA_CONTIG(*residual);
+               TORCH_CHECK(residual->scalar_type() == at::kFloat && residual->numel() >= L.n_pad &&
+                               residual->device() == grad.device(),
+                           "residual: f32[n_pad = ", L.n_pad, "] on the gradient's device");
+               req.residual = residual->data_ptr<float>();
+             }
              return e.submit(req, fan_stream());
            },
            py::arg("grad"), py::arg("master"), py::arg("lp") = py::none(), py::arg("mom") = py::none(),
@@ -340,7 +348,7 @@ void register_engine(pybind11::module_& m) {
            py::arg("prepacked_elems") = 0, py::arg("layout_shard") = 0, py::arg("layout_chunks") = 0,
            py::arg("on_producer") = false, py::arg("opt") = 0, py::arg("var") = py::none(),
            py::arg("adamw") = py::none(), py::arg("lamb") = py::none(), py::arg("n_adapt") = -1,
-           py::arg("trust_out") = py::none(), py::arg("clip") = py::none(),
+           py::arg("trust_out") = py::none(), py::arg("clip") = py::none(), py::arg("residual") = py::none(),
            py::call_guard<py::gil_scoped_release>())
       .def("prepack_shape", [](AllReduceEngine& e, int64_t n) {
         const auto s = e.prepack_shape(n);

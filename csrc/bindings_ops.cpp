@@ -418,6 +418,62 @@ void col_sum(const at::Tensor& x, at::Tensor& out, double scale, bool accumulate
                  workspace.data_ptr<float>(), fan_stream());
 }
 
+// The error-feedback wire ops (bfp_format.h launch_wire_pack_ef / launch_wire_reduce_ef). Every destination is one wire
+// shard's uint8 buffer, 16-B aligned; a None entry is a null destination.
+float* ef_plane(at::Tensor& residual, int64_t need) {
+  FAN_T_CUDA_CONTIG(residual);
+  TORCH_CHECK(residual.scalar_type() == at::kFloat && residual.numel() >= need, "residual: f32[", need, "]");
+  return residual.data_ptr<float>();
+}
+
+WirePtrs ef_dsts(const std::vector<c10::optional<at::Tensor>>& dsts, size_t sb, const at::Tensor& ref) {
+  TORCH_CHECK(dsts.size() <= (size_t)kMaxPeers, "at most 16 destinations");
+  WirePtrs to{};
+  for (size_t i = 0; i < dsts.size(); ++i) {
+    if (!dsts[i] || !dsts[i]->defined()) continue;
+    const at::Tensor& d = *dsts[i];
+    TORCH_CHECK(d.is_cuda() && d.is_contiguous() && d.device() == ref.device() && d.scalar_type() == at::kByte &&
+                    (size_t)d.numel() >= sb && (reinterpret_cast<uintptr_t>(d.data_ptr()) & 15) == 0,
+                "destination ", i, ": 16-B aligned uint8 buffer of one wire shard on the input's device");
+    to.p[i] = d.data_ptr<uint8_t>();
+  }
+  return to;
+}
+
+void wire_pack_ef(const at::Tensor& x, at::Tensor& residual, const std::vector<c10::optional<at::Tensor>>& dsts,
+                  int64_t shard_elems, int64_t codec, int64_t self_shard) {
+  FAN_T_CUDA_CONTIG(x);
+  TORCH_CHECK(codec == kBfpTrunc || codec == kBfpRne, "error feedback: BFP codecs only");
+  TORCH_CHECK(shard_elems > 0 && shard_elems % 256 == 0, "shard_elems must be a positive multiple of 256");
+  TORCH_CHECK(x.numel() == shard_elems * (int64_t)dsts.size(), "one destination per shard");
+  TORCH_CHECK(residual.device() == x.device(), "residual: on the gradient's device");
+  float* e = ef_plane(residual, x.numel());
+  const WirePtrs to = ef_dsts(dsts, wire_shard_bytes((int)codec, (size_t)shard_elems), x);
+  launch_wire_pack_ef((int)codec, dcode(x), x.data_ptr(), e, to, (size_t)shard_elems, (int)dsts.size(),
+                      (int)self_shard, false, fan_stream());
+}
+
+void wire_reduce_ef(const at::Tensor& slots, int64_t n_slots, int64_t self_pos, const at::Tensor& local,
+                    at::Tensor& residual, const std::vector<c10::optional<at::Tensor>>& dsts, int64_t shard_elems,
+                    int64_t codec) {
+  FAN_T_CUDA_CONTIG(slots);
+  FAN_T_CUDA_CONTIG(local);
+  TORCH_CHECK(codec == kBfpTrunc || codec == kBfpRne, "error feedback: BFP codecs only");
+  TORCH_CHECK(shard_elems > 0 && shard_elems % 256 == 0, "shard_elems must be a positive multiple of 256");
+  TORCH_CHECK(n_slots >= 1 && self_pos >= 0 && self_pos < n_slots, "self_pos names one of the n_slots slots");
+  const size_t sb = wire_shard_bytes((int)codec, (size_t)shard_elems);
+  // only slots other than self_pos are read (self_pos is replaced by the dense local operand)
+  const int64_t last_read = self_pos == n_slots - 1 ? n_slots - 2 : n_slots - 1;
+  TORCH_CHECK((size_t)slots.numel() * slots.element_size() >= sb * (size_t)(last_read + 1), "slots buffer too small");
+  TORCH_CHECK(local.numel() >= shard_elems, "local operand too small");
+  TORCH_CHECK(residual.device() == local.device() && slots.device() == local.device(), "one device");
+  TORCH_CHECK(!dsts.empty(), "reduce_ef needs an output");
+  float* e = ef_plane(residual, shard_elems);
+  const WirePtrs to = ef_dsts(dsts, sb, local);
+  launch_wire_reduce_ef((int)codec, dcode(local), slots.data_ptr(), sb, (int)n_slots, (int)self_pos, local.data_ptr(),
+                        e, to, (int)dsts.size(), (size_t)shard_elems, false, fan_stream());
+}
+
 }  // namespace
 
 void register_gemm(pybind11::module_& m) {
@@ -507,6 +563,12 @@ void register_nn(pybind11::module_& m) {
         "softmax + cross-entropy over the classifier GEMM's unreduced split-K slabs (+ bias; logits written)");
   m.def("col_sum", &col_sum, "bias-gradient column sum");
   m.def("col_sum_workspace_floats", [](int64_t M, int64_t N) { return (int64_t)col_sum_workspace_floats((int)M, (int)N); });
+  m.def("wire_pack_ef", &wire_pack_ef, "wire_pack with error feedback: encode x + residual per shard, keep the rest",
+        pybind11::arg("x"), pybind11::arg("residual"), pybind11::arg("dsts"), pybind11::arg("shard_elems"),
+        pybind11::arg("codec"), pybind11::arg("self_shard") = -1);
+  m.def("wire_reduce_ef", &wire_reduce_ef, "wire_reduce with error feedback: encode sum + residual, keep the rest",
+        pybind11::arg("slots"), pybind11::arg("n_slots"), pybind11::arg("self_pos"), pybind11::arg("local"),
+        pybind11::arg("residual"), pybind11::arg("dsts"), pybind11::arg("shard_elems"), pybind11::arg("codec"));
 }
 
 void register_planner(pybind11::module_& m) {

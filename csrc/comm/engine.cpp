@@ -359,6 +359,16 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const Eng
   const size_t sb = wire_shard_bytes(c, s);
   const uint8_t* g = reinterpret_cast<const uint8_t*>(req.grad);
   hipStream_t st = cur_.run;
+  // Error feedback: req.residual (submit(): mesh, a BFP codec, no prepacked input, one chunk, not sharded) is read and
+  // written only by the kernels launched here and in run_mesh_direct, all on `st`, the stream of this request's
+  // communication phase; the sender stage writes every shard of the plane but r, the owner stage shard r. Why step
+  // t + 1's pack sees step t's owner-stage store: both run on the comm stream, in its order — or one of them on the
+  // producer stream (an on_producer request, a backward's last), and SlotTable::begin orders the two streams in both
+  // directions: a comm-stream request waits for `ready`, recorded on the producer stream after everything enqueued
+  // there, the previous step's on-producer communication phase included; an on-producer request makes the producer
+  // stream wait for everything on the comm stream so far. Inline engines run every request in the producer stream's
+  // order. A caller that moves a bucket between producer streams orders them itself, as for the gradient buffer.
+  float* ef = req.residual;
   if (req.prepacked) {  // encode what the producer did not (bias gradient + padding)
     launch_wire_pack_range(c, gdt, req.grad, const_cast<uint8_t*>(req.prepacked), (size_t)s,
                            (size_t)req.prepacked_elems, (size_t)L.n_pad, st);
@@ -367,7 +377,8 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const Eng
     // the producer's encoding IS the (single-rank) result: no reduce pass
     if (req.prepacked) return {make_epilogue(req, req.prepacked, s, 1, 0, s)};
     uint8_t* S = epi_scratch("mesh_S" + std::to_string(sb), sb);
-    launch_wire_reduce(c, gdt, S, sb, 1, 0, g, S, nullptr, (size_t)s, st);
+    if (ef) launch_wire_reduce_ef(c, gdt, S, sb, 1, 0, g, ef, S, (size_t)s, st);  // one rank: the owner stage alone
+    else launch_wire_reduce(c, gdt, S, sb, 1, 0, g, S, nullptr, (size_t)s, st);
     return {make_epilogue(req, S, s, 1, 0, s)};
   }
   if (L.chunks > 1) return run_mesh_chunked(L, req);
@@ -377,7 +388,14 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const Eng
   if (!zero_copy(c, gdt) && !req.prepacked) {
     RoctxRange rr("fan/mesh/pack");
     uint8_t* Pb = scratch("mesh_P" + std::to_string(sb * N), sb * N, st);
-    launch_wire_pack(c, gdt, g, Pb, (size_t)s, N, st);
+    if (ef) {
+      // (shard r's row is the plain encoding of g, as without feedback: the owner reduce reads g itself)
+      WirePtrs to{};
+      for (int q = 0; q < N; ++q) to.p[q] = Pb + (size_t)q * sb;
+      launch_wire_pack_ef(c, gdt, g, ef, to, (size_t)s, N, r, false, st);
+    } else {
+      launch_wire_pack(c, gdt, g, Pb, (size_t)s, N, st);
+    }
     P = Pb;
   }
   mark(kTpPacked);
@@ -417,7 +435,9 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const Eng
   {
     RoctxRange rr("fan/mesh/reduce");
     // (1-rank group: the reduced shard is the gathered bucket, so the reduce writes the epilogue's buffer directly)
-    launch_wire_reduce(c, gdt, R, sb, N, r, g + (size_t)r * s * esize(gdt), ident ? G : S, nullptr, (size_t)s, st);
+    const uint8_t* own = g + (size_t)r * s * esize(gdt);
+    if (ef) launch_wire_reduce_ef(c, gdt, R, sb, N, r, own, ef + (size_t)r * s, ident ? G : S, (size_t)s, st);
+    else launch_wire_reduce(c, gdt, R, sb, N, r, own, ident ? G : S, nullptr, (size_t)s, st);
   }
   mark(kTpReduced);
   if (!ident) {
@@ -502,6 +522,8 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineL
       else if (raw) segs.push_back({g + (size_t)q * s * esize(gdt), to.p[q], sb});
     }
     if (req.prepacked || raw) d->move(segs, st);
+    // error feedback (ordering: run_mesh): to.p[r] is null, so shard r is neither encoded nor fed back here
+    else if (req.residual) launch_wire_pack_ef(c, gdt, g, req.residual, to, (size_t)s, N, r, true, st);
     else launch_wire_pack_to(c, gdt, g, to, (size_t)s, N, st);
     tag_sent(r1, "mesh_pack", sb);
   }
@@ -548,8 +570,12 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineL
     RoctxRange rr("fan/mesh/direct_reduce");
     WirePtrs out{};
     for (int q = 0; q < N; ++q) out.p[q] = d->dst(r2, q);  // q == r: this rank's own copy (its own slot)
-    launch_wire_reduce_to(c, gdt, d->src_base(r1), d->src_stride(), N, r, g + (size_t)r * s * esize(gdt), out, N,
-                          (size_t)s, st);
+    const uint8_t* own = g + (size_t)r * s * esize(gdt);
+    if (req.residual)
+      launch_wire_reduce_ef(c, gdt, d->src_base(r1), d->src_stride(), N, r, own, req.residual + (size_t)r * s, out, N,
+                            (size_t)s, true, st);
+    else
+      launch_wire_reduce_to(c, gdt, d->src_base(r1), d->src_stride(), N, r, own, out, N, (size_t)s, st);
     d->release(r1, st);
     tag_sent(r2, "mesh_reduce", sb);
   }
@@ -1078,6 +1104,19 @@ int AllReduceEngine::submit(const EngineRequest& req, hipStream_t producer) {
     FAN_CHECK(layout(req.n_valid, req.layout_shard, req.layout_chunks).chunks <= 1,
               "clip: not with a chunked layout (layout_chunks > 1, or a bucket above chunk_elems)");
     FAN_CHECK(!(cfg_.compat_owner_fp32 && cfg_.algo == 1), "clip: not with the ring's compat_owner_fp32");
+  }
+  if (req.residual) {
+    // Error feedback lives in the mesh schedule's two encoders (refused before the request takes a slot).
+    FAN_CHECK(cfg_.codec != kRawF32, "error feedback: nothing to feed back with the raw codec (raw_f32 drops nothing)");
+    FAN_CHECK(cfg_.codec == kBfpTrunc || cfg_.codec == kBfpRne, "error feedback: raw_bf16 is not supported yet (BFP "
+                                                                "codecs only)");
+    FAN_CHECK(req.prepacked == nullptr, "error feedback: not with prepacked input (the GEMM's encoding carries no "
+                                        "residual)");
+    FAN_CHECK(cfg_.algo == 0, "error feedback: mesh schedule only (the ring schedule is not supported yet)");
+    FAN_CHECK(layout(req.n_valid, req.layout_shard, req.layout_chunks).chunks <= 1,
+              "error feedback: not with a chunked layout (layout_chunks > 1, or a bucket above chunk_elems)");
+    FAN_CHECK(!sharded(req), "error feedback: not with the sharded update (shard_update)");
+    FAN_CHECK(world_ <= kMaxPeers, "error feedback: at most 16 ranks (one destination per shard)");
   }
   {
     // the slot this request takes still holds a clipped request: its forced commit would update with a coefficient

@@ -170,6 +170,12 @@ struct EngineRequest {
   // with the norm pass over its gathered wire, and commit_group() — never commit() — enqueues its update, which
   // scales grad_scale by words[0].
   const float* clip_words = nullptr;
+  // error feedback (mesh, BFP codecs): the bucket's f32 residual plane on this rank, layout().n_pad elements, zeroed by
+  // the caller before the bucket's first request. Non-null: the sender's pack and the owner's re-encode run their
+  // error-fed forms (bfp_format.h launch_wire_pack_ef / launch_wire_reduce_ef), which update it in place; the gathered
+  // wire keeps its format, so every epilogue runs unchanged. Refused with prepacked input, the ring schedule, chunked
+  // layouts, the sharded update and more than kMaxPeers ranks.
+  float* residual = nullptr;
   float* out_sum = nullptr;
   const uint8_t* prepacked = nullptr;
   int64_t prepacked_elems = 0;

@@ -117,7 +117,9 @@ def run(argv=None, out=sys.stdout):
     trainer = DataParallelTrainer(model, engine, lr=cfg.lr, weight_decay=cfg.weight_decay, momentum=cfg.momentum,
                                   loss_scale=cfg.loss_scale, profile=cfg.profile, optimizer=cfg.optimizer,
                                   betas=(cfg.beta1, cfg.beta2), eps=cfg.eps, trust_ratio=cfg.trust_ratio,
-                                  max_grad_norm=cfg.clip_grad_norm if cfg.clip_grad_norm > 0 else None)
+                                  max_grad_norm=cfg.clip_grad_norm if cfg.clip_grad_norm > 0 else None,
+                                  error_feedback=cfg.error_feedback,
+                                  error_feedback_codec=f"bfp_{cfg.rounding}")
     trainer.opt_step = opt_step
     x, y = make_data(mb, sizes[0], sizes[-1], rank, cfg.seed, device, dtype)
     threads = int(os.environ.get("OMP_NUM_THREADS", "1"))
@@ -189,7 +191,7 @@ def run(argv=None, out=sys.stdout):
                         meta={"bn": a.bn, "bk": a.bk, "bc": a.bc, "world": world}, optimizer=cfg.optimizer,
                         opt_step=trainer.opt_step)
     D.cleanup()
-    return {"loss": loss, "s_per_iter": total / max(cfg.iters, 1), "model": model}
+    return {"loss": loss, "s_per_iter": total / max(cfg.iters, 1), "model": model, "trainer": trainer}
 
 
 def main():

@@ -41,6 +41,7 @@ class TrainConfig:
     optimizer: str = "sgd"         # sgd | adamw
     trust_ratio: bool = False      # adamw: layer-wise trust ratio (LAMB)
     clip_grad_norm: float = 0.0    # > 0: clip the reduced gradient of all layers to this 2-norm (0: off)
+    error_feedback: bool = False   # BFP mesh: each encoder keeps what it drops and adds it to the next step's input
     beta1: float = 0.9
     beta2: float = 0.999
     eps: float = 1e-8
@@ -80,6 +81,11 @@ def add_named_flags(ap: argparse.ArgumentParser):
     ap.add_argument("--clip-grad-norm", type=float, default=d.clip_grad_norm,
                     help="clip the step's reduced gradient (all layers, one vector) to this 2-norm (0: off; at most 8 "
                          "layers)")
+    ap.add_argument("--error-feedback", action="store_true",
+                    help="compressed mesh all-reduce (BFP codecs): every encoder keeps what it drops in a per-rank f32 "
+                         "residual plane per layer and adds it to the next step's input; the engine then packs the "
+                         "gradients itself (no GEMM-fused encode); --compress local takes the one-slot round trip "
+                         "of the --rounding codec. The planes are not checkpointed: --resume restarts them at zero")
     ap.add_argument("--beta1", type=float, default=d.beta1, help="AdamW first-moment decay")
     ap.add_argument("--beta2", type=float, default=d.beta2, help="AdamW second-moment decay")
     ap.add_argument("--eps", type=float, default=d.eps, help="AdamW denominator term")

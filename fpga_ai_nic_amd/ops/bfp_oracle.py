@@ -167,6 +167,48 @@ def reduce_slots(slots, local=None, self_pos: int = -1, codec="bfp_rne", shard_e
     return acc
 
 
+# --------------------------------------------------------------------------- error feedback
+def _ef_codec(codec) -> int:
+    c = codec_id(codec)
+    if c not in (0, 1):
+        raise ValueError(f"error feedback: BFP codecs only, got {CODEC_NAMES.get(c, c)!r} (a raw codec drops nothing)")
+    return c
+
+
+def ef_pack(g: np.ndarray, e: np.ndarray, shard_elems: int, codec="bfp_rne", self_shard: int = -1):
+    """Sender stage of the error-fed mesh all-reduce over a bucket of shards of ``shard_elems`` elements: every shard
+    but ``self_shard`` is encoded from ``x = f32(g) + e`` (one f32 add, the group exponent taken from x) and keeps
+    ``e' = x - dec(enc(x))`` (one f32 subtract, ``dec`` the decoder's real output); shard ``self_shard`` (-1: none) is
+    encoded from g alone and its slice of e is left as it is. Returns (wire uint8, e' float32); e is not modified."""
+    c = _ef_codec(codec)
+    g = np.ascontiguousarray(g, dtype=np.float32).reshape(-1)
+    e2 = np.array(e, dtype=np.float32).reshape(-1)
+    assert g.size % shard_elems == 0 and shard_elems % 256 == 0 and e2.size >= g.size
+    out = []
+    for q in range(g.size // shard_elems):
+        sl = slice(q * shard_elems, (q + 1) * shard_elems)
+        if q == self_shard:
+            out.append(pack(g[sl], shard_elems, c))
+            continue
+        with np.errstate(over="ignore", invalid="ignore"):
+            x = (g[sl] + e2[sl]).astype(np.float32)
+            out.append(pack(x, shard_elems, c))
+            e2[sl] = (x - quantize(x, c)).astype(np.float32)
+    return np.concatenate(out), e2
+
+
+def ef_reduce(slots, local, self_pos: int, e_shard: np.ndarray, codec="bfp_rne", shard_elems: int | None = None):
+    """Owner stage: ``acc`` = :func:`reduce_slots` (slot order, slot ``self_pos`` from the dense ``local``), then
+    ``y = acc + e_shard`` (one f32 add after the slot sum), the output wire ``enc(y)`` and
+    ``e_shard' = y - dec(enc(y))``. Returns (wire uint8, e_shard' float32)."""
+    c = _ef_codec(codec)
+    n = shard_elems
+    acc = reduce_slots(slots, local, self_pos, c, n)
+    with np.errstate(over="ignore", invalid="ignore"):
+        y = (acc + np.asarray(e_shard, np.float32).reshape(-1)[:n]).astype(np.float32)
+        return pack(y, n, c), (y - quantize(y, c)).astype(np.float32)
+
+
 def sgd(w: np.ndarray, g: np.ndarray, lr: float, grad_scale: float = 1.0, weight_decay: float = 0.0,
         momentum: float = 0.0, mom: np.ndarray | None = None, nesterov: bool = False):
     """fp32 SGD with the kernel's operation order (fma emulated in float64, then rounded)."""

@@ -83,6 +83,73 @@ def reduce(slots: torch.Tensor, n_slots: int, self_pos: int, local: torch.Tensor
         as_bytes(out_wire)[: buf.size].copy_(torch.from_numpy(buf))
 
 
+def _ef_check(residual: torch.Tensor, need: int, ref: torch.Tensor, codec) -> int:
+    c = codec_id(codec)
+    if c not in (0, 1):
+        raise ValueError(f"error feedback: BFP codecs only, got {O.CODEC_NAMES.get(c, c)!r} (a raw codec drops "
+                         f"nothing)")
+    if not (isinstance(residual, torch.Tensor) and residual.dtype == torch.float32 and residual.is_contiguous()):
+        raise ValueError("error feedback: the residual plane is a contiguous float32 tensor")
+    if residual.device != ref.device:
+        raise ValueError(f"error feedback: the residual plane lives on {residual.device}, the gradient on {ref.device}")
+    if residual.numel() < need:
+        raise ValueError(f"error feedback: the residual plane has {residual.numel()} elements, the request needs {need}")
+    return c
+
+
+def pack_ef(x: torch.Tensor, residual: torch.Tensor, out, shard_elems: int, codec, self_shard: int = -1):
+    """:func:`pack` with error feedback (``bfp_oracle.ef_pack``): every shard but ``self_shard`` is encoded from
+    ``x + residual`` and the f32 ``residual`` plane (x.numel() elements, updated in place) keeps what the codec dropped;
+    shard ``self_shard`` is encoded from x alone and its residual slice is left alone. ``out``: one uint8 buffer
+    (shards back to back), or a list with one uint8 buffer per shard — a ``None`` entry skips that shard entirely
+    (neither encoded nor fed back; at most 16 shards either way on the GPU)."""
+    n_shards = x.numel() // shard_elems
+    if x.numel() % shard_elems:
+        raise ValueError("numel must be a multiple of shard_elems")
+    c = _ef_check(residual, x.numel(), x, codec)
+    sb = O.shard_bytes(c, shard_elems)
+    dsts = list(out) if isinstance(out, (list, tuple)) else [as_bytes(out)[q * sb:(q + 1) * sb] for q in range(n_shards)]
+    if len(dsts) != n_shards:
+        raise ValueError("one destination per shard")
+    if x.is_cuda:
+        _ext.require().wire_pack_ef(x, residual, dsts, int(shard_elems), c, int(self_shard))
+        return out
+    e = residual.view(-1).numpy()
+    g = _np_f32(x)
+    for q, d in enumerate(dsts):
+        if d is None:
+            continue
+        sl = slice(q * shard_elems, (q + 1) * shard_elems)
+        buf, e2 = O.ef_pack(g[sl], e[sl], shard_elems, c, 0 if q == self_shard else -1)
+        e[sl] = e2
+        as_bytes(d)[:sb].copy_(torch.from_numpy(buf))
+    return out
+
+
+def reduce_ef(slots: torch.Tensor, n_slots: int, self_pos: int, local: torch.Tensor, residual: torch.Tensor,
+              out_wire, shard_elems: int, codec):
+    """:func:`reduce` to wire with error feedback (``bfp_oracle.ef_reduce``): the slots' sum (slot ``self_pos`` from the
+    dense ``local``, required) plus the f32 ``residual`` shard is encoded into ``out_wire`` — one uint8 buffer or a
+    list of them (``None`` entries skipped), each receiving the same bytes — and ``residual`` (shard_elems elements,
+    updated in place) keeps what that encode dropped."""
+    if local is None:
+        raise ValueError("reduce_ef: the dense local operand is required")
+    c = _ef_check(residual, shard_elems, local, codec)
+    dsts = list(out_wire) if isinstance(out_wire, (list, tuple)) else [out_wire]
+    if slots.is_cuda:
+        _ext.require().wire_reduce_ef(slots, int(n_slots), int(self_pos), local, residual, dsts, int(shard_elems), c)
+        return
+    sb = O.shard_bytes(c, shard_elems)
+    raw = _np_u8(slots)
+    slot_list = [raw[r * sb:(r + 1) * sb] for r in range(n_slots)]
+    e = residual.view(-1).numpy()
+    buf, e2 = O.ef_reduce(slot_list, _np_f32(local), self_pos, e[:shard_elems], c, shard_elems)
+    e[:shard_elems] = e2
+    for d in dsts:
+        if d is not None:
+            as_bytes(d)[:sb].copy_(torch.from_numpy(buf))
+
+
 def sgd(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Tensor, *, codec,
         lp: torch.Tensor | None = None, mom: torch.Tensor | None = None, lr: float, grad_scale: float = 1.0,
         weight_decay: float = 0.0, momentum: float = 0.0, nesterov: bool = False, n_valid: int | None = None,

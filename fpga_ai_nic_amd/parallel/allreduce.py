@@ -109,6 +109,42 @@ def clip_group_check(handles, max_norm):
     return words
 
 
+MAX_PEERS = 16  # csrc/bfp/bfp_format.h kMaxPeers: the destination table of the kernels that store per shard
+
+
+def residual_request(residual, L, *, codec_id, algo, world, device, prepacked=False, sharded=False):
+    """Validate one request's ``residual=`` plane (error feedback: the f32 plane of ``L.n_pad`` elements that keeps
+    what this rank's encoders dropped, zeroed by the caller before the bucket's first request and updated in place by
+    every request). Returns the flat plane, or None without one."""
+    if residual is None:
+        return None
+    if codec_id == 2:
+        raise ValueError("error feedback: nothing to feed back with the raw codec (raw_f32 drops nothing)")
+    if codec_id == 3:
+        raise ValueError("error feedback: raw_bf16 is not supported yet (BFP codecs only)")
+    if prepacked:
+        raise ValueError("error feedback: not with prepacked input (the GEMM's encoding carries no residual)")
+    if algo != "mesh":
+        raise ValueError("error feedback: mesh schedule only (the ring schedule is not supported yet)")
+    if L.chunks > 1:
+        raise ValueError("error feedback: not with a chunked layout")
+    if sharded:
+        raise ValueError("error feedback: not with a sharded-update engine")
+    if world > MAX_PEERS:
+        raise ValueError(f"error feedback: at most {MAX_PEERS} ranks (one destination per shard), got {world}")
+    if not (isinstance(residual, torch.Tensor) and residual.dtype == torch.float32):
+        raise ValueError("error feedback: the residual plane is a float32 tensor (whatever the gradient's dtype)")
+    if not residual.is_contiguous():
+        raise ValueError("error feedback: the residual plane must be contiguous")
+    if residual.device.type != torch.device(device).type or (
+            residual.device.type == "cuda" and torch.device(device).index not in (None, residual.device.index)):
+        raise ValueError(f"error feedback: the residual plane lives on {residual.device}, the engine runs on {device}")
+    if residual.numel() < L.n_pad:
+        raise ValueError(f"error feedback: the residual plane has {residual.numel()} elements; the layout needs "
+                         f"{L.n_pad} (engine.layout(n).n_pad)")
+    return residual.view(-1)
+
+
 def adamw_request(opt, mom, var, *, lr, weight_decay, momentum, nesterov, betas, eps, step, trust_ratio=False,
                   n_adapt=None, n_valid=None):
     """Validate one request's optimizer arguments; the step's ``bfp_oracle.AdamWScalars`` for ``opt="adamw"``
@@ -365,7 +401,7 @@ class CompressedAllReduce:
                       name: str = "bucket", opt: str = "sgd", var: torch.Tensor | None = None,
                       betas=(0.9, 0.999), eps: float = 1e-8, step: int | None = None, trust_ratio: bool = False,
                       n_adapt: int | None = None, trust_out: torch.Tensor | None = None,
-                      clip: torch.Tensor | None = None) -> Handle:
+                      clip: torch.Tensor | None = None, residual: torch.Tensor | None = None) -> Handle:
         """All-reduce ``grad`` (flat, padded to ``layout(n).n_pad``) and apply SGD to ``master`` (+bf16 ``lp``).
         ``opt="adamw"``: AdamW instead, ``mom`` / ``var`` the first / second moment planes (both required), ``step``
         the bucket's 1-based update count. ``trust_ratio`` (AdamW): scale the step of the bucket's first ``n_adapt``
@@ -373,7 +409,10 @@ class CompressedAllReduce:
         epilogue becomes two passes around one norm reduction, and ``trust_out`` (3 f32, optional) receives
         {lr * phi, lr, phi}. ``clip`` (four f32 words on the engine's device; ``defer=True`` required): the request
         joins the clip group of those words — its communication phase ends with the norm pass over its reduced
-        gradient, and ``commit_group`` computes the group's coefficient and commits its members."""
+        gradient, and ``commit_group`` computes the group's coefficient and commits its members. ``residual`` (f32,
+        ``layout(n).n_pad`` elements, zeroed before the bucket's first request): error feedback — this rank's encoders
+        (the sender's pack and the owner's re-encode) add it to their input and store what they dropped back into it;
+        the gathered wire keeps its format, so every epilogue runs unchanged. Mesh schedule and BFP codecs only."""
         clip_request(clip, defer, self.device)
         if clip is not None and self.compat_owner_fp32 and self.algo == "ring":
             raise ValueError("clip: not with compat_owner_fp32 (the owner's slices would be updated from another "
@@ -389,6 +428,8 @@ class CompressedAllReduce:
         n_adapt = n_valid if n_adapt is None else int(n_adapt)
         L = self.layout(n_valid)
         self._check(grad, L)
+        residual = residual_request(residual, L, codec_id=self.codec_id, algo=self.algo, world=self.world,
+                                    device=self.device)
         sgd_kw = dict(lr=lr, grad_scale=grad_scale, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov)
         tr = dict(pairs=0, regions=[])  # trust ratio: the regions pass 1 has run over, for the ratio and pass 2
         cl = None if clip is None else dict(words=clip.view(-1), partials=None, count=0, norm=True)
@@ -449,11 +490,11 @@ class CompressedAllReduce:
 
         def comm():
             if cl is not None:
-                thunks = clipped(list(self._run(L, grad, finish, owner_fp32)))
+                thunks = clipped(list(self._run(L, grad, finish, owner_fp32, residual=residual)))
                 if not lamb:
                     return thunks
             elif not lamb:
-                return self._run(L, grad, finish, owner_fp32)
+                return self._run(L, grad, finish, owner_fp32, residual=residual)
             # one partials segment per region a schedule hands to finish(): one (mesh), or one per ring
             cap = wire.lamb_partials_for(master, 1 << 40)
             tr["partials"] = self._buf(L, "lamb_partials", 16 * cap * max(1, self.rings), torch.float64, per_slot=True)
@@ -461,7 +502,7 @@ class CompressedAllReduce:
                 self._buf(L, "lamb_words", 12, torch.float32, per_slot=True)
             if cl is not None:
                 return thunks + [lamb_finish]
-            return list(self._run(L, grad, finish, owner_fp32)) + [lamb_finish]
+            return list(self._run(L, grad, finish, owner_fp32, residual=residual)) + [lamb_finish]
 
         h = self._launch(comm, name, L, defer, update_after)
         h._clip = cl
@@ -495,11 +536,14 @@ class CompressedAllReduce:
         return handles
 
     def allreduce(self, grad: torch.Tensor, out: torch.Tensor, *, n_valid: int | None = None,
-                  name: str = "bucket") -> Handle:
-        """Sum-only all-reduce: decoded result written to ``out`` (f32 or bf16, same padded length)."""
+                  name: str = "bucket", residual: torch.Tensor | None = None) -> Handle:
+        """Sum-only all-reduce: decoded result written to ``out`` (f32 or bf16, same padded length). ``residual``: the
+        bucket's error-feedback plane, as :meth:`allreduce_sgd`."""
         n_valid = int(n_valid if n_valid is not None else grad.numel())
         L = self.layout(n_valid)
         self._check(grad, L)
+        residual = residual_request(residual, L, codec_id=self.codec_id, algo=self.algo, world=self.world,
+                                    device=self.device)
 
         def finish(G, shard, n_shards, off, length, skip=(-1, 0)):
             wire.unpack(G, out.view(-1)[off:off + length], shard, self.codec_id)
@@ -507,8 +551,8 @@ class CompressedAllReduce:
         def owner_fp32(buf, off, length):
             pass
 
-        return self._launch(lambda: self._run(L, grad, finish, owner_fp32, allow_compat=False), name, L, False,
-                            None)
+        return self._launch(lambda: self._run(L, grad, finish, owner_fp32, allow_compat=False, residual=residual),
+                            name, L, False, None)
 
     def _check(self, grad, L):
         if grad.numel() < L.n_pad:
@@ -604,19 +648,27 @@ class CompressedAllReduce:
                 f"async_error={self.transport.async_error()!r}")
 
     # -------------------------------------------------------------------------------- execution
-    def _run(self, L, grad, finish, owner_fp32, allow_compat=True):
+    def _run(self, L, grad, finish, owner_fp32, allow_compat=True, residual=None):
         """Issue the communication phase; returns the epilogue thunks (run now or at commit)."""
         if L.algo == "mesh":
-            return self._mesh(L, grad, finish)
+            return self._mesh(L, grad, finish, residual)
         return self._ring(L, grad, finish, owner_fp32, allow_compat)
 
-    def _mesh(self, L, grad, finish):
+    def _mesh(self, L, grad, finish, residual=None):
         N, r, s, c = self.world, self.rank, L.shard, self.codec_id
         sb = wire.shard_bytes(c, s)
         g = grad.view(-1)[: L.n_pad]
+        # Error feedback: `residual` (residual_request: f32, n_pad elements, a BFP codec) is read and written here
+        # only, by the kernels of this request's communication phase on the stream it runs on — the comm stream, whose
+        # order puts step t's owner-stage store before step t + 1's pack (CPU / inline: the caller's own order). The
+        # sender stage writes every shard but r, the owner stage shard r: disjoint parts of the plane.
+        e = residual
         S = self._buf(L, "mesh_S", sb, per_slot=N == 1 and not self.force_comm)
         if N == 1 and not self.force_comm:
-            wire.reduce(S, 1, 0, g[:s], S, None, s, c)
+            if e is not None:
+                wire.reduce_ef(S, 1, 0, g[:s], e[:s], S, s, c)
+            else:
+                wire.reduce(S, 1, 0, g[:s], S, None, s, c)
             return [lambda: finish(S, s, 1, 0, s)]
         if c == 2 and g.dtype == torch.float32:
             P = wire.as_bytes(g)
@@ -624,7 +676,10 @@ class CompressedAllReduce:
             P = wire.as_bytes(g)
         else:
             P = self._buf(L, "mesh_P", sb * N)
-            wire.pack(g, P, s, c)
+            if e is not None:
+                wire.pack_ef(g, e[: L.n_pad], P, s, c, self_shard=r)
+            else:
+                wire.pack(g, P, s, c)
         cs = self._tag(P.view(N, sb)) if self.verify else None
         self.fault.maybe_corrupt("mesh_pack", P)
         R = self._buf(L, "mesh_R", sb * N)
@@ -633,7 +688,10 @@ class CompressedAllReduce:
             cs_r = torch.empty_like(cs)
             self.transport.all_to_all(cs, cs_r)
             self._verify_rows(R.view(N, sb), cs_r, list(range(N)), "mesh all_to_all")
-        wire.reduce(R, N, r, g[r * s:(r + 1) * s], S, None, s, c)
+        if e is not None:
+            wire.reduce_ef(R, N, r, g[r * s:(r + 1) * s], e[r * s:(r + 1) * s], S, s, c)
+        else:
+            wire.reduce(R, N, r, g[r * s:(r + 1) * s], S, None, s, c)
         G = self._buf(L, "mesh_G", sb * N, per_slot=True)
         self.transport.all_gather(S, G)
         if self.verify:

@@ -46,7 +46,7 @@ class RcclAllReduce(CompressedAllReduce):
         N = self.world
         return 0 if N == 1 else int(2 * (N - 1) / N * L.n_pad * 4)
 
-    def _run(self, L, grad, finish, owner_fp32, allow_compat=True):
+    def _run(self, L, grad, finish, owner_fp32, allow_compat=True, residual=None):
         g = grad.view(-1)[: L.n_pad]
         self.transport.all_reduce_(g)
         return [lambda: finish(wire.as_bytes(g), L.n_pad, 1, 0, L.n_pad)]
@@ -85,8 +85,19 @@ class DataParallelTrainer:
                  commit_at_end: bool | None = None, fused_update: bool | None = None,
                  gemm_inflight: str | None = None, wgrad_pair: bool | str | None = None, optimizer: str = "sgd",
                  betas=(0.9, 0.999), eps: float = 1e-8, trust_ratio: bool = False,
-                 max_grad_norm: float | None = None):
-        """``max_grad_norm``: clip the step's reduced gradient — every layer's, as one vector, after the all-reduce and
+                 max_grad_norm: float | None = None, error_feedback: bool = False,
+                 error_feedback_codec: str = "bfp_rne"):
+        """``error_feedback``: error feedback (residual compensation) for the compressed mesh all-reduce — every layer
+        bucket gets one zeroed f32 plane per rank (``residuals``), passed with the layer's request, in which this rank's
+        encoders keep what they dropped and from which they add it to the next step's input. ``prepack`` and hence
+        ``fused_update`` are off (the bwd-weight GEMM writes f32 and the engine packs: the GEMM's encoding carries no
+        residual). BFP codecs and the mesh schedule only; not with a sharded-update engine or a chunked layout. Without
+        an engine the local update takes the gradient through the one-slot round trip (``wire.reduce_ef``) of
+        ``error_feedback_codec`` (an engine's own codec always wins).
+        With any ``optimizer``, ``trust_ratio`` and ``max_grad_norm``. The planes are per-rank state and are not
+        checkpointed: a resumed run restarts them at zero.
+
+        ``max_grad_norm``: clip the step's reduced gradient — every layer's, as one vector, after the all-reduce and
         through the wire codec, times ``grad_scale`` — to this 2-norm (``torch.nn.utils.clip_grad_norm_``'s
         coefficient). The layers' requests form one clip group: each ends its communication phase with a norm pass
         over its gathered wire, and the step commits through ``engine.commit_group`` in the order L-1..0, whatever
@@ -158,6 +169,22 @@ class DataParallelTrainer:
                 raise ValueError("max_grad_norm: not with a sharded-update engine (each owner updates its shard before "
                                  "the bucket is reduced)")
             self.grad_norm = torch.zeros(4, dtype=torch.float32, device=model.device)
+        self.error_feedback = bool(error_feedback)
+        self.residuals = None
+        self._ef_wire = None  # the engine-less trainer's one-slot wire, per layer
+        self.ef_codec = getattr(engine, "codec", "bfp_rne") if engine is not None else error_feedback_codec
+        if self.error_feedback:
+            if wire.is_raw(self.ef_codec):
+                raise ValueError(f"error_feedback: nothing to feed back with a raw codec ({self.ef_codec}); BFP codecs "
+                                 f"only")
+            if engine is not None and getattr(engine, "algo", "mesh") != "mesh":
+                raise ValueError("error_feedback: mesh schedule only (the ring schedule is not supported yet)")
+            if bool(getattr(engine, "shard_update", False)):
+                raise ValueError("error_feedback: not with a sharded-update engine")
+            if engine is not None and any(getattr(engine.layout(l.n), "chunks", 1) > 1 for l in model.layers):
+                raise ValueError("error_feedback: not with a chunked layout (a bucket above the engine's chunk_elems)")
+            self.residuals = [torch.zeros(l.n_pad, dtype=torch.float32, device=model.device) for l in model.layers]
+            prepack = False
         self.loss_scale = loss_scale
         # gradients are of the LOCAL mean loss; the all-reduce sums over ranks -> average with 1/N
         self.grad_scale = (1.0 / self.world) if average else 1.0
@@ -221,18 +248,40 @@ class DataParallelTrainer:
             self.last_on_producer = False
 
     def _opt_kw(self, l):
-        """The optimizer arguments of layer l's request in the step being enqueued."""
-        clip = {} if self.grad_norm is None else dict(clip=self.grad_norm)
+        """The optimizer, clip-group and error-feedback arguments of layer l's request in the step being enqueued."""
+        kw = {} if self.grad_norm is None else dict(clip=self.grad_norm)
+        if self.residuals is not None:
+            kw["residual"] = self.residuals[self._index(l)]
         if self.optimizer != "adamw":
-            return clip
-        kw = dict(clip, opt="adamw", var=l.var, betas=self.betas, eps=self.eps, step=self.opt_step)
+            return kw
+        kw.update(opt="adamw", var=l.var, betas=self.betas, eps=self.eps, step=self.opt_step)
         if self.trust_ratio:
             kw.update(trust_ratio=True, n_adapt=self._n_adapt(l), trust_out=self._trust_row(l))
         return kw
 
     def _trust_row(self, l):
         """Layer l's row of ``trust_ratios`` (found by identity: buckets of equal shape compare by their tensors)."""
-        return self.trust_ratios[next(i for i, x in enumerate(self.m.layers) if x is l)]
+        return self.trust_ratios[self._index(l)]
+
+    def _index(self, l):
+        return next(i for i, x in enumerate(self.m.layers) if x is l)
+
+    def _local_src(self, l):
+        """(wire bytes, their codec) the engine-less update of layer l reads: the f32 gradient itself as raw_f32, or
+        with error feedback the one-slot wire ``_ef_local`` encoded this step."""
+        if self.residuals is None:
+            return wire.as_bytes(l.grad), "raw_f32"
+        return self._ef_wire[self._index(l)], self.ef_codec
+
+    def _ef_local(self, l):
+        """Engine-less error feedback: layer l's gradient plus its residual through the codec's round trip at one
+        slot (the owner stage alone, as a one-rank engine)."""
+        if self._ef_wire is None:
+            self._ef_wire = [torch.zeros(wire.shard_bytes(self.ef_codec, x.n_pad), dtype=torch.uint8,
+                                         device=x.grad.device) for x in self.m.layers]
+        i = self._index(l)
+        S = self._ef_wire[i]
+        wire.reduce_ef(S, 1, 0, l.grad, self.residuals[i], S, l.n_pad, self.ef_codec)
 
     def _n_adapt(self, l):
         """The adapted tensor of layer l's bucket: its weight matrix; the bias segment behind it takes ratio 1."""
@@ -246,20 +295,21 @@ class DataParallelTrainer:
         segs = []
         for i in reversed(range(self.m.L)):
             l = self.m.layers[i]
-            k = wire.sumsq(wire.as_bytes(l.grad), l.n_pad, 1, codec="raw_f32", partials=self._clip_partials[i],
-                           n_valid=l.n)
+            src, codec = self._local_src(l)
+            k = wire.sumsq(src, l.n_pad, 1, codec=codec, partials=self._clip_partials[i], n_valid=l.n)
             segs.append((self._clip_partials[i], 0, k))
         wire.clip_coef(segs, self.max_grad_norm, self.grad_scale, self.grad_norm)
 
     def _sgd_local(self, l):
         clip = self.grad_norm
+        src, codec = self._local_src(l)
         if self.trust_ratio:
             scalars = wire.O.lamb_scalars(self.lr, self.wd, self.betas[0], self.betas[1], self.eps, self.opt_step)
             if self._trust_partials is None:
                 self._trust_partials = torch.zeros(2 * wire.lamb_partials_for(l.master, 1 << 40), dtype=torch.float64,
                                                    device=l.master.device)
             words, kw = self._trust_row(l), dict(n_valid=l.n, n_adapt=self._n_adapt(l))
-            k = wire.lamb_moments(wire.as_bytes(l.grad), l.n_pad, 1, l.master, codec="raw_f32", mom=l.mom, var=l.var,
+            k = wire.lamb_moments(src, l.n_pad, 1, l.master, codec=codec, mom=l.mom, var=l.var,
                                   scalars=scalars, partials=self._trust_partials, grad_scale=self.grad_scale,
                                   clip=clip, **kw)
             wire.lamb_ratio(self._trust_partials, k, self.lr, words)
@@ -267,10 +317,10 @@ class DataParallelTrainer:
             return
         if self.optimizer == "adamw":
             scalars = wire.O.adamw_scalars(self.lr, self.wd, self.betas[0], self.betas[1], self.eps, self.opt_step)
-            wire.adamw(wire.as_bytes(l.grad), l.n_pad, 1, l.master, codec="raw_f32", lp=l.lp, mom=l.mom, var=l.var,
+            wire.adamw(src, l.n_pad, 1, l.master, codec=codec, lp=l.lp, mom=l.mom, var=l.var,
                        scalars=scalars, grad_scale=self.grad_scale, n_valid=l.n, clip=clip)
             return
-        wire.sgd(wire.as_bytes(l.grad), l.n_pad, 1, l.master, codec="raw_f32", lp=l.lp, mom=l.mom, lr=self.lr,
+        wire.sgd(src, l.n_pad, 1, l.master, codec=codec, lp=l.lp, mom=l.mom, lr=self.lr,
                  grad_scale=self.grad_scale, weight_decay=self.wd, momentum=self.momentum, nesterov=self.nesterov,
                  n_valid=l.n, clip=clip)
 
@@ -390,6 +440,8 @@ class DataParallelTrainer:
                                                           momentum=self.momentum, nesterov=self.nesterov, defer=True,
                                                           name=f"fc{i}", **kw, **self._opt_kw(l))
                             self._gemm_grid(True)
+                        elif self.residuals is not None:
+                            self._ef_local(l)
                         m.backward_data(i)
                         if h is not None:
                             clipped = self.grad_norm is not None  # (commits with its group, below)

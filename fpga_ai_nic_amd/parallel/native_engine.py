@@ -24,7 +24,7 @@ import torch
 from .. import _ext
 from ..ops import wire
 from .allreduce import (CLIP_GROUP_LIMIT, NUM_SLOTS, BucketLayout, ChecksumError, CommTimeoutError, adamw_request,
-                        clip_group_check, clip_request)
+                        clip_group_check, clip_request, residual_request)
 from .transport import NativeTransport, Transport
 
 _ALGOS = {"mesh": 0, "ring": 1}
@@ -258,7 +258,8 @@ class NativeAllReduce:
                       name: str = "bucket", prepacked=None, layout=None, on_producer: bool = False,
                       opt: str = "sgd", var: torch.Tensor | None = None, betas=(0.9, 0.999), eps: float = 1e-8,
                       step: int | None = None, trust_ratio: bool = False, n_adapt: int | None = None,
-                      trust_out: torch.Tensor | None = None, clip: torch.Tensor | None = None) -> NativeHandle:
+                      trust_out: torch.Tensor | None = None, clip: torch.Tensor | None = None,
+                      residual: torch.Tensor | None = None) -> NativeHandle:
         """``opt="adamw"``: AdamW instead of SGD, ``mom`` / ``var`` the first / second moment planes (both required),
         ``step`` the bucket's 1-based update count (as :meth:`CompressedAllReduce.allreduce_sgd`). ``trust_ratio`` /
         ``n_adapt`` / ``trust_out``: the layer-wise trust ratio (LAMB), as there; refused with the sharded update, a
@@ -269,9 +270,13 @@ class NativeAllReduce:
         current (producer) stream instead of the engine's comm stream — the last request of a backward, which has
         nothing left to overlap with (saves two cross-stream hand-offs on the critical path). ``clip`` (four f32 device
         words, ``defer=True`` required): the request joins the clip group of those words and commits through
-        :meth:`commit_group` (as :meth:`CompressedAllReduce.allreduce_sgd`); refused where the trust ratio is."""
+        :meth:`commit_group` (as :meth:`CompressedAllReduce.allreduce_sgd`); refused where the trust ratio is.
+        ``residual`` (f32, ``layout(n).n_pad`` elements, zeroed before the bucket's first request): error feedback, as
+        :meth:`CompressedAllReduce.allreduce_sgd`; mesh and BFP codecs only, not with ``prepacked``, a chunked layout
+        or the sharded update."""
         n_valid = int(n_valid if n_valid is not None else master.numel())
         clip_request(clip, defer, self.device)
+        residual = self._residual(residual, n_valid, prepacked, layout)
         scalars = adamw_request(opt, mom, var, lr=lr, weight_decay=weight_decay, momentum=momentum,
                                 nesterov=nesterov, betas=betas, eps=eps, step=step, trust_ratio=trust_ratio,
                                 n_adapt=n_adapt, n_valid=n_valid)
@@ -301,6 +306,8 @@ class NativeAllReduce:
                 raise ValueError("clip: not with a chunked layout (the chunks' epilogues run before the whole bucket "
                                  "is reduced)")
             okw = dict(okw, clip=clip.view(-1))
+        if residual is not None:
+            okw = dict(okw, residual=residual)
         # an immediate request (no ordering after the producer's later work) is committed by the engine itself, so
         # a chunked bucket runs its per-chunk epilogues inside the pipeline (bounded scratch)
         eng_defer = defer or update_after is not None
@@ -340,16 +347,28 @@ class NativeAllReduce:
         return handles
 
     def allreduce(self, grad: torch.Tensor, out: torch.Tensor, *, n_valid: int | None = None,
-                  name: str = "bucket", prepacked=None) -> NativeHandle:
-        """Sum-only all-reduce: decoded f32 result written to ``out`` (padded length)."""
+                  name: str = "bucket", prepacked=None, residual: torch.Tensor | None = None) -> NativeHandle:
+        """Sum-only all-reduce: decoded f32 result written to ``out`` (padded length). ``residual``: the bucket's
+        error-feedback plane, as :meth:`allreduce_sgd`."""
         n_valid = int(n_valid if n_valid is not None else grad.numel())
         if out.dtype != torch.float32:
             raise TypeError("native allreduce writes f32 sums")
         pre, pre_n = (None, 0) if prepacked is None else prepacked
+        residual = self._residual(residual, n_valid, prepacked, None)
+        okw = {} if residual is None else dict(residual=residual)
         slot = self.C.submit(grad.view(-1), out.view(-1), None, None, n_valid, 0.0, 1.0, 0.0, 0.0, False, False,
-                             False, out.view(-1), pre, int(pre_n))
+                             False, out.view(-1), pre, int(pre_n), **okw)
         self._account(n_valid)
         return NativeHandle(self, slot, self.C.slot_seq(slot), name, pending=False)
+
+    def _residual(self, residual, n_valid, prepacked, layout):
+        """A request's validated error-feedback plane (flat), or None."""
+        if residual is None:
+            return None
+        ls, lc = (0, 0) if layout is None else (int(layout[0]), int(layout[1]))
+        return residual_request(residual, self.layout(n_valid, ls, lc), codec_id=self.codec_id, algo=self.algo,
+                                world=self.world, device=self.device, prepacked=prepacked is not None,
+                                sharded=self.shard_update)
 
     def _account(self, n):
         self.stats["requests"] += 1

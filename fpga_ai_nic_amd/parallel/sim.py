@@ -60,3 +60,30 @@ def ring_allreduce(grads: list[np.ndarray], orders: list[list[int]], slice_elems
                 for r in range(N):
                     outs[r][lo:lo + S] = full_f32 if (owner_fp32 and r == owner and N > 1) else val
     return outs
+
+
+def mesh_allreduce_ef(grads: list[np.ndarray], residuals: list[np.ndarray], shard: int, codec="bfp_rne"):
+    """The mesh all-reduce with error feedback: rank r keeps one f32 residual plane ``residuals[r]`` of
+    ``shard * N`` elements. Sender r ships ``enc(g_r[q] + e_r[q])`` for every shard q != r and keeps what the codec
+    dropped in ``e_r[q]``; owner s sums the decoded slots in rank order (its own g_s[s] un-quantised), adds
+    ``e_s[s]`` after the sum, re-encodes, and keeps what that encode dropped in ``e_s[s]``. Returns
+    (decoded result every rank ends up with, the N new planes); with zero planes the result is
+    :func:`mesh_allreduce`'s."""
+    N = len(grads)
+    f32 = np.float32
+    new = [np.array(e, dtype=f32).reshape(-1)[: shard * N].copy() for e in residuals]
+    out = np.zeros(shard * N, f32)
+    for s in range(N):
+        sl = slice(s * shard, (s + 1) * shard)
+        acc = np.zeros(shard, f32)
+        for r in range(N):
+            v = grads[r][sl].astype(f32)
+            if r != s:
+                x = (v + new[r][sl]).astype(f32)
+                v = _enc_dec(x, codec)
+                new[r][sl] = (x - v).astype(f32)
+            acc = (acc + v).astype(f32)
+        y = (acc + new[s][sl]).astype(f32)
+        out[sl] = _enc_dec(y, codec)
+        new[s][sl] = (y - out[sl]).astype(f32)
+    return out, new
