@@ -14,6 +14,11 @@
 // Packed layout of one shard of n_s elements (n_s % 256 == 0): [int8 mant[n_s]][uint8 exp[n_s/16]]
 // (the SoA analogue of the reference's 16 mantissa flits + 1 exponent flit per 32 groups,
 // hw/bfp_adapter.sv:279-379). A multi-shard buffer is shards back to back.
+//
+// The reference's MANTISSA_SIZE / MANT_SIZE is a parameter of its encoder, decoder and adapter; kBfp4Rne is the
+// framework's rne form at 4 bits: [u8 nib[n_s/2]][u8 exp[n_s/16]], 9 bytes per 16 values, byte i of a group's 8
+// holding value 2i in bits [3:0] and value 2i+1 in bits [7:4] (two's complement). Exponent plane and shard starts
+// stay 16-B aligned (n_s % 256 == 0). The reference ships no 4-bit configuration, so there is no truncating form.
 #pragma once
 #include "common/hip_common.h"
 
@@ -24,7 +29,13 @@ enum Codec : int {
   kBfpRne = 1,    // framework default: round-to-nearest-even, exact decode q * 2^(E-133)
   kRawF32 = 2,    // uncompressed fp32 on the wire
   kRawBf16 = 3,   // uncompressed bf16 on the wire
+  kBfp4Rne = 4,   // 4-bit mantissas (two per byte), round-to-nearest-even, exact decode q * 2^(E-129)
 };
+
+// Codecs whose groups of 16 values share an exponent byte (every BFP width), and the 8-bit ones among them: the only
+// ones the GEMM wire epilogues encode (prepack, the fused update) and the 4-values-per-lane layout (Lanes4) handles.
+__host__ __device__ constexpr bool codec_shared_exp(int c) { return c == kBfpTrunc || c == kBfpRne || c == kBfp4Rne; }
+__host__ __device__ constexpr bool codec_bfp8(int c) { return c == kBfpTrunc || c == kBfpRne; }
 
 enum DType : int { kF32 = 0, kBF16 = 1 };
 
@@ -115,6 +126,7 @@ __host__ __device__ inline size_t wire_shard_bytes(int codec, size_t n_s) {
   switch (codec) {
     case kBfpTrunc:
     case kBfpRne: return n_s + n_s / 16;
+    case kBfp4Rne: return n_s / 2 + n_s / 16;
     case kRawF32: return n_s * 4;
     default: return n_s * 2;
   }
@@ -152,6 +164,36 @@ __device__ __forceinline__ float bfp_decode_rne(int32_t q, uint32_t E) {
   return E == 255u ? __uint_as_float(0x7FC00000u) : ldexpf((float)q, (int)E - 133);
 }
 
+// The 4-bit form: q = clamp(rne(x * 2^(129-E)), -7, 7), a two's-complement nibble; decode q * 2^(E-129).
+__device__ __forceinline__ int32_t bfp4_encode_rne(float x, uint32_t E) {
+  float s = rintf(ldexpf(x, 129 - (int)E));
+  s = fminf(fmaxf(s, -7.0f), 7.0f);
+  return (int32_t)s;
+}
+
+__device__ __forceinline__ float bfp4_decode_rne(int32_t q, uint32_t E) {
+  return E == 255u ? __uint_as_float(0x7FC00000u) : ldexpf((float)q, (int)E - 129);
+}
+
+// Nibble j (0..7) of a dword of mantissas, sign-extended (a shift pair).
+__device__ __forceinline__ int32_t bfp4_nibble(uint32_t w, int j) { return (int32_t)(w << (28 - 4 * j)) >> 28; }
+
+// Encode / decode of one value by codec (the 8-bit forms take and return the byte's value, the 4-bit form the nibble's).
+template <int C>
+__device__ __forceinline__ int32_t bfp_encode(float x, uint32_t E) {
+  static_assert(codec_shared_exp(C), "BFP codecs");
+  if constexpr (C == kBfpTrunc) return bfp_encode_trunc(__float_as_uint(x), E);
+  else if constexpr (C == kBfpRne) return bfp_encode_rne(x, E);
+  else return bfp4_encode_rne(x, E);
+}
+template <int C>
+__device__ __forceinline__ float bfp_decode(int32_t q, uint32_t E) {
+  static_assert(codec_shared_exp(C), "BFP codecs");
+  if constexpr (C == kBfpTrunc) return bfp_decode_trunc(q, E);
+  else if constexpr (C == kBfpRne) return bfp_decode_rne(q, E);
+  else return bfp4_decode_rne(q, E);
+}
+
 // ---------------------------------------------------------------- 8-value lane codecs
 template <int C>
 struct WireLane;
@@ -165,7 +207,7 @@ struct BfpLane {
     for (int j = 0; j < 8; ++j) {
       const uint32_t w = j < 4 ? m.x : m.y;
       const int32_t q = (int32_t)(int8_t)(uint8_t)(w >> (8 * (j & 3)));
-      v[j] = (C == kBfpTrunc) ? bfp_decode_trunc(q, E) : bfp_decode_rne(q, E);
+      v[j] = bfp_decode<C>(q, E);
     }
   }
   // Both lanes of the pair (lane, lane^1) must be active: they hold the two halves of a group.
@@ -178,7 +220,7 @@ struct BfpLane {
     uint32_t w[2] = {0u, 0u};
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const int32_t q = (C == kBfpTrunc) ? bfp_encode_trunc(__float_as_uint(v[j]), E) : bfp_encode_rne(v[j], E);
+      const int32_t q = bfp_encode<C>(v[j], E);
       w[j >> 2] |= ((uint32_t)q & 0xFFu) << (8 * (j & 3));
     }
     *reinterpret_cast<uint2*>(shard + le) = make_uint2(w[0], w[1]);
@@ -190,6 +232,32 @@ template <>
 struct WireLane<kBfpTrunc> : BfpLane<kBfpTrunc> {};
 template <>
 struct WireLane<kBfpRne> : BfpLane<kBfpRne> {};
+
+// 4-bit mantissas, shard layout [u8 nib[n_s/2]][u8 exp[n_s/16]]: a lane's 8 values are ONE dword of nibbles (value 2i
+// in bits [3:0] of byte i, value 2i+1 in bits [7:4], i.e. value j in bits [4j+3:4j] of the dword), the exponent
+// exchange of the pair is BfpLane's.
+template <>
+struct WireLane<kBfp4Rne> {
+  __device__ static __forceinline__ void load8(const uint8_t* shard, size_t n_s, size_t le, float v[8]) {
+    const uint32_t m = *reinterpret_cast<const uint32_t*>(shard + (le >> 1));
+    const uint32_t E = shard[(n_s >> 1) + (le >> 4)];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = bfp4_decode_rne(bfp4_nibble(m, j), E);
+  }
+  // Both lanes of the pair (lane, lane^1) must be active: they hold the two halves of a group.
+  __device__ static __forceinline__ void store8(uint8_t* shard, size_t n_s, size_t le, const float v[8]) {
+    uint32_t mx = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) mx = max(mx, __float_as_uint(v[j]) & 0x7FFFFFFFu);
+    mx = max(mx, (uint32_t)__shfl_xor((int)mx, 1));
+    const uint32_t E = mx >> 23;
+    uint32_t w = 0u;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w |= ((uint32_t)bfp4_encode_rne(v[j], E) & 0xFu) << (4 * j);
+    *reinterpret_cast<uint32_t*>(shard + (le >> 1)) = w;
+    if ((le & 15) == 0) shard[(n_s >> 1) + (le >> 4)] = (uint8_t)E;
+  }
+};
 
 template <>
 struct WireLane<kRawF32> {
@@ -256,7 +324,7 @@ struct BfpLane16 {
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       const int32_t q = (int32_t)(int8_t)(uint8_t)(w[j >> 2] >> (8 * (j & 3)));
-      v[j] = (C == kBfpTrunc) ? bfp_decode_trunc(q, E) : bfp_decode_rne(q, E);
+      v[j] = bfp_decode<C>(q, E);
     }
   }
   __device__ static __forceinline__ void store16(uint8_t* shard, size_t n_s, size_t le, const float v[16]) {
@@ -267,7 +335,7 @@ struct BfpLane16 {
     uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
-      const int32_t q = (C == kBfpTrunc) ? bfp_encode_trunc(__float_as_uint(v[j]), E) : bfp_encode_rne(v[j], E);
+      const int32_t q = bfp_encode<C>(v[j], E);
       w[j >> 2] |= ((uint32_t)q & 0xFFu) << (8 * (j & 3));
     }
     *reinterpret_cast<uint4*>(shard + le) = make_uint4(w[0], w[1], w[2], w[3]);
@@ -284,6 +352,34 @@ template <>
 struct WireLane16<kBfpTrunc> : BfpLane16<kBfpTrunc> {};
 template <>
 struct WireLane16<kBfpRne> : BfpLane16<kBfpRne> {};
+
+// The 4-bit group per lane: ONE 8-B load or store of nibbles per lane (adjacent lanes cover contiguous bytes), the
+// exponent plane gathered into one 16-B store by lane 16k as above.
+template <>
+struct WireLane16<kBfp4Rne> {
+  __device__ static __forceinline__ void load16(const uint8_t* shard, size_t n_s, size_t le, float v[16]) {
+    const uint2 m = *reinterpret_cast<const uint2*>(shard + (le >> 1));
+    const uint32_t E = shard[(n_s >> 1) + (le >> 4)];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = bfp4_decode_rne(bfp4_nibble(j < 8 ? m.x : m.y, j & 7), E);
+  }
+  __device__ static __forceinline__ void store16(uint8_t* shard, size_t n_s, size_t le, const float v[16]) {
+    uint32_t mx = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) mx = max(mx, __float_as_uint(v[j]) & 0x7FFFFFFFu);
+    const uint32_t E = mx >> 23;
+    uint32_t w[2] = {0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 16; ++j) w[j >> 3] |= ((uint32_t)bfp4_encode_rne(v[j], E) & 0xFu) << (4 * (j & 7));
+    *reinterpret_cast<uint2*>(shard + (le >> 1)) = make_uint2(w[0], w[1]);
+    uint32_t e4 = E | ((uint32_t)__shfl_down((int)E, 1) << 8) | ((uint32_t)__shfl_down((int)E, 2) << 16) |
+                  ((uint32_t)__shfl_down((int)E, 3) << 24);
+    const uint32_t e4b = (uint32_t)__shfl_down((int)e4, 4), e4c = (uint32_t)__shfl_down((int)e4, 8),
+                   e4d = (uint32_t)__shfl_down((int)e4, 12);
+    if ((threadIdx.x & 15) == 0)
+      *reinterpret_cast<uint4*>(shard + (n_s >> 1) + (le >> 4)) = make_uint4(e4, e4b, e4c, e4d);
+  }
+};
 
 // Dense (local) operand loads: f32 or bf16 arrays.
 template <typename T>
@@ -327,9 +423,10 @@ struct DenseLane16 {
 // The value every rank decodes after `x` is encoded in a group of shared exponent E.
 template <int C>
 __device__ __forceinline__ float bfp_roundtrip(float x, uint32_t E) {
-  const int32_t q = (C == kBfpTrunc) ? bfp_encode_trunc(__float_as_uint(x), E) : bfp_encode_rne(x, E);
-  const int32_t q8 = (int32_t)(int8_t)(uint8_t)((uint32_t)q & 0xFFu);  // the stored byte, as the decoder reads it
-  return (C == kBfpTrunc) ? bfp_decode_trunc(q8, E) : bfp_decode_rne(q8, E);
+  const int32_t q = bfp_encode<C>(x, E);
+  // the stored byte (nibble), as the decoder reads it
+  const int32_t qs = C == kBfp4Rne ? bfp4_nibble((uint32_t)q & 0xFu, 0) : (int32_t)(int8_t)(uint8_t)((uint32_t)q & 0xFFu);
+  return bfp_decode<C>(qs, E);
 }
 
 template <int C>
@@ -352,7 +449,7 @@ struct Lanes16 {
     DenseLane16<bf16_t>::store16(p, e, v);
   }
   __device__ static __forceinline__ void roundtrip(float v[16]) {
-    if constexpr (C == kBfpTrunc || C == kBfpRne) {
+    if constexpr (codec_shared_exp(C)) {
       uint32_t mx = 0;
 #pragma unroll
       for (int j = 0; j < 16; ++j) mx = max(mx, __float_as_uint(v[j]) & 0x7FFFFFFFu);
@@ -388,7 +485,7 @@ __device__ __forceinline__ uint32_t bfp_quad_exponent(const float v[4]) {
 // out of range, and they are all active at store_wire and roundtrip (bfp_quad_exponent).
 template <int C>
 struct Lanes4 {
-  static_assert(C == kBfpTrunc || C == kBfpRne, "BFP codecs");
+  static_assert(codec_bfp8(C), "8-bit BFP codecs");
   static constexpr int kVals = 4;
   __device__ static __forceinline__ void load_wire(const uint8_t* shard, size_t n_s, size_t le, float v[4]) {
     const uint32_t m = *reinterpret_cast<const uint32_t*>(shard + le);
@@ -396,7 +493,7 @@ struct Lanes4 {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int32_t q = (int32_t)(int8_t)(uint8_t)(m >> (8 * j));
-      v[j] = (C == kBfpTrunc) ? bfp_decode_trunc(q, E) : bfp_decode_rne(q, E);
+      v[j] = bfp_decode<C>(q, E);
     }
   }
   __device__ static __forceinline__ void load_dense(const float* p, size_t e, float v[4]) {
@@ -413,7 +510,7 @@ struct Lanes4 {
     uint32_t w = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int32_t q = (C == kBfpTrunc) ? bfp_encode_trunc(__float_as_uint(v[j]), E) : bfp_encode_rne(v[j], E);
+      const int32_t q = bfp_encode<C>(v[j], E);
       w |= ((uint32_t)q & 0xFFu) << (8 * j);
     }
     *reinterpret_cast<uint32_t*>(shard + le) = w;

@@ -623,6 +623,7 @@ __global__ void __launch_bounds__(kBlock)
     case kBfpRne: { constexpr int C = kBfpRne; __VA_ARGS__; break; }     \
     case kRawF32: { constexpr int C = kRawF32; __VA_ARGS__; break; }     \
     case kRawBf16: { constexpr int C = kRawBf16; __VA_ARGS__; break; }   \
+    case kBfp4Rne: { constexpr int C = kBfp4Rne; __VA_ARGS__; break; }   \
     default: FAN_CHECK(false, "unknown codec");              \
   }
 
@@ -679,11 +680,12 @@ void launch_wire_unpack(int codec, int out_dtype, const void* in, void* out, siz
   FAN_HIP_CHECK(hipGetLastError());
 }
 
-// The lane layout and the grid of a reduce kernel: launch(L{}, grid) with L = Lanes4<C> (4 values per lane) for a BFP
-// codec when wire_reduce4_for(n_slots), else Lanes16<C> (a group per lane).
+// The lane layout and the grid of a reduce kernel: launch(L{}, grid) with L = Lanes4<C> (4 values per lane) for an
+// 8-bit BFP codec when wire_reduce4_for(n_slots), else Lanes16<C> (a group per lane; kBfp4Rne always: 4 of its values
+// are two bytes, too narrow a store to be worth a layout of their own).
 template <int C, typename F>
 static void with_lanes(int n_slots, size_t n_s, int cap, F&& launch) {
-  if constexpr (C == kBfpTrunc || C == kBfpRne) {
+  if constexpr (codec_bfp8(C)) {
     if (wire_reduce4_for(n_slots)) return launch(Lanes4<C>{}, stream_grid(n_s / 4, kBlock, cap));
   }
   launch(Lanes16<C>{}, stream_grid(n_s / 16, kBlock, cap));
@@ -914,7 +916,7 @@ void launch_wire_reduce_to(int codec, int local_dtype, const void* slots, size_t
 }
 
 static void check_ef(int codec, const float* residual) {
-  FAN_CHECK(codec == kBfpTrunc || codec == kBfpRne, "error feedback: BFP codecs only (a raw codec drops nothing)");
+  FAN_CHECK(codec_shared_exp(codec), "error feedback: BFP codecs only (a raw codec drops nothing)");
   FAN_CHECK(residual != nullptr && (reinterpret_cast<uintptr_t>(residual) & 15) == 0,
             "error feedback: a 16-B aligned f32 residual plane");
 }
@@ -938,6 +940,7 @@ void launch_wire_pack_ef(int codec, int in_dtype, const void* in, float* residua
                          dst, n_s, n_shards, self_shard, rel);                                                      \
   } while (0)
   if (codec == kBfpTrunc) FAN_PACK_EF(kBfpTrunc);
+  else if (codec == kBfp4Rne) FAN_PACK_EF(kBfp4Rne);
   else FAN_PACK_EF(kBfpRne);
 #undef FAN_PACK_EF
   FAN_HIP_CHECK(hipGetLastError());
@@ -973,6 +976,9 @@ void launch_wire_reduce_ef(int codec, int local_dtype, const void* slots, size_t
   if (codec == kBfpTrunc)
     reduce_ef_dispatch<kBfpTrunc>(local_dtype, sl, slot_stride, n_slots, self_pos, local, residual, dst, n_dst, n_s,
                                   cap, rel, stream);
+  else if (codec == kBfp4Rne)
+    reduce_ef_dispatch<kBfp4Rne>(local_dtype, sl, slot_stride, n_slots, self_pos, local, residual, dst, n_dst, n_s, cap,
+                                 rel, stream);
   else
     reduce_ef_dispatch<kBfpRne>(local_dtype, sl, slot_stride, n_slots, self_pos, local, residual, dst, n_dst, n_s, cap,
                                 rel, stream);

@@ -443,7 +443,7 @@ WirePtrs ef_dsts(const std::vector<c10::optional<at::Tensor>>& dsts, size_t sb, 
 void wire_pack_ef(const at::Tensor& x, at::Tensor& residual, const std::vector<c10::optional<at::Tensor>>& dsts,
                   int64_t shard_elems, int64_t codec, int64_t self_shard) {
   FAN_T_CUDA_CONTIG(x);
-  TORCH_CHECK(codec == kBfpTrunc || codec == kBfpRne, "error feedback: BFP codecs only");
+  TORCH_CHECK(codec_shared_exp((int)codec), "error feedback: BFP codecs only");
   TORCH_CHECK(shard_elems > 0 && shard_elems % 256 == 0, "shard_elems must be a positive multiple of 256");
   TORCH_CHECK(x.numel() == shard_elems * (int64_t)dsts.size(), "one destination per shard");
   TORCH_CHECK(residual.device() == x.device(), "residual: on the gradient's device");
@@ -458,7 +458,7 @@ void wire_reduce_ef(const at::Tensor& slots, int64_t n_slots, int64_t self_pos, 
                     int64_t codec) {
   FAN_T_CUDA_CONTIG(slots);
   FAN_T_CUDA_CONTIG(local);
-  TORCH_CHECK(codec == kBfpTrunc || codec == kBfpRne, "error feedback: BFP codecs only");
+  TORCH_CHECK(codec_shared_exp((int)codec), "error feedback: BFP codecs only");
   TORCH_CHECK(shard_elems > 0 && shard_elems % 256 == 0, "shard_elems must be a positive multiple of 256");
   TORCH_CHECK(n_slots >= 1 && self_pos >= 0 && self_pos < n_slots, "self_pos names one of the n_slots slots");
   const size_t sb = wire_shard_bytes((int)codec, (size_t)shard_elems);

@@ -1108,8 +1108,7 @@ int AllReduceEngine::submit(const EngineRequest& req, hipStream_t producer) {
   if (req.residual) {
     // Error feedback lives in the mesh schedule's two encoders (refused before the request takes a slot).
     FAN_CHECK(cfg_.codec != kRawF32, "error feedback: nothing to feed back with the raw codec (raw_f32 drops nothing)");
-    FAN_CHECK(cfg_.codec == kBfpTrunc || cfg_.codec == kBfpRne, "error feedback: raw_bf16 is not supported yet (BFP "
-                                                                "codecs only)");
+    FAN_CHECK(codec_shared_exp(cfg_.codec), "error feedback: raw_bf16 is not supported yet (BFP codecs only)");
     FAN_CHECK(req.prepacked == nullptr, "error feedback: not with prepacked input (the GEMM's encoding carries no "
                                         "residual)");
     FAN_CHECK(cfg_.algo == 0, "error feedback: mesh schedule only (the ring schedule is not supported yet)");

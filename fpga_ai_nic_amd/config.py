@@ -3,8 +3,9 @@
 Reference knobs and where they went:
   iters / MB / fuse_type / type / bn bk bc / C1..CN  -> positional CLI, kept (sw/mlp_mpi_example_f32.cpp:270-320)
   NUM_NODES=3 (sw:38)                               -> world size from the launcher (any N >= 1)
-  `BFP_EN (hw/all_reduce.sv:13)                     -> compress = bfp | raw | rccl | local
-  NUM_FP=16, MANT_SIZE=8 (hw/bfp_adapter.sv:34-36)   -> fixed wire format; rounding = rne | trunc (bit-exact ref)
+  `BFP_EN (hw/all_reduce.sv:13)                     -> compress = bfp | bfp4 | raw | rccl | local
+  NUM_FP=16, MANT_SIZE=8 (hw/bfp_adapter.sv:34-36)   -> group of 16; 8-bit mantissas (bfp; rounding = rne | trunc, the
+                                                        bit-exact ref) or 4-bit (bfp4, rne only)
   BUF_SIZE=512 CL slice (hw/all_reduce.sv:102)      -> slice_elems (ring)
   lr 0.1 hard-coded (hw/weight_update.sv:444)        -> lr, momentum, weight_decay
   loss_weight 0.1 (sw:250)                           -> loss_scale
@@ -27,7 +28,7 @@ class TrainConfig:
     bc: int = 64
     sizes: list = field(default_factory=lambda: [1024, 4096, 4096, 1024])
     dtype: str = "bf16"            # bf16 | f32
-    compress: str = "bfp"          # bfp | raw | raw_bf16 | rccl | local
+    compress: str = "bfp"          # bfp | bfp4 | raw | raw_bf16 | rccl | local
     rounding: str = "rne"          # rne | trunc
     algo: str = "mesh"             # mesh | ring
     rings: int = 1
@@ -62,7 +63,9 @@ class TrainConfig:
 def add_named_flags(ap: argparse.ArgumentParser):
     d = TrainConfig()
     ap.add_argument("--dtype", default=d.dtype, choices=["bf16", "f32"])
-    ap.add_argument("--compress", default=d.compress, choices=["bfp", "raw", "raw_bf16", "rccl", "local"])
+    ap.add_argument("--compress", default=d.compress, choices=["bfp", "bfp4", "raw", "raw_bf16", "rccl", "local"],
+                    help="wire format of the all-reduce: bfp = 8-bit mantissas (17 B per 16 values), bfp4 = 4-bit "
+                         "mantissas (9 B per 16 values, --rounding rne only; meant for use with --error-feedback)")
     ap.add_argument("--rounding", default=d.rounding, choices=["rne", "trunc"])
     ap.add_argument("--algo", default=d.algo, choices=["mesh", "ring"])
     ap.add_argument("--rings", type=int, default=d.rings)
@@ -101,6 +104,16 @@ def add_named_flags(ap: argparse.ArgumentParser):
     return ap
 
 
+def wire_codec(compress: str, rounding: str = "rne") -> str:
+    """The wire codec name of a --compress / --rounding pair (the engine kinds of ``parallel.dp.make_engine``)."""
+    if compress == "bfp4":
+        if rounding != "rne":
+            raise ValueError(f"--compress bfp4 has no {rounding!r} rounding: the 4-bit codec is bfp4_rne only (the "
+                             f"reference ships no 4-bit configuration to be bit-exact to)")
+        return "bfp4_rne"
+    return {"bfp": f"bfp_{rounding}", "raw": "raw_f32", "raw_bf16": "raw_bf16"}[compress]
+
+
 def config_from_args(a, positional_sizes=None) -> TrainConfig:
     c = TrainConfig()
     for f in dataclasses.fields(TrainConfig):
@@ -109,4 +122,6 @@ def config_from_args(a, positional_sizes=None) -> TrainConfig:
             setattr(c, key, getattr(a, key))
     if positional_sizes:
         c.sizes = list(positional_sizes)
+    if c.compress == "bfp4":
+        wire_codec(c.compress, c.rounding)  # (--rounding trunc: a ValueError)
     return c

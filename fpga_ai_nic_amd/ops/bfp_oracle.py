@@ -12,8 +12,12 @@ Two numerics are modelled:
   (exact zero, symmetric range, half the error bound of truncation). E = 255 (Inf/NaN in the group)
   decodes to NaN so corrupted gradients fail loudly.
 
+``bfp4_rne`` is the ``rne`` form at a 4-bit mantissa (the reference's MANT_SIZE knob; it ships no such configuration,
+so there is no truncating form): q = clamp(rint(x * 2^(129-E)), -7, 7), decode q * 2^(E-129), E = 255 -> NaN.
+
 Packed layout of a shard of n_s elements (n_s % 256 == 0): ``[int8 mant[n_s]][uint8 exp[n_s/16]]``;
-multi-shard buffers are shards back to back.
+``bfp4_rne``: ``[uint8 nib[n_s/2]][uint8 exp[n_s/16]]``, byte i of a group's 8 holding value 2i in bits [3:0] and
+value 2i+1 in bits [7:4] (two's complement nibbles). Multi-shard buffers are shards back to back.
 """
 from __future__ import annotations
 
@@ -22,7 +26,8 @@ import math
 import numpy as np
 
 GROUP = 16
-CODECS = {"bfp_trunc": 0, "bfp_rne": 1, "raw_f32": 2, "raw_bf16": 3}
+CODECS = {"bfp_trunc": 0, "bfp_rne": 1, "raw_f32": 2, "raw_bf16": 3, "bfp4_rne": 4}
+BFP_CODECS = (0, 1, 4)  # a shared exponent per group of 16; (0, 1) are the 8-bit ones the GEMM epilogues encode
 CODEC_NAMES = {v: k for k, v in CODECS.items()}
 
 
@@ -36,6 +41,8 @@ def shard_bytes(codec, n_s: int) -> int:
     c = codec_id(codec)
     if c in (0, 1):
         return n_s + n_s // 16
+    if c == 4:
+        return n_s // 2 + n_s // 16
     return n_s * (4 if c == 2 else 2)
 
 
@@ -71,11 +78,12 @@ def encode_groups(x: np.ndarray, rounding: str = "rne"):
         a = np.where(d >= 32, 0, m >> np.minimum(d, 31))
         t = np.where((bits >> 31) == 1, -a, a)
         q = (t >> 17).astype(np.int8)
-    elif rounding == "rne":
+    elif rounding in ("rne", "rne4"):
+        top, lim = (133, 127.0) if rounding == "rne" else (129, 7.0)
         with np.errstate(over="ignore", invalid="ignore"):
-            s = np.ldexp(x, (133 - E.astype(np.int32)))
+            s = np.ldexp(x, (top - E.astype(np.int32)))
             s = np.rint(s)
-            s = np.clip(np.nan_to_num(s, nan=-127.0, posinf=127.0, neginf=-127.0), -127, 127)
+            s = np.clip(np.nan_to_num(s, nan=-lim, posinf=lim, neginf=-lim), -lim, lim)
         q = s.astype(np.int8)
     else:
         raise ValueError(rounding)
@@ -94,8 +102,9 @@ def decode_groups(q: np.ndarray, E: np.ndarray, rounding: str = "rne") -> np.nda
         frac = (M << zc) & 0x7FFFFE
         bits = (sign << 31) | (ex << 23) | frac
         return bits.astype(np.uint32).view(np.float32).reshape(-1)
-    if rounding == "rne":
-        v = np.ldexp(q.astype(np.float32), (Eu.astype(np.int32) - 133)).astype(np.float32)
+    if rounding in ("rne", "rne4"):
+        with np.errstate(over="ignore"):  # (E = 255 decodes to NaN below)
+            v = np.ldexp(q.astype(np.float32), Eu.astype(np.int32) - (133 if rounding == "rne" else 129))
         v = np.where(Eu == 255, np.float32(np.nan), v)
         return v.reshape(-1).astype(np.float32)
     raise ValueError(rounding)
@@ -103,7 +112,20 @@ def decode_groups(q: np.ndarray, E: np.ndarray, rounding: str = "rne") -> np.nda
 
 def _rounding_of(codec) -> str:
     c = codec_id(codec)
-    return "trunc" if c == 0 else "rne"
+    return "trunc" if c == 0 else "rne4" if c == 4 else "rne"
+
+
+def pack_nibbles(q: np.ndarray) -> np.ndarray:
+    """int8 values in [-8, 7] (even count) -> uint8, value 2i in bits [3:0] of byte i and value 2i+1 in bits [7:4]."""
+    u = np.asarray(q, dtype=np.int8).reshape(-1).view(np.uint8) & 0xF
+    return (u[0::2] | (u[1::2] << 4)).astype(np.uint8)
+
+
+def unpack_nibbles(b: np.ndarray) -> np.ndarray:
+    """The inverse of :func:`pack_nibbles`: uint8 [n/2] -> sign-extended int8 [n]."""
+    b = np.asarray(b, dtype=np.uint8).reshape(-1)
+    u = np.stack([b & 0xF, b >> 4], 1).reshape(-1).astype(np.int16)
+    return np.where(u >= 8, u - 16, u).astype(np.int8)
 
 
 # --------------------------------------------------------------------------- packed buffers
@@ -119,7 +141,7 @@ def pack(x: np.ndarray, shard_elems: int, codec="bfp_rne") -> np.ndarray:
     out = []
     for s in range(x.size // shard_elems):
         q, E = encode_groups(x[s * shard_elems:(s + 1) * shard_elems], _rounding_of(c))
-        out.append(q.view(np.uint8))
+        out.append(pack_nibbles(q) if c == 4 else q.view(np.uint8))
         out.append(E)
     return np.concatenate(out)
 
@@ -135,7 +157,9 @@ def unpack(buf: np.ndarray, n: int, shard_elems: int, codec="bfp_rne") -> np.nda
     out = []
     for s in range(n // shard_elems):
         sh = buf[s * sb:(s + 1) * sb]
-        out.append(decode_groups(sh[:shard_elems].view(np.int8), sh[shard_elems:], _rounding_of(c)))
+        nm = shard_elems // 2 if c == 4 else shard_elems
+        q = unpack_nibbles(sh[:nm]) if c == 4 else sh[:nm].view(np.int8)
+        out.append(decode_groups(q, sh[nm:], _rounding_of(c)))
     return np.concatenate(out) if out else np.zeros(0, np.float32)
 
 
@@ -170,7 +194,7 @@ def reduce_slots(slots, local=None, self_pos: int = -1, codec="bfp_rne", shard_e
 # --------------------------------------------------------------------------- error feedback
 def _ef_codec(codec) -> int:
     c = codec_id(codec)
-    if c not in (0, 1):
+    if c not in BFP_CODECS:
         raise ValueError(f"error feedback: BFP codecs only, got {CODEC_NAMES.get(c, c)!r} (a raw codec drops nothing)")
     return c
 

@@ -85,7 +85,7 @@ def reduce(slots: torch.Tensor, n_slots: int, self_pos: int, local: torch.Tensor
 
 def _ef_check(residual: torch.Tensor, need: int, ref: torch.Tensor, codec) -> int:
     c = codec_id(codec)
-    if c not in (0, 1):
+    if c not in O.BFP_CODECS:
         raise ValueError(f"error feedback: BFP codecs only, got {O.CODEC_NAMES.get(c, c)!r} (a raw codec drops "
                          f"nothing)")
     if not (isinstance(residual, torch.Tensor) and residual.dtype == torch.float32 and residual.is_contiguous()):

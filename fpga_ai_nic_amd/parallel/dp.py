@@ -22,6 +22,7 @@ from ..models.mlp import MLP
 from ..ops import gemm as G
 from ..ops import gemm_tune, wire
 from ..utils import tracing
+from ..config import wire_codec
 from .allreduce import NUM_SLOTS, OPTIMIZERS, CompressedAllReduce, Handle, _round_up
 from .transport import Transport
 
@@ -58,7 +59,8 @@ def make_engine(transport: Transport | None, kind: str = "bfp", *, rounding: str
                 side_stream: bool = False, ring_sub: int = 0, shard_update: bool | None = None, device=None):
     """``device`` (Python engines): where the engine keeps its buffers; None: the current GPU when there is one. A
     CPU run on a machine that has a GPU must name it, or the engine's scratch lands on the GPU beside CPU gradients.
-    kind: 'bfp' (compressed engine), 'raw' (engine, uncompressed fp32 wire), 'rccl' (baseline),
+    kind: 'bfp' (compressed engine), 'bfp4' (the same with 4-bit mantissas, codec bfp4_rne: ``rounding`` must be 'rne'),
+    'raw' (engine, uncompressed fp32 wire), 'rccl' (baseline),
     'local' (no communication: world 1). impl: 'python' (request path issued from Python over any
     transport) or 'native' (C++ engine over its own RCCL communicator, or over ``comm``, e.g. the direct P2P
     communicator of :func:`~fpga_ai_nic_amd.parallel.transport.make_p2p_comm`; GPU only)."""
@@ -66,7 +68,7 @@ def make_engine(transport: Transport | None, kind: str = "bfp", *, rounding: str
         return None
     if kind == "rccl":
         return RcclAllReduce(transport, timeout_s=timeout_s, force_comm=force_comm, device=device)
-    codec = {"bfp": f"bfp_{rounding}", "raw": "raw_f32", "raw_bf16": "raw_bf16"}[kind]
+    codec = wire_codec(kind, rounding)
     if impl == "native":
         from .native_engine import NativeAllReduce
 
