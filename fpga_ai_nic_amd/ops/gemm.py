@@ -86,7 +86,7 @@ def gemm(A, a_t: bool, B, b_t: bool, C, epilogue: int = EPI_NONE, bias=None, aux
             from . import nn as _nn
 
             gemm(A, a_t, B, b_t, C, epilogue, bias, aux, accumulate, split_k, tile)
-            _nn.col_sum(B.t() if b_t else B, colsum)
+            _nn.col_sum(B.t().contiguous() if b_t else B, colsum)  # (col_sum takes unit column stride)
             return C
         if A.dtype == torch.bfloat16:
             if C.dtype == torch.bfloat16 and not _aligned16(C, bias, aux if epilogue == EPI_RELU_MASK else None):

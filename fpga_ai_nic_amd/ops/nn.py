@@ -27,8 +27,19 @@ def softmax_xent_slabs(slabs: dict, bias: torch.Tensor, logits: torch.Tensor, la
     """:func:`softmax_xent` over the classifier GEMM's unreduced split-K slabs (``slabs`` from ``ops.gemm.gemm``'s
     ``defer_reduce``): logits = the slabs' sum in split order + bias, as the GEMM's own reduce computes them (also
     written to ``logits``), then the fused softmax + cross-entropy — one launch instead of two."""
-    _ext.require().softmax_xent_slabs(slabs["ws"], int(slabs["sk"]), bias, logits, labels, dlogits, loss_rows,
-                                      float(grad_scale))
+    ws, sk = slabs["ws"], int(slabs["sk"])
+    if ws.is_cuda:
+        _ext.require().softmax_xent_slabs(ws, sk, bias, logits, labels, dlogits, loss_rows, float(grad_scale))
+        return
+    M, C = logits.shape
+    if C % 8 or C > 2048 or sk < 1 or ws.numel() < sk * M * C:
+        raise ValueError(f"softmax_xent_slabs: C % 8 == 0, C <= 2048 and {sk} slabs of {M} x {C} needed")
+    s = ws.reshape(-1)[: sk * M * C].view(sk, M, C).float()
+    acc = s[0].clone()
+    for q in range(1, sk):  # split order, as the kernel adds them
+        acc = acc + s[q]
+    logits.copy_(acc + bias.float())
+    softmax_xent(logits, labels, dlogits, loss_rows, grad_scale)
 
 
 def col_sum(x: torch.Tensor, out: torch.Tensor, scale: float = 1.0, accumulate: bool = False):

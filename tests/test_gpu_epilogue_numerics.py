@@ -316,8 +316,13 @@ def _softmax_inputs_cpu(Cc, in_bf16):
     x[36, Cc - nm:] = float("-inf")  # the last classes masked (row 36: alone in the last block)
     y[36] = Cc // 2 - 1
     x = x.to(BF if in_bf16 else F32)
+    return dict(x=x, y=y, **softmax_reference(x, y))
+
+
+def softmax_reference(x, y):
+    """float64 loss rows and gradient of the (already rounded) logits ``x`` [M][C] with labels ``y``."""
     xd = x.double()
-    rows = torch.arange(M)
+    rows = torch.arange(x.shape[0], device=x.device)
     lse = torch.logsumexp(xd, 1)
     xl = xd[rows, y.long()]
     loss = lse - xl
@@ -326,7 +331,7 @@ def _softmax_inputs_cpu(Cc, in_bf16):
     d *= SMX_GRAD_SCALE
     assert bool(torch.isfinite(loss).all()) and bool(torch.isfinite(d).all())
     # the loss is the difference of two float32 quantities of these sizes: its absolute term scales with them
-    return dict(x=x, y=y, loss=loss, d=d, loss_scale=torch.maximum(lse.abs(), xl.abs()).clamp(min=1.0))
+    return dict(loss=loss, d=d, loss_scale=torch.maximum(lse.abs(), xl.abs()).clamp(min=1.0))
 
 
 @functools.lru_cache(maxsize=None)
@@ -351,8 +356,9 @@ def run_softmax(dev, Cc, in_bf16, out_bf16, padded=False):
     return d, dfull, loss, lfull
 
 
-def verify_softmax(dev, Cc, in_bf16, out_bf16, d, dfull=None, loss=None, lfull=None, r=SMX_R, what=""):
-    inp = softmax_inputs(Cc, in_bf16, dev)
+def verify_softmax(dev, Cc, in_bf16, out_bf16, d, dfull=None, loss=None, lfull=None, r=SMX_R, what="", inp=None):
+    """``inp``: a reference other than the inputs of (Cc, in_bf16) — :func:`softmax_reference` of the logits used."""
+    inp = softmax_inputs(Cc, in_bf16, dev) if inp is None else inp
     what = f"{what} C={Cc} in={'bf16' if in_bf16 else 'f32'} out={'bf16' if out_bf16 else 'f32'}"
     if loss is not None:
         _check(loss, inp["loss"], r * inp["loss"].abs() + SMX_A * inp["loss_scale"], what + " loss")
