@@ -529,6 +529,148 @@ struct Lanes4 {
   }
 };
 
+// ---------------------------------------------------------------- stochastic rounding (ops/bfp_oracle.py sr_*)
+// The rne codecs' encoders with an unbiased rounding, q = floor(t) + (frac(t) > u): the wire format and the decoders
+// stay as they are. The random byte of element i of the padded bucket (i < 2^32) is byte i & 3 of the hash word
+// h(k0, k1, i >> 2), so a lane's 4 consecutive values cost one hash and the bits depend on nothing but the key and the
+// element. The key is computed on the host from the request's 64-bit seed, the encoding rank and the stage.
+__host__ __device__ constexpr bool codec_sr(int c) { return c == kBfpRne || c == kBfp4Rne; }
+
+struct SrKey {
+  uint32_t k0, k1;
+};
+
+// stage: 0 the sender's pack, 1 the owner's re-encode.
+inline SrKey sr_key(uint64_t seed, int rank, int stage) {
+  return {(uint32_t)seed, (uint32_t)(seed >> 32) ^ ((uint32_t)(2 * rank + stage + 1) * 0x9E3779B9u)};
+}
+
+__host__ __device__ __forceinline__ uint32_t sr_mix(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7FEB352Du;
+  x ^= x >> 15;
+  x *= 0x846CA68Bu;
+  x ^= x >> 16;
+  return x;
+}
+__host__ __device__ __forceinline__ uint32_t sr_hash(SrKey k, uint32_t w) { return sr_mix(sr_mix(w ^ k.k0) + k.k1); }
+
+// One value of a finite group (E != 255; the caller sends an E == 255 group through bfp_encode<C>), all f32:
+// t = x * 2^(k-E), f = floor(t), d = t - f, u = (b + 0.5) / 256 (exact), q = clamp(f + (d > u), -qmax, qmax). A value
+// the codec represents exactly has d == 0 and keeps its q whatever b is.
+template <int C>
+__device__ __forceinline__ int32_t bfp_encode_sr(float x, uint32_t E, uint32_t b) {
+  static_assert(codec_sr(C), "rne codecs");
+  constexpr int kTop = C == kBfp4Rne ? 129 : 133;
+  constexpr float kMax = C == kBfp4Rne ? 7.0f : 127.0f;
+  const float t = ldexpf(x, kTop - (int)E);
+  const float f = floorf(t);
+  const float d = t - f;
+  const float u = ((float)b + 0.5f) * (1.0f / 256.0f);
+  const float s = f + (d > u ? 1.0f : 0.0f);
+  return (int32_t)fminf(fmaxf(s, -kMax), kMax);
+}
+
+// The mantissas of kVals (4 or 16) consecutive values of a group of shared exponent E, first element i of the padded
+// bucket (i % 4 == 0), packed as the wire holds them: 8-bit codec value j in byte j, 4-bit value j in nibble j.
+template <int C, int kVals>
+__device__ __forceinline__ void sr_encode_vals(const float (&v)[kVals], uint32_t E, SrKey key, uint32_t i,
+                                               uint32_t (&w)[(kVals * (C == kBfp4Rne ? 4 : 8) + 31) / 32]) {
+  constexpr int kBits = C == kBfp4Rne ? 4 : 8;
+  constexpr uint32_t kMask = (1u << kBits) - 1u;
+#pragma unroll
+  for (int j = 0; j < (kVals * kBits + 31) / 32; ++j) w[j] = 0u;
+  if (E != 255u) {
+#pragma unroll
+    for (int g = 0; g < kVals / 4; ++g) {
+      const uint32_t h = sr_hash(key, (i >> 2) + g);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int e = 4 * g + j;
+        const int32_t q = bfp_encode_sr<C>(v[e], E, (h >> (8 * j)) & 0xFFu);
+        w[(e * kBits) >> 5] |= ((uint32_t)q & kMask) << ((e * kBits) & 31);
+      }
+    }
+  } else {  // a non-finite group: the rne encoder's bytes
+#pragma unroll
+    for (int e = 0; e < kVals; ++e)
+      w[(e * kBits) >> 5] |= ((uint32_t)bfp_encode<C>(v[e], E) & kMask) << ((e * kBits) & 31);
+  }
+}
+
+// Value e of the words sr_encode_vals packed, as the decoder reads it.
+template <int C>
+__device__ __forceinline__ float sr_decode_val(const uint32_t* w, int e, uint32_t E) {
+  if constexpr (C == kBfp4Rne) return bfp4_decode_rne(bfp4_nibble(w[e >> 3], e & 7), E);
+  else return bfp_decode_rne((int32_t)(int8_t)(uint8_t)(w[e >> 2] >> (8 * (e & 3))), E);
+}
+
+// The stochastic forms of a lane layout's store_wire and roundtrip (Lanes16<C> / Lanes4<C> above, same requirements on
+// the active lanes): `to` is a destination table, every non-null entry below n_dst receives the same bytes from one
+// encode; `i` is the bucket index of the lane's first value.
+template <typename L>
+struct SrLanes;
+
+template <int C>
+struct SrLanes<Lanes16<C>> {
+  static constexpr int kWords = C == kBfp4Rne ? 2 : 4;
+  __device__ static __forceinline__ uint32_t exponent(const float (&v)[16]) {
+    uint32_t mx = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) mx = max(mx, __float_as_uint(v[j]) & 0x7FFFFFFFu);
+    return mx >> 23;
+  }
+  __device__ static __forceinline__ void store_wire(uint8_t* const* to, int n_dst, size_t n_s, size_t le,
+                                                    const float (&v)[16], SrKey key, uint32_t i) {
+    const uint32_t E = exponent(v);
+    uint32_t w[kWords];
+    sr_encode_vals<C, 16>(v, E, key, i, w);
+    // exponent plane: 4 lanes -> one dword, 4 dwords -> one 16-B store by lane 16k (WireLane16)
+    uint32_t e4 = E | ((uint32_t)__shfl_down((int)E, 1) << 8) | ((uint32_t)__shfl_down((int)E, 2) << 16) |
+                  ((uint32_t)__shfl_down((int)E, 3) << 24);
+    const uint32_t e4b = (uint32_t)__shfl_down((int)e4, 4), e4c = (uint32_t)__shfl_down((int)e4, 8),
+                   e4d = (uint32_t)__shfl_down((int)e4, 12);
+    const size_t mant = C == kBfp4Rne ? n_s >> 1 : n_s;  // bytes of the mantissa plane
+    for (int k = 0; k < n_dst; ++k) {                    // (wave-uniform condition)
+      uint8_t* shard = to[k];
+      if (shard == nullptr) continue;
+      if constexpr (C == kBfp4Rne) *reinterpret_cast<uint2*>(shard + (le >> 1)) = make_uint2(w[0], w[1]);
+      else *reinterpret_cast<uint4*>(shard + le) = make_uint4(w[0], w[1], w[2], w[3]);
+      if ((threadIdx.x & 15) == 0) *reinterpret_cast<uint4*>(shard + mant + (le >> 4)) = make_uint4(e4, e4b, e4c, e4d);
+    }
+  }
+  __device__ static __forceinline__ void roundtrip(float (&v)[16], SrKey key, uint32_t i) {
+    const uint32_t E = exponent(v);
+    uint32_t w[kWords];
+    sr_encode_vals<C, 16>(v, E, key, i, w);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = sr_decode_val<C>(w, j, E);
+  }
+};
+
+template <int C>
+struct SrLanes<Lanes4<C>> {
+  __device__ static __forceinline__ void store_wire(uint8_t* const* to, int n_dst, size_t n_s, size_t le,
+                                                    const float (&v)[4], SrKey key, uint32_t i) {
+    const uint32_t E = bfp_quad_exponent(v);
+    uint32_t w[1];
+    sr_encode_vals<C, 4>(v, E, key, i, w);
+    for (int k = 0; k < n_dst; ++k) {
+      uint8_t* shard = to[k];
+      if (shard == nullptr) continue;
+      *reinterpret_cast<uint32_t*>(shard + le) = w[0];
+      if ((le & 15) == 0) shard[n_s + (le >> 4)] = (uint8_t)E;
+    }
+  }
+  __device__ static __forceinline__ void roundtrip(float (&v)[4], SrKey key, uint32_t i) {
+    const uint32_t E = bfp_quad_exponent(v);
+    uint32_t w[1];
+    sr_encode_vals<C, 4>(v, E, key, i, w);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = sr_decode_val<C>(w, j, E);
+  }
+};
+
 // ---------------------------------------------------------------- release of stores into peer memory
 // A kernel that stores into peers' receive arenas (direct P2P transport) must have every store performed before the
 // stream-ordered flag write that tells the peer to read them (p2p_comm.h, memory ordering). Modes (FAN_P2P_RELEASE,
@@ -665,6 +807,21 @@ void launch_wire_reduce_ef(int codec, int local_dtype, const void* slots, size_t
                            hipStream_t stream);
 void launch_wire_reduce_ef(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
                            const void* local, float* residual, void* out_wire, size_t n_s, hipStream_t stream);
+// Stochastic rounding for the two encoders of the mesh schedule, kBfpRne and kBfp4Rne only; stateless, and the wire
+// format is unchanged. ops/bfp_oracle.py sr_pack / sr_reduce define the bits, which do not depend on the grid or the
+// lane layout. `base` is the bucket index of the launch's first element; the launch's last index must be below 2^32.
+// Sender stage: launch_wire_pack_to with key = sr_key(seed, rank, 0). Shard self_shard (-1: none) takes the plain rne
+// encoder; a null destination skips its shard. `peers` as launch_wire_pack_ef.
+void launch_wire_pack_sr(int codec, int in_dtype, const void* in, const WirePtrs& dst, size_t n_s, int n_shards,
+                         int self_shard, SrKey key, size_t base, bool peers, hipStream_t stream);
+// Owner stage: launch_wire_reduce_to (local operand required) with key = sr_key(seed, rank, 1); `base` is the owner
+// shard's first element in the bucket. Both lane layouts (set_wire_reduce4), the same bits. The output goes to every
+// non-null dst.p[i] (i < n_dst) or, in the second form, to the one local buffer out_wire.
+void launch_wire_reduce_sr(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
+                           const void* local, const WirePtrs& dst, int n_dst, size_t n_s, SrKey key, size_t base,
+                           bool peers, hipStream_t stream);
+void launch_wire_reduce_sr(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
+                           const void* local, void* out_wire, size_t n_s, SrKey key, size_t base, hipStream_t stream);
 // Sharded update of the owner's shard (engine shard_update mode, ZeRO-1 style): sum the N received wire shards
 // (slot self_pos replaced by the dense local operand), take the sum through the wire codec's round trip in registers
 // (exactly the values every rank would decode from the re-encoded owner shard in the unsharded schedule), apply SGD to

@@ -22,6 +22,8 @@
 //                  wire_lamb_apply (pass 2) — with a deterministic fp64 reduction in between (no atomics).
 //   error feedback = no counterpart in the reference (what its adapter drops is gone): wire_pack_ef and wire_reduce_ef,
 //                  the mesh schedule's two encoders with a per-rank f32 residual plane beside the unchanged wire.
+//   stochastic rounding = no counterpart either: wire_pack_sr and wire_reduce_sr, the same two encoders rounding up
+//                  with probability equal to the dropped fraction (a counter-based hash per 4 values, no state).
 #include "bfp/bfp_format.h"
 
 #include <algorithm>
@@ -327,6 +329,50 @@ __global__ void __launch_bounds__(kBlock)
 #pragma unroll
     for (int j = 0; j < L::kVals; ++j) e[j] = acc[j] - e[j];
     L::store_f32(resid, le, e);
+  }
+  if (rel >= 0) p2p_release(rel);
+}
+
+// ---------------------------------------------------------------- stochastic rounding (bfp_oracle.sr_pack / sr_reduce)
+// The same two encoders with the unbiased rounding of bfp_format.h SrLanes: no state, no atomics, no LDS; the element
+// index that selects the random byte is base + (offset in the launch), whatever the grid.
+
+// Sender stage: wire_pack_to_kernel's traversal; shard self_shard takes the plain rne store (grid-uniform branch).
+template <typename TIN, int C>
+__global__ void __launch_bounds__(kBlock)
+    wire_pack_sr_kernel(const TIN* __restrict__ in, WirePtrs dst, size_t n_s, int n_shards, int self_shard, SrKey key,
+                        uint32_t base, int rel) {
+  const size_t tasks = n_s >> 4;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (int s = 0; s < n_shards; ++s) {
+    uint8_t* d = dst.p[s];
+    if (d == nullptr) continue;
+    const TIN* src = in + (size_t)s * n_s;
+    const uint32_t sbase = base + (uint32_t)((size_t)s * n_s);
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
+      float v[16];
+      DenseLane16<TIN>::load16(src, t << 4, v);
+      if (s == self_shard) WireLane16<C>::store16(d, n_s, t << 4, v);
+      else SrLanes<Lanes16<C>>::store_wire(&d, 1, n_s, t << 4, v, key, sbase + (uint32_t)(t << 4));
+    }
+  }
+  if (rel >= 0) p2p_release(rel);
+}
+
+// Owner stage: wire_reduce_to_kernel's body, the sum encoded once and stored to every destination, in either lane
+// layout (same operations per value, so the same bits).
+template <typename L, typename TL>
+__global__ void __launch_bounds__(kBlock)
+    wire_reduce_sr_kernel(const uint8_t* __restrict__ slots, size_t slot_stride, int n_slots, int self_pos,
+                          const TL* __restrict__ local, WirePtrs dst, int n_dst, size_t n_s, SrKey key, uint32_t base,
+                          int rel) {
+  const size_t tasks = n_s / L::kVals;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
+    const size_t le = t * L::kVals;
+    float acc[L::kVals];
+    sum_slots<L>(slots, slot_stride, n_slots, self_pos, local, n_s, le, acc);
+    SrLanes<L>::store_wire(dst.p, n_dst, n_s, le, acc, key, base + (uint32_t)le);
   }
   if (rel >= 0) p2p_release(rel);
 }
@@ -991,6 +1037,81 @@ void launch_wire_reduce_ef(int codec, int local_dtype, const void* slots, size_t
   dst.p[0] = (uint8_t*)out_wire;
   FAN_CHECK(out_wire != nullptr, "reduce_ef needs an output");
   launch_wire_reduce_ef(codec, local_dtype, slots, slot_stride, n_slots, self_pos, local, residual, dst, 1, n_s, false,
+                        stream);
+}
+
+static void check_sr(int codec, size_t base, size_t n) {
+  FAN_CHECK(codec_sr(codec), "stochastic rounding: bfp_rne and bfp4_rne only");
+  FAN_CHECK(base % 16 == 0 && base <= ((size_t)1 << 32) && n <= ((size_t)1 << 32) - base,
+            "stochastic rounding: element indices must stay below 2^32");
+}
+
+void launch_wire_pack_sr(int codec, int in_dtype, const void* in, const WirePtrs& dst, size_t n_s, int n_shards,
+                         int self_shard, SrKey key, size_t base, bool peers, hipStream_t stream) {
+  check_ns(n_s);
+  FAN_CHECK(n_shards >= 0 && n_shards <= kMaxPeers, "pack_sr: at most 16 destinations");
+  check_sr(codec, base, n_s * (size_t)n_shards);
+  if (n_s == 0 || n_shards == 0) return;
+  const int cap = peers ? std::min(wire_max_blocks(), p2p_grid_cap()) : wire_max_blocks();
+  const int rel = peers ? p2p_release_mode() : -1;
+  const int grid = stream_grid(n_s / 16, kBlock, cap);
+#define FAN_PACK_SR(C)                                                                                               \
+  do {                                                                                                               \
+    if (in_dtype == kF32)                                                                                            \
+      hipLaunchKernelGGL((wire_pack_sr_kernel<float, C>), grid, kBlock, 0, stream, (const float*)in, dst, n_s,       \
+                         n_shards, self_shard, key, (uint32_t)base, rel);                                            \
+    else                                                                                                             \
+      hipLaunchKernelGGL((wire_pack_sr_kernel<bf16_t, C>), grid, kBlock, 0, stream, (const bf16_t*)in, dst, n_s,     \
+                         n_shards, self_shard, key, (uint32_t)base, rel);                                            \
+  } while (0)
+  if (codec == kBfp4Rne) FAN_PACK_SR(kBfp4Rne);
+  else FAN_PACK_SR(kBfpRne);
+#undef FAN_PACK_SR
+  FAN_HIP_CHECK(hipGetLastError());
+}
+
+template <int C>
+static void reduce_sr_dispatch(int local_dtype, const uint8_t* sl, size_t slot_stride, int n_slots, int self_pos,
+                               const void* local, const WirePtrs& dst, int n_dst, size_t n_s, SrKey key, uint32_t base,
+                               int cap, int rel, hipStream_t stream) {
+  with_lanes<C>(n_slots, n_s, cap, [&](auto lanes, int grid) {
+    using L = decltype(lanes);
+    if (local_dtype == kF32)
+      hipLaunchKernelGGL((wire_reduce_sr_kernel<L, float>), grid, kBlock, 0, stream, sl, slot_stride, n_slots, self_pos,
+                         (const float*)local, dst, n_dst, n_s, key, base, rel);
+    else
+      hipLaunchKernelGGL((wire_reduce_sr_kernel<L, bf16_t>), grid, kBlock, 0, stream, sl, slot_stride, n_slots,
+                         self_pos, (const bf16_t*)local, dst, n_dst, n_s, key, base, rel);
+  });
+}
+
+void launch_wire_reduce_sr(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
+                           const void* local, const WirePtrs& dst, int n_dst, size_t n_s, SrKey key, size_t base,
+                           bool peers, hipStream_t stream) {
+  check_ns(n_s);
+  check_sr(codec, base, n_s);
+  FAN_CHECK(n_dst >= 1 && n_dst <= kMaxPeers && local != nullptr,
+            "reduce_sr: local operand and 1 to 16 destinations");
+  FAN_CHECK(self_pos >= 0 && self_pos < n_slots, "reduce_sr: self_pos names the slot the local operand stands for");
+  if (n_s == 0) return;
+  const int cap = peers ? std::min(wire_max_blocks(), p2p_grid_cap()) : wire_max_blocks();
+  const int rel = peers ? p2p_release_mode() : -1;
+  const uint8_t* sl = (const uint8_t*)slots;
+  if (codec == kBfp4Rne)
+    reduce_sr_dispatch<kBfp4Rne>(local_dtype, sl, slot_stride, n_slots, self_pos, local, dst, n_dst, n_s, key,
+                                 (uint32_t)base, cap, rel, stream);
+  else
+    reduce_sr_dispatch<kBfpRne>(local_dtype, sl, slot_stride, n_slots, self_pos, local, dst, n_dst, n_s, key,
+                                (uint32_t)base, cap, rel, stream);
+  FAN_HIP_CHECK(hipGetLastError());
+}
+
+void launch_wire_reduce_sr(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
+                           const void* local, void* out_wire, size_t n_s, SrKey key, size_t base, hipStream_t stream) {
+  WirePtrs dst{};
+  dst.p[0] = (uint8_t*)out_wire;
+  FAN_CHECK(out_wire != nullptr, "reduce_sr needs an output");
+  launch_wire_reduce_sr(codec, local_dtype, slots, slot_stride, n_slots, self_pos, local, dst, 1, n_s, key, base, false,
                         stream);
 }
 

@@ -252,7 +252,7 @@ void register_engine(pybind11::module_& m) {
               int64_t layout_chunks, bool on_producer, int64_t opt, c10::optional<at::Tensor> var,
               c10::optional<std::vector<double>> adamw, c10::optional<std::vector<double>> lamb, int64_t n_adapt,
               c10::optional<at::Tensor> trust_out, c10::optional<at::Tensor> clip,
-              c10::optional<at::Tensor> residual) {
+              c10::optional<at::Tensor> residual, bool sr, uint64_t sr_seed) {
              FAN_T_CUDA_CONTIG(grad);
              TORCH_CHECK(grad.scalar_type() == at::kFloat || grad.scalar_type() == at::kBFloat16,
                          "gradients must be f32 or bf16");
@@ -339,6 +339,8 @@ void register_engine(pybind11::module_& m) {
                            "residual: f32[n_pad = ", L.n_pad, "] on the gradient's device");
                req.residual = residual->data_ptr<float>();
              }
+             req.sr = sr;  // stochastic rounding under this 64-bit request seed
+             req.sr_seed = sr_seed;
              return e.submit(req, fan_stream());
            },
            py::arg("grad"), py::arg("master"), py::arg("lp") = py::none(), py::arg("mom") = py::none(),
@@ -349,6 +351,7 @@ void register_engine(pybind11::module_& m) {
            py::arg("on_producer") = false, py::arg("opt") = 0, py::arg("var") = py::none(),
            py::arg("adamw") = py::none(), py::arg("lamb") = py::none(), py::arg("n_adapt") = -1,
            py::arg("trust_out") = py::none(), py::arg("clip") = py::none(), py::arg("residual") = py::none(),
+           py::arg("sr") = false, py::arg("sr_seed") = 0,
            py::call_guard<py::gil_scoped_release>())
       .def("prepack_shape", [](AllReduceEngine& e, int64_t n) {
         const auto s = e.prepack_shape(n);

@@ -474,6 +474,54 @@ void wire_reduce_ef(const at::Tensor& slots, int64_t n_slots, int64_t self_pos, 
                         e, to, (int)dsts.size(), (size_t)shard_elems, false, fan_stream());
 }
 
+// The stochastic-rounding wire ops (bfp_format.h launch_wire_pack_sr / launch_wire_reduce_sr): destinations as above;
+// `seed` is the request's 64-bit seed, `rank` the encoding rank and `base` the bucket index of the first element;
+// `peers` launches as the direct-P2P engine does (the P2P grid cap and release mode; the bits do not depend on it).
+SrKey sr_key_of(int64_t codec, const pybind11::int_& seed, int64_t rank, int stage, int64_t base, int64_t n) {
+  TORCH_CHECK(codec_sr((int)codec), "stochastic rounding: bfp_rne and bfp4_rne only");
+  TORCH_CHECK(rank >= 0 && rank < kMaxPeers, "stochastic rounding: rank in [0, 16)");
+  TORCH_CHECK(base >= 0 && base % 16 == 0 && base + n <= ((int64_t)1 << 32),
+              "stochastic rounding: a padded bucket of 2^32 or more elements (indices are 32-bit)");
+  uint64_t s = 0;
+  try {
+    s = seed.cast<uint64_t>();
+  } catch (const std::exception&) {
+    TORCH_CHECK(false, "stochastic rounding: the seed is an int in [0, 2^64)");
+  }
+  return sr_key(s, (int)rank, stage);
+}
+
+void wire_pack_sr(const at::Tensor& x, const std::vector<c10::optional<at::Tensor>>& dsts, int64_t shard_elems,
+                  int64_t codec, pybind11::int_ seed, int64_t rank, int64_t self_shard, int64_t base, bool peers) {
+  FAN_T_CUDA_CONTIG(x);
+  TORCH_CHECK(shard_elems > 0 && shard_elems % 256 == 0, "shard_elems must be a positive multiple of 256");
+  TORCH_CHECK(x.numel() == shard_elems * (int64_t)dsts.size(), "one destination per shard");
+  const SrKey key = sr_key_of(codec, seed, rank, 0, base, x.numel());
+  const WirePtrs to = ef_dsts(dsts, wire_shard_bytes((int)codec, (size_t)shard_elems), x);
+  launch_wire_pack_sr((int)codec, dcode(x), x.data_ptr(), to, (size_t)shard_elems, (int)dsts.size(), (int)self_shard,
+                      key, (size_t)base, peers, fan_stream());
+}
+
+void wire_reduce_sr(const at::Tensor& slots, int64_t n_slots, int64_t self_pos, const at::Tensor& local,
+                    const std::vector<c10::optional<at::Tensor>>& dsts, int64_t shard_elems, int64_t codec,
+                    pybind11::int_ seed, int64_t rank, int64_t base, bool peers) {
+  FAN_T_CUDA_CONTIG(slots);
+  FAN_T_CUDA_CONTIG(local);
+  TORCH_CHECK(shard_elems > 0 && shard_elems % 256 == 0, "shard_elems must be a positive multiple of 256");
+  TORCH_CHECK(n_slots >= 1 && self_pos >= 0 && self_pos < n_slots, "self_pos names one of the n_slots slots");
+  const SrKey key = sr_key_of(codec, seed, rank, 1, base, shard_elems);
+  const size_t sb = wire_shard_bytes((int)codec, (size_t)shard_elems);
+  // only slots other than self_pos are read (self_pos is replaced by the dense local operand)
+  const int64_t last_read = self_pos == n_slots - 1 ? n_slots - 2 : n_slots - 1;
+  TORCH_CHECK((size_t)slots.numel() * slots.element_size() >= sb * (size_t)(last_read + 1), "slots buffer too small");
+  TORCH_CHECK(local.numel() >= shard_elems, "local operand too small");
+  TORCH_CHECK(slots.device() == local.device(), "one device");
+  TORCH_CHECK(!dsts.empty(), "reduce_sr needs an output");
+  const WirePtrs to = ef_dsts(dsts, sb, local);
+  launch_wire_reduce_sr((int)codec, dcode(local), slots.data_ptr(), sb, (int)n_slots, (int)self_pos, local.data_ptr(),
+                        to, (int)dsts.size(), (size_t)shard_elems, key, (size_t)base, peers, fan_stream());
+}
+
 }  // namespace
 
 void register_gemm(pybind11::module_& m) {
@@ -569,6 +617,14 @@ void register_nn(pybind11::module_& m) {
   m.def("wire_reduce_ef", &wire_reduce_ef, "wire_reduce with error feedback: encode sum + residual, keep the rest",
         pybind11::arg("slots"), pybind11::arg("n_slots"), pybind11::arg("self_pos"), pybind11::arg("local"),
         pybind11::arg("residual"), pybind11::arg("dsts"), pybind11::arg("shard_elems"), pybind11::arg("codec"));
+  m.def("wire_pack_sr", &wire_pack_sr, "wire_pack with stochastic rounding under key (seed, rank, 0)",
+        pybind11::arg("x"), pybind11::arg("dsts"), pybind11::arg("shard_elems"), pybind11::arg("codec"),
+        pybind11::arg("seed"), pybind11::arg("rank"), pybind11::arg("self_shard") = -1, pybind11::arg("base") = 0,
+        pybind11::arg("peers") = false);
+  m.def("wire_reduce_sr", &wire_reduce_sr, "wire_reduce to wire with stochastic rounding under key (seed, rank, 1)",
+        pybind11::arg("slots"), pybind11::arg("n_slots"), pybind11::arg("self_pos"), pybind11::arg("local"),
+        pybind11::arg("dsts"), pybind11::arg("shard_elems"), pybind11::arg("codec"), pybind11::arg("seed"),
+        pybind11::arg("rank"), pybind11::arg("base") = 0, pybind11::arg("peers") = false);
 }
 
 void register_planner(pybind11::module_& m) {

@@ -369,6 +369,10 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const Eng
   // stream wait for everything on the comm stream so far. Inline engines run every request in the producer stream's
   // order. A caller that moves a bucket between producer streams orders them itself, as for the gradient buffer.
   float* ef = req.residual;
+  // Stochastic rounding: req.sr (submit(): an rne BFP codec, mesh, no prepacked input, one chunk, not sharded, no
+  // residual) swaps the same two encoders for their stateless stochastic forms; sender r draws from key
+  // (sr_seed, r, 0), owner r from key (sr_seed, r, 1), element indices are those of the padded bucket.
+  const bool sr = req.sr;
   if (req.prepacked) {  // encode what the producer did not (bias gradient + padding)
     launch_wire_pack_range(c, gdt, req.grad, const_cast<uint8_t*>(req.prepacked), (size_t)s,
                            (size_t)req.prepacked_elems, (size_t)L.n_pad, st);
@@ -378,6 +382,7 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const Eng
     if (req.prepacked) return {make_epilogue(req, req.prepacked, s, 1, 0, s)};
     uint8_t* S = epi_scratch("mesh_S" + std::to_string(sb), sb);
     if (ef) launch_wire_reduce_ef(c, gdt, S, sb, 1, 0, g, ef, S, (size_t)s, st);  // one rank: the owner stage alone
+    else if (sr) launch_wire_reduce_sr(c, gdt, S, sb, 1, 0, g, S, (size_t)s, sr_key(req.sr_seed, 0, 1), 0, st);
     else launch_wire_reduce(c, gdt, S, sb, 1, 0, g, S, nullptr, (size_t)s, st);
     return {make_epilogue(req, S, s, 1, 0, s)};
   }
@@ -393,6 +398,10 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const Eng
       WirePtrs to{};
       for (int q = 0; q < N; ++q) to.p[q] = Pb + (size_t)q * sb;
       launch_wire_pack_ef(c, gdt, g, ef, to, (size_t)s, N, r, false, st);
+    } else if (sr) {  // (shard r's row: plain rne, as above)
+      WirePtrs to{};
+      for (int q = 0; q < N; ++q) to.p[q] = Pb + (size_t)q * sb;
+      launch_wire_pack_sr(c, gdt, g, to, (size_t)s, N, r, sr_key(req.sr_seed, r, 0), 0, false, st);
     } else {
       launch_wire_pack(c, gdt, g, Pb, (size_t)s, N, st);
     }
@@ -437,6 +446,9 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const Eng
     // (1-rank group: the reduced shard is the gathered bucket, so the reduce writes the epilogue's buffer directly)
     const uint8_t* own = g + (size_t)r * s * esize(gdt);
     if (ef) launch_wire_reduce_ef(c, gdt, R, sb, N, r, own, ef + (size_t)r * s, ident ? G : S, (size_t)s, st);
+    else if (sr)
+      launch_wire_reduce_sr(c, gdt, R, sb, N, r, own, ident ? G : S, (size_t)s, sr_key(req.sr_seed, r, 1),
+                            (size_t)r * s, st);
     else launch_wire_reduce(c, gdt, R, sb, N, r, own, ident ? G : S, nullptr, (size_t)s, st);
   }
   mark(kTpReduced);
@@ -524,6 +536,8 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineL
     if (req.prepacked || raw) d->move(segs, st);
     // error feedback (ordering: run_mesh): to.p[r] is null, so shard r is neither encoded nor fed back here
     else if (req.residual) launch_wire_pack_ef(c, gdt, g, req.residual, to, (size_t)s, N, r, true, st);
+    // stochastic rounding: to.p[r] is null as well, so shard r is not encoded here
+    else if (req.sr) launch_wire_pack_sr(c, gdt, g, to, (size_t)s, N, r, sr_key(req.sr_seed, r, 0), 0, true, st);
     else launch_wire_pack_to(c, gdt, g, to, (size_t)s, N, st);
     tag_sent(r1, "mesh_pack", sb);
   }
@@ -574,6 +588,9 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineL
     if (req.residual)
       launch_wire_reduce_ef(c, gdt, d->src_base(r1), d->src_stride(), N, r, own, req.residual + (size_t)r * s, out, N,
                             (size_t)s, true, st);
+    else if (req.sr)
+      launch_wire_reduce_sr(c, gdt, d->src_base(r1), d->src_stride(), N, r, own, out, N, (size_t)s,
+                            sr_key(req.sr_seed, r, 1), (size_t)r * s, true, st);
     else
       launch_wire_reduce_to(c, gdt, d->src_base(r1), d->src_stride(), N, r, own, out, N, (size_t)s, st);
     d->release(r1, st);
@@ -1116,6 +1133,23 @@ int AllReduceEngine::submit(const EngineRequest& req, hipStream_t producer) {
               "error feedback: not with a chunked layout (layout_chunks > 1, or a bucket above chunk_elems)");
     FAN_CHECK(!sharded(req), "error feedback: not with the sharded update (shard_update)");
     FAN_CHECK(world_ <= kMaxPeers, "error feedback: at most 16 ranks (one destination per shard)");
+  }
+  if (req.sr) {
+    // Stochastic rounding lives in the same two encoders (refused before the request takes a slot).
+    FAN_CHECK(cfg_.codec == kBfpRne || cfg_.codec == kBfp4Rne,
+              "stochastic rounding: bfp_rne and bfp4_rne only (bfp_trunc is the reference's floor, a raw codec rounds "
+              "nothing)");
+    FAN_CHECK(req.residual == nullptr, "stochastic rounding: not together with error feedback (pick one)");
+    FAN_CHECK(req.prepacked == nullptr, "stochastic rounding: not with prepacked input (the GEMM's encoding rounds to "
+                                        "nearest)");
+    FAN_CHECK(cfg_.algo == 0, "stochastic rounding: mesh schedule only (the ring schedule is not supported yet)");
+    const EngineLayout SL = layout(req.n_valid, req.layout_shard, req.layout_chunks);
+    FAN_CHECK(SL.chunks <= 1,
+              "stochastic rounding: not with a chunked layout (layout_chunks > 1, or a bucket above chunk_elems)");
+    FAN_CHECK(!sharded(req), "stochastic rounding: not with the sharded update (shard_update)");
+    FAN_CHECK(world_ <= kMaxPeers, "stochastic rounding: at most 16 ranks (one destination per shard)");
+    FAN_CHECK((uint64_t)SL.n_pad < ((uint64_t)1 << 32),
+              "stochastic rounding: a padded bucket of 2^32 or more elements (element indices are 32-bit)");
   }
   {
     // the slot this request takes still holds a clipped request: its forced commit would update with a coefficient

@@ -176,6 +176,11 @@ struct EngineRequest {
   // wire keeps its format, so every epilogue runs unchanged. Refused with prepacked input, the ring schedule, chunked
   // layouts, the sharded update and more than kMaxPeers ranks.
   float* residual = nullptr;
+  // stochastic rounding (mesh, bfp_rne / bfp4_rne): the sender's pack and the owner's re-encode run their stochastic
+  // forms (bfp_format.h launch_wire_pack_sr / launch_wire_reduce_sr) under the 64-bit request seed sr_seed; stateless,
+  // the gathered wire keeps its format. Refused where `residual` is, and together with it.
+  bool sr = false;
+  uint64_t sr_seed = 0;
   float* out_sum = nullptr;
   const uint8_t* prepacked = nullptr;
   int64_t prepacked_elems = 0;

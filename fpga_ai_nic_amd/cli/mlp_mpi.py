@@ -108,19 +108,22 @@ def run(argv=None, out=sys.stdout):
         for l in model.layers:
             transport.broadcast_(l.master, 0)
         model.sync_lp()
-    start_iter, opt_step = 0, 0
+    start_iter, opt_step, sr_step = 0, 0, 0
     if cfg.resume:
         info = checkpoint.load(cfg.resume, model)
         start_iter = int(info.get("iteration", 0))
         if info.get("optimizer", "sgd") == cfg.optimizer:  # the update count belongs to the moments it was saved with
             opt_step = int(info.get("opt_step", 0))
+        sr_step = int(info.get("sr_step", 0))  # (saved by a --stochastic-rounding run only)
     trainer = DataParallelTrainer(model, engine, lr=cfg.lr, weight_decay=cfg.weight_decay, momentum=cfg.momentum,
                                   loss_scale=cfg.loss_scale, profile=cfg.profile, optimizer=cfg.optimizer,
                                   betas=(cfg.beta1, cfg.beta2), eps=cfg.eps, trust_ratio=cfg.trust_ratio,
                                   max_grad_norm=cfg.clip_grad_norm if cfg.clip_grad_norm > 0 else None,
                                   error_feedback=cfg.error_feedback,
-                                  error_feedback_codec=f"bfp_{cfg.rounding}")
+                                  error_feedback_codec=f"bfp_{cfg.rounding}",
+                                  stochastic_rounding=cfg.stochastic_rounding, sr_seed=cfg.sr_seed)
     trainer.opt_step = opt_step
+    trainer.sr_step = sr_step
     x, y = make_data(mb, sizes[0], sizes[-1], rank, cfg.seed, device, dtype)
     threads = int(os.environ.get("OMP_NUM_THREADS", "1"))
     check = abs(float(os.environ.get("CHECK", "1") or 1))  # reference: env CHECK (sw:227-228)
@@ -189,7 +192,7 @@ def run(argv=None, out=sys.stdout):
     if cfg.checkpoint and rank == 0:
         checkpoint.save(cfg.checkpoint, model, iteration=start_iter + cfg.warmup + cfg.iters, dtype=cfg.dtype,
                         meta={"bn": a.bn, "bk": a.bk, "bc": a.bc, "world": world}, optimizer=cfg.optimizer,
-                        opt_step=trainer.opt_step)
+                        opt_step=trainer.opt_step, sr_step=trainer.sr_step if cfg.stochastic_rounding else None)
     D.cleanup()
     return {"loss": loss, "s_per_iter": total / max(cfg.iters, 1), "model": model, "trainer": trainer}
 

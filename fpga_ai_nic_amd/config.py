@@ -43,6 +43,8 @@ class TrainConfig:
     trust_ratio: bool = False      # adamw: layer-wise trust ratio (LAMB)
     clip_grad_norm: float = 0.0    # > 0: clip the reduced gradient of all layers to this 2-norm (0: off)
     error_feedback: bool = False   # BFP mesh: each encoder keeps what it drops and adds it to the next step's input
+    stochastic_rounding: bool = False  # rne BFP mesh: each encoder rounds up with probability = the dropped fraction
+    sr_seed: int = 0               # the run's base seed of the stochastic rounding, an int in [0, 2^64)
     beta1: float = 0.9
     beta2: float = 0.999
     eps: float = 1e-8
@@ -89,6 +91,13 @@ def add_named_flags(ap: argparse.ArgumentParser):
                          "residual plane per layer and adds it to the next step's input; the engine then packs the "
                          "gradients itself (no GEMM-fused encode); --compress local takes the one-slot round trip "
                          "of the --rounding codec. The planes are not checkpointed: --resume restarts them at zero")
+    ap.add_argument("--stochastic-rounding", action="store_true",
+                    help="compressed mesh all-reduce (--compress bfp | bfp4, --rounding rne): every encoder rounds up "
+                         "with probability equal to the dropped fraction, so each encode is unbiased; stateless (no "
+                         "plane, no extra traffic), not with --error-feedback; the engine then packs the gradients "
+                         "itself (no GEMM-fused encode). The update counter its seeds come from is checkpointed")
+    ap.add_argument("--sr-seed", type=int, default=d.sr_seed,
+                    help="base seed of --stochastic-rounding, an int in [0, 2^64)")
     ap.add_argument("--beta1", type=float, default=d.beta1, help="AdamW first-moment decay")
     ap.add_argument("--beta2", type=float, default=d.beta2, help="AdamW second-moment decay")
     ap.add_argument("--eps", type=float, default=d.eps, help="AdamW denominator term")

@@ -233,6 +233,122 @@ def ef_reduce(slots, local, self_pos: int, e_shard: np.ndarray, codec="bfp_rne",
         return pack(y, n, c), (y - quantize(y, c)).astype(np.float32)
 
 
+# --------------------------------------------------------------------------- stochastic rounding
+# The rne codecs' encoders with an unbiased rounding: q = floor(t) + (frac(t) > u), u a counter-based random threshold.
+# One 32-bit hash word serves the 4 consecutive elements 4w..4w+3 of the padded bucket (a byte each), keyed by the
+# request's seed, the encoding rank and the stage, so the bits depend on nothing but (seed, rank, stage, element).
+SR_CODECS = (1, 4)          # bfp_rne, bfp4_rne (the trunc codec is the reference's floor: nothing to randomise)
+SR_MAX_ELEMS = 1 << 32      # element indices are 32-bit
+_M32 = 0xFFFFFFFF
+_M64 = (1 << 64) - 1
+
+
+def sr_codec(codec) -> int:
+    c = codec_id(codec)
+    if c not in SR_CODECS:
+        raise ValueError(f"stochastic rounding: bfp_rne and bfp4_rne only, got {CODEC_NAMES.get(c, c)!r}")
+    return c
+
+
+def sr_seed_check(seed) -> int:
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise ValueError(f"stochastic rounding: the seed is an int in [0, 2^64), got {seed!r}")
+    seed = int(seed)
+    if not 0 <= seed <= _M64:
+        raise ValueError(f"stochastic rounding: the seed is an int in [0, 2^64), got {seed}")
+    return seed
+
+
+def _sr_mix(x: np.ndarray) -> np.ndarray:
+    x = x ^ (x >> np.uint32(16))
+    x = x * np.uint32(0x7FEB352D)
+    x = x ^ (x >> np.uint32(15))
+    x = x * np.uint32(0x846CA68B)
+    return x ^ (x >> np.uint32(16))
+
+
+def sr_hash(k0: int, k1: int, w) -> np.ndarray:
+    """h(k0, k1, w) = mix(mix(w ^ k0) + k1) on uint32 with wraparound (w: word indices, any shape)."""
+    w = np.asarray(w, dtype=np.uint32)
+    with np.errstate(over="ignore"):
+        return _sr_mix(_sr_mix(w ^ np.uint32(k0 & _M32)) + np.uint32(k1 & _M32))
+
+
+def sr_key(seed: int, rank: int, stage: int) -> tuple[int, int]:
+    """The two key words of (request seed, encoding rank, stage: 0 the sender's pack, 1 the owner's re-encode)."""
+    seed = sr_seed_check(seed)
+    return seed & _M32, (seed >> 32) ^ (((2 * int(rank) + int(stage) + 1) * 0x9E3779B9) & _M32)
+
+
+def sr_step_seed(base: int, step: int, bucket: int) -> int:
+    """The trainer's seed of one request: update ``step`` of bucket (layer) ``bucket`` under the run's ``base``."""
+    return sr_seed_check(base) ^ ((int(step) * 0x9E3779B97F4A7C15 + int(bucket) * 0xD1B54A32D192ED03) & _M64)
+
+
+def sr_bytes(key, base: int, n: int) -> np.ndarray:
+    """The random bytes of elements base..base+n-1 (base % 4 == 0): byte i & 3 of h(key, i >> 2)."""
+    if base % 4 or n % 4 or base < 0 or base + n > SR_MAX_ELEMS:
+        raise ValueError(f"stochastic rounding: elements [{base}, {base + n}) must lie below 2^32 on multiples of 4")
+    h = sr_hash(key[0], key[1], np.arange(base >> 2, (base + n) >> 2, dtype=np.uint64).astype(np.uint32))
+    return ((h[:, None] >> (np.arange(4, dtype=np.uint32) * np.uint32(8))) & np.uint32(0xFF)).reshape(-1)
+
+
+def sr_encode_groups(x: np.ndarray, codec, key, base: int = 0):
+    """x: float32 (size % 16 == 0), element 0 at index ``base`` of the padded bucket -> (q int8 [n], E uint8 [n/16]).
+    Per group of shared exponent E (the rne encoder's own): E == 255 takes the rne encoder; otherwise, in f32,
+    t = ldexp(x, k - E), f = floor(t), d = t - f, u = (b + 0.5) / 256, q = clamp(f + (d > u), -qmax, qmax)."""
+    c = sr_codec(codec)
+    top, lim = (133, 127.0) if c == 1 else (129, 7.0)
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, GROUP)
+    E = _shared_exp(x.view(np.uint32))
+    q_rne, _ = encode_groups(x, _rounding_of(c))
+    u = ((sr_bytes(key, base, x.size).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 256)).reshape(-1, GROUP)
+    with np.errstate(over="ignore", invalid="ignore"):
+        t = np.ldexp(x, top - E.astype(np.int32)).astype(np.float32)
+        f = np.floor(t)
+        d = (t - f).astype(np.float32)
+        s = np.clip(f + (d > u).astype(np.float32), -lim, lim)
+        q = np.where(E == 255, q_rne.reshape(-1, GROUP), np.nan_to_num(s).astype(np.int8))
+    return q.reshape(-1).astype(np.int8), E.reshape(-1).astype(np.uint8)
+
+
+def sr_quantize(x: np.ndarray, codec, key, base: int = 0) -> np.ndarray:
+    """decode(stochastic encode(x)): what every rank decodes (the decoder is the codec's own)."""
+    c = sr_codec(codec)
+    q, E = sr_encode_groups(x, c, key, base)
+    return decode_groups(q, E, _rounding_of(c))
+
+
+def _sr_pack_shard(x, c, key, base):
+    q, E = sr_encode_groups(x, c, key, base)
+    return np.concatenate([pack_nibbles(q) if c == 4 else q.view(np.uint8), E])
+
+
+def sr_pack(g: np.ndarray, shard_elems: int, codec, seed: int, rank: int, self_shard: int = -1, base: int = 0):
+    """Sender stage of the stochastically rounded mesh all-reduce: every shard of ``g`` but ``self_shard`` (-1: none;
+    that one takes plain rne) is encoded with key (seed, rank, 0); element j of g is element ``base + j`` of the padded
+    bucket. Returns the wire (shards back to back)."""
+    c = sr_codec(codec)
+    key = sr_key(seed, rank, 0)
+    g = np.ascontiguousarray(g, dtype=np.float32).reshape(-1)
+    assert g.size % shard_elems == 0 and shard_elems % 256 == 0
+    out = []
+    for q in range(g.size // shard_elems):
+        sl = slice(q * shard_elems, (q + 1) * shard_elems)
+        out.append(pack(g[sl], shard_elems, c) if q == self_shard
+                   else _sr_pack_shard(g[sl], c, key, base + q * shard_elems))
+    return np.concatenate(out)
+
+
+def sr_reduce(slots, local, self_pos: int, codec, shard_elems: int, seed: int, rank: int, base: int = 0):
+    """Owner stage: :func:`reduce_slots` (slot order, slot ``self_pos`` from the dense ``local``), the sum encoded
+    stochastically with key (seed, rank, 1); ``base`` is the owner shard's first element in the padded bucket. Returns
+    the wire shard."""
+    c = sr_codec(codec)
+    acc = reduce_slots(slots, local, self_pos, c, shard_elems)
+    return _sr_pack_shard(acc, c, sr_key(seed, rank, 1), base)
+
+
 def sgd(w: np.ndarray, g: np.ndarray, lr: float, grad_scale: float = 1.0, weight_decay: float = 0.0,
         momentum: float = 0.0, mom: np.ndarray | None = None, nesterov: bool = False):
     """fp32 SGD with the kernel's operation order (fma emulated in float64, then rounded)."""

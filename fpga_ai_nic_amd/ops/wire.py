@@ -150,6 +150,69 @@ def reduce_ef(slots: torch.Tensor, n_slots: int, self_pos: int, local: torch.Ten
             as_bytes(d)[:sb].copy_(torch.from_numpy(buf))
 
 
+def _sr_check(codec, seed, rank: int, base: int, n: int) -> tuple[int, int]:
+    c = O.sr_codec(codec)
+    seed = O.sr_seed_check(seed)
+    if not 0 <= int(rank) < 16:
+        raise ValueError(f"stochastic rounding: rank in [0, 16), got {rank}")
+    if base < 0 or base % 16 or base + n > O.SR_MAX_ELEMS:
+        raise ValueError(f"stochastic rounding: elements [{base}, {base + n}) of a padded bucket of 2^32 or more "
+                         f"elements (element indices are 32-bit, base a multiple of 16)")
+    return c, seed
+
+
+def pack_sr(x: torch.Tensor, out, shard_elems: int, codec, seed: int, rank: int, self_shard: int = -1, base: int = 0,
+            peers: bool = False):
+    """:func:`pack` with stochastic rounding (``bfp_oracle.sr_pack``; ``bfp_rne`` / ``bfp4_rne``): every shard but
+    ``self_shard`` (plain rne) is encoded with key (seed, rank, 0); element j of x is element ``base + j`` of the
+    padded bucket. ``out``: one uint8 buffer (shards back to back), or a list with one uint8 buffer per shard — a
+    ``None`` entry skips that shard (at most 16 shards either way on the GPU). ``peers`` (GPU): launch as the
+    direct-P2P engine does, under its grid cap and release mode; the bits do not depend on it."""
+    n_shards = x.numel() // shard_elems
+    if x.numel() % shard_elems:
+        raise ValueError("numel must be a multiple of shard_elems")
+    c, seed = _sr_check(codec, seed, rank, int(base), x.numel())
+    sb = O.shard_bytes(c, shard_elems)
+    dsts = list(out) if isinstance(out, (list, tuple)) else [as_bytes(out)[q * sb:(q + 1) * sb] for q in range(n_shards)]
+    if len(dsts) != n_shards:
+        raise ValueError("one destination per shard")
+    if x.is_cuda:
+        _ext.require().wire_pack_sr(x, dsts, int(shard_elems), c, seed, int(rank), int(self_shard), int(base),
+                                    bool(peers))
+        return out
+    g = _np_f32(x)
+    for q, d in enumerate(dsts):
+        if d is None:
+            continue
+        sl = slice(q * shard_elems, (q + 1) * shard_elems)
+        buf = O.sr_pack(g[sl], shard_elems, c, seed, rank, 0 if q == self_shard else -1, int(base) + q * shard_elems)
+        as_bytes(d)[:sb].copy_(torch.from_numpy(buf))
+    return out
+
+
+def reduce_sr(slots: torch.Tensor, n_slots: int, self_pos: int, local: torch.Tensor, out_wire, shard_elems: int,
+              codec, seed: int, rank: int, base: int = 0, peers: bool = False):
+    """:func:`reduce` to wire with stochastic rounding (``bfp_oracle.sr_reduce``): the slots' sum (slot ``self_pos``
+    from the dense ``local``, required) is encoded with key (seed, rank, 1) into ``out_wire`` — one uint8 buffer or a
+    list of them (``None`` entries skipped), each receiving the same bytes. ``base``: the shard's first element in the
+    padded bucket; ``peers`` as :func:`pack_sr`."""
+    if local is None:
+        raise ValueError("reduce_sr: the dense local operand is required")
+    c, seed = _sr_check(codec, seed, rank, int(base), shard_elems)
+    dsts = list(out_wire) if isinstance(out_wire, (list, tuple)) else [out_wire]
+    if slots.is_cuda:
+        _ext.require().wire_reduce_sr(slots, int(n_slots), int(self_pos), local, dsts, int(shard_elems), c, seed,
+                                      int(rank), int(base), bool(peers))
+        return
+    sb = O.shard_bytes(c, shard_elems)
+    raw = _np_u8(slots)
+    slot_list = [raw[r * sb:(r + 1) * sb] for r in range(n_slots)]
+    buf = O.sr_reduce(slot_list, _np_f32(local), self_pos, c, shard_elems, seed, rank, int(base))
+    for d in dsts:
+        if d is not None:
+            as_bytes(d)[:sb].copy_(torch.from_numpy(buf))
+
+
 def sgd(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Tensor, *, codec,
         lp: torch.Tensor | None = None, mom: torch.Tensor | None = None, lr: float, grad_scale: float = 1.0,
         weight_decay: float = 0.0, momentum: float = 0.0, nesterov: bool = False, n_valid: int | None = None,

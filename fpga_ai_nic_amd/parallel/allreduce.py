@@ -145,6 +145,33 @@ def residual_request(residual, L, *, codec_id, algo, world, device, prepacked=Fa
     return residual.view(-1)
 
 
+def sr_request(sr_seed, L, *, codec_id, algo, world, prepacked=False, sharded=False, residual=None):
+    """Validate one request's ``sr_seed=`` (stochastic rounding: this rank's two encoders of the mesh schedule round up
+    with probability equal to the dropped fraction, drawing from a hash of the 64-bit request seed, the rank, the stage
+    and the element's index in the padded bucket). Returns the seed as an int, or None without one."""
+    if sr_seed is None:
+        return None
+    if residual is not None:
+        raise ValueError("stochastic rounding: not together with error feedback (sr_seed and residual: pick one)")
+    if codec_id not in wire.O.SR_CODECS:
+        raise ValueError(f"stochastic rounding: bfp_rne and bfp4_rne only, got {wire.O.CODEC_NAMES.get(codec_id, codec_id)!r}"
+                         f" (bfp_trunc is the reference's floor, a raw codec rounds nothing)")
+    if prepacked:
+        raise ValueError("stochastic rounding: not with prepacked input (the GEMM's encoding rounds to nearest)")
+    if algo != "mesh":
+        raise ValueError("stochastic rounding: mesh schedule only (the ring schedule is not supported yet)")
+    if L.chunks > 1:
+        raise ValueError("stochastic rounding: not with a chunked layout")
+    if sharded:
+        raise ValueError("stochastic rounding: not with a sharded-update engine")
+    if world > MAX_PEERS:
+        raise ValueError(f"stochastic rounding: at most {MAX_PEERS} ranks (one destination per shard), got {world}")
+    if L.n_pad >= wire.O.SR_MAX_ELEMS:
+        raise ValueError(f"stochastic rounding: a padded bucket of 2^32 or more elements ({L.n_pad}; element indices "
+                         f"are 32-bit)")
+    return wire.O.sr_seed_check(sr_seed)
+
+
 def adamw_request(opt, mom, var, *, lr, weight_decay, momentum, nesterov, betas, eps, step, trust_ratio=False,
                   n_adapt=None, n_valid=None):
     """Validate one request's optimizer arguments; the step's ``bfp_oracle.AdamWScalars`` for ``opt="adamw"``
@@ -401,7 +428,8 @@ class CompressedAllReduce:
                       name: str = "bucket", opt: str = "sgd", var: torch.Tensor | None = None,
                       betas=(0.9, 0.999), eps: float = 1e-8, step: int | None = None, trust_ratio: bool = False,
                       n_adapt: int | None = None, trust_out: torch.Tensor | None = None,
-                      clip: torch.Tensor | None = None, residual: torch.Tensor | None = None) -> Handle:
+                      clip: torch.Tensor | None = None, residual: torch.Tensor | None = None,
+                      sr_seed: int | None = None) -> Handle:
         """All-reduce ``grad`` (flat, padded to ``layout(n).n_pad``) and apply SGD to ``master`` (+bf16 ``lp``).
         ``opt="adamw"``: AdamW instead, ``mom`` / ``var`` the first / second moment planes (both required), ``step``
         the bucket's 1-based update count. ``trust_ratio`` (AdamW): scale the step of the bucket's first ``n_adapt``
@@ -412,7 +440,10 @@ class CompressedAllReduce:
         gradient, and ``commit_group`` computes the group's coefficient and commits its members. ``residual`` (f32,
         ``layout(n).n_pad`` elements, zeroed before the bucket's first request): error feedback — this rank's encoders
         (the sender's pack and the owner's re-encode) add it to their input and store what they dropped back into it;
-        the gathered wire keeps its format, so every epilogue runs unchanged. Mesh schedule and BFP codecs only."""
+        the gathered wire keeps its format, so every epilogue runs unchanged. Mesh schedule and BFP codecs only.
+        ``sr_seed`` (an int in [0, 2^64); not with ``residual``): stochastic rounding — the same two encoders round up
+        with probability equal to the dropped fraction (``bfp_oracle.sr_pack`` / ``sr_reduce``), stateless; every rank
+        passes the same seed. Mesh schedule, ``bfp_rne`` / ``bfp4_rne`` only."""
         clip_request(clip, defer, self.device)
         if clip is not None and self.compat_owner_fp32 and self.algo == "ring":
             raise ValueError("clip: not with compat_owner_fp32 (the owner's slices would be updated from another "
@@ -428,6 +459,7 @@ class CompressedAllReduce:
         n_adapt = n_valid if n_adapt is None else int(n_adapt)
         L = self.layout(n_valid)
         self._check(grad, L)
+        sr_seed = sr_request(sr_seed, L, codec_id=self.codec_id, algo=self.algo, world=self.world, residual=residual)
         residual = residual_request(residual, L, codec_id=self.codec_id, algo=self.algo, world=self.world,
                                     device=self.device)
         sgd_kw = dict(lr=lr, grad_scale=grad_scale, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov)
@@ -490,11 +522,11 @@ class CompressedAllReduce:
 
         def comm():
             if cl is not None:
-                thunks = clipped(list(self._run(L, grad, finish, owner_fp32, residual=residual)))
+                thunks = clipped(list(self._run(L, grad, finish, owner_fp32, residual=residual, sr_seed=sr_seed)))
                 if not lamb:
                     return thunks
             elif not lamb:
-                return self._run(L, grad, finish, owner_fp32, residual=residual)
+                return self._run(L, grad, finish, owner_fp32, residual=residual, sr_seed=sr_seed)
             # one partials segment per region a schedule hands to finish(): one (mesh), or one per ring
             cap = wire.lamb_partials_for(master, 1 << 40)
             tr["partials"] = self._buf(L, "lamb_partials", 16 * cap * max(1, self.rings), torch.float64, per_slot=True)
@@ -502,7 +534,7 @@ class CompressedAllReduce:
                 self._buf(L, "lamb_words", 12, torch.float32, per_slot=True)
             if cl is not None:
                 return thunks + [lamb_finish]
-            return list(self._run(L, grad, finish, owner_fp32, residual=residual)) + [lamb_finish]
+            return list(self._run(L, grad, finish, owner_fp32, residual=residual, sr_seed=sr_seed)) + [lamb_finish]
 
         h = self._launch(comm, name, L, defer, update_after)
         h._clip = cl
@@ -536,12 +568,13 @@ class CompressedAllReduce:
         return handles
 
     def allreduce(self, grad: torch.Tensor, out: torch.Tensor, *, n_valid: int | None = None,
-                  name: str = "bucket", residual: torch.Tensor | None = None) -> Handle:
+                  name: str = "bucket", residual: torch.Tensor | None = None, sr_seed: int | None = None) -> Handle:
         """Sum-only all-reduce: decoded result written to ``out`` (f32 or bf16, same padded length). ``residual``: the
-        bucket's error-feedback plane, as :meth:`allreduce_sgd`."""
+        bucket's error-feedback plane, ``sr_seed``: the request's stochastic-rounding seed, as :meth:`allreduce_sgd`."""
         n_valid = int(n_valid if n_valid is not None else grad.numel())
         L = self.layout(n_valid)
         self._check(grad, L)
+        sr_seed = sr_request(sr_seed, L, codec_id=self.codec_id, algo=self.algo, world=self.world, residual=residual)
         residual = residual_request(residual, L, codec_id=self.codec_id, algo=self.algo, world=self.world,
                                     device=self.device)
 
@@ -551,8 +584,8 @@ class CompressedAllReduce:
         def owner_fp32(buf, off, length):
             pass
 
-        return self._launch(lambda: self._run(L, grad, finish, owner_fp32, allow_compat=False, residual=residual),
-                            name, L, False, None)
+        return self._launch(lambda: self._run(L, grad, finish, owner_fp32, allow_compat=False, residual=residual,
+                                              sr_seed=sr_seed), name, L, False, None)
 
     def _check(self, grad, L):
         if grad.numel() < L.n_pad:
@@ -648,13 +681,13 @@ class CompressedAllReduce:
                 f"async_error={self.transport.async_error()!r}")
 
     # -------------------------------------------------------------------------------- execution
-    def _run(self, L, grad, finish, owner_fp32, allow_compat=True, residual=None):
+    def _run(self, L, grad, finish, owner_fp32, allow_compat=True, residual=None, sr_seed=None):
         """Issue the communication phase; returns the epilogue thunks (run now or at commit)."""
         if L.algo == "mesh":
-            return self._mesh(L, grad, finish, residual)
+            return self._mesh(L, grad, finish, residual, sr_seed)
         return self._ring(L, grad, finish, owner_fp32, allow_compat)
 
-    def _mesh(self, L, grad, finish, residual=None):
+    def _mesh(self, L, grad, finish, residual=None, sr_seed=None):
         N, r, s, c = self.world, self.rank, L.shard, self.codec_id
         sb = wire.shard_bytes(c, s)
         g = grad.view(-1)[: L.n_pad]
@@ -663,10 +696,15 @@ class CompressedAllReduce:
         # order puts step t's owner-stage store before step t + 1's pack (CPU / inline: the caller's own order). The
         # sender stage writes every shard but r, the owner stage shard r: disjoint parts of the plane.
         e = residual
+        # Stochastic rounding: `sr` (sr_request: an rne BFP codec, never with `residual`) swaps the same two encoders
+        # for their stateless stochastic forms — sender r under key (sr, r, 0), owner r under key (sr, r, 1).
+        sr = sr_seed
         S = self._buf(L, "mesh_S", sb, per_slot=N == 1 and not self.force_comm)
         if N == 1 and not self.force_comm:
             if e is not None:
                 wire.reduce_ef(S, 1, 0, g[:s], e[:s], S, s, c)
+            elif sr is not None:
+                wire.reduce_sr(S, 1, 0, g[:s], S, s, c, sr, 0)
             else:
                 wire.reduce(S, 1, 0, g[:s], S, None, s, c)
             return [lambda: finish(S, s, 1, 0, s)]
@@ -678,6 +716,8 @@ class CompressedAllReduce:
             P = self._buf(L, "mesh_P", sb * N)
             if e is not None:
                 wire.pack_ef(g, e[: L.n_pad], P, s, c, self_shard=r)
+            elif sr is not None:
+                wire.pack_sr(g, P, s, c, sr, r, self_shard=r)
             else:
                 wire.pack(g, P, s, c)
         cs = self._tag(P.view(N, sb)) if self.verify else None
@@ -690,6 +730,8 @@ class CompressedAllReduce:
             self._verify_rows(R.view(N, sb), cs_r, list(range(N)), "mesh all_to_all")
         if e is not None:
             wire.reduce_ef(R, N, r, g[r * s:(r + 1) * s], e[r * s:(r + 1) * s], S, s, c)
+        elif sr is not None:
+            wire.reduce_sr(R, N, r, g[r * s:(r + 1) * s], S, s, c, sr, r, base=r * s)
         else:
             wire.reduce(R, N, r, g[r * s:(r + 1) * s], S, None, s, c)
         G = self._buf(L, "mesh_G", sb * N, per_slot=True)

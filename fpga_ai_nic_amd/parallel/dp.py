@@ -23,7 +23,7 @@ from ..ops import gemm as G
 from ..ops import gemm_tune, wire
 from ..utils import tracing
 from ..config import wire_codec
-from .allreduce import NUM_SLOTS, OPTIMIZERS, CompressedAllReduce, Handle, _round_up
+from .allreduce import MAX_PEERS, NUM_SLOTS, OPTIMIZERS, CompressedAllReduce, Handle, _round_up
 from .transport import Transport
 
 
@@ -47,7 +47,7 @@ class RcclAllReduce(CompressedAllReduce):
         N = self.world
         return 0 if N == 1 else int(2 * (N - 1) / N * L.n_pad * 4)
 
-    def _run(self, L, grad, finish, owner_fp32, allow_compat=True, residual=None):
+    def _run(self, L, grad, finish, owner_fp32, allow_compat=True, residual=None, sr_seed=None):
         g = grad.view(-1)[: L.n_pad]
         self.transport.all_reduce_(g)
         return [lambda: finish(wire.as_bytes(g), L.n_pad, 1, 0, L.n_pad)]
@@ -88,8 +88,18 @@ class DataParallelTrainer:
                  gemm_inflight: str | None = None, wgrad_pair: bool | str | None = None, optimizer: str = "sgd",
                  betas=(0.9, 0.999), eps: float = 1e-8, trust_ratio: bool = False,
                  max_grad_norm: float | None = None, error_feedback: bool = False,
-                 error_feedback_codec: str = "bfp_rne"):
-        """``error_feedback``: error feedback (residual compensation) for the compressed mesh all-reduce — every layer
+                 error_feedback_codec: str = "bfp_rne", stochastic_rounding: bool = False, sr_seed: int = 0):
+        """``stochastic_rounding``: stochastic rounding for the compressed mesh all-reduce — every layer's request
+        carries ``sr_seed=bfp_oracle.sr_step_seed(sr_seed, sr_step, layer)``, under which this rank's two encoders round
+        up with probability equal to the dropped fraction; ``sr_step`` is the trainer's update counter (1-based,
+        advanced once per ``backward_pass``, checkpointed by the CLI). Stateless: no plane, no extra traffic; one
+        encode has about twice round-to-nearest's variance and is unbiased. ``prepack`` and hence ``fused_update`` are
+        off, as with ``error_feedback``. ``bfp_rne`` / ``bfp4_rne`` and the mesh schedule only; not with a
+        sharded-update engine, a chunked layout or ``error_feedback`` (pick one). Without an engine the local update
+        takes the gradient through the one-slot round trip (``wire.reduce_sr``) of ``error_feedback_codec``. A step
+        cannot be captured into a graph (its seed is a by-value kernel argument).
+
+        ``error_feedback``: error feedback (residual compensation) for the compressed mesh all-reduce — every layer
         bucket gets one zeroed f32 plane per rank (``residuals``), passed with the layer's request, in which this rank's
         encoders keep what they dropped and from which they add it to the next step's input. ``prepack`` and hence
         ``fused_update`` are off (the bwd-weight GEMM writes f32 and the engine packs: the GEMM's encoding carries no
@@ -187,6 +197,28 @@ class DataParallelTrainer:
                 raise ValueError("error_feedback: not with a chunked layout (a bucket above the engine's chunk_elems)")
             self.residuals = [torch.zeros(l.n_pad, dtype=torch.float32, device=model.device) for l in model.layers]
             prepack = False
+        self.stochastic_rounding = bool(stochastic_rounding)
+        self.sr_seed = wire.O.sr_seed_check(sr_seed)
+        self.sr_step = 0  # updates enqueued so far (the step of sr_step_seed; checkpointed with the flag on)
+        if self.stochastic_rounding:
+            if self.error_feedback:
+                raise ValueError("stochastic_rounding: not together with error_feedback (pick one)")
+            if wire.codec_id(self.ef_codec) not in wire.O.SR_CODECS:
+                raise ValueError(f"stochastic_rounding: bfp_rne and bfp4_rne only, got {self.ef_codec!r} (bfp_trunc is "
+                                 f"the reference's floor, a raw codec rounds nothing)")
+            if engine is not None and getattr(engine, "algo", "mesh") != "mesh":
+                raise ValueError("stochastic_rounding: mesh schedule only (the ring schedule is not supported yet)")
+            if bool(getattr(engine, "shard_update", False)):
+                raise ValueError("stochastic_rounding: not with a sharded-update engine")
+            if engine is not None and any(getattr(engine.layout(l.n), "chunks", 1) > 1 for l in model.layers):
+                raise ValueError("stochastic_rounding: not with a chunked layout (a bucket above the engine's "
+                                 "chunk_elems)")
+            if self.world > MAX_PEERS:
+                raise ValueError(f"stochastic_rounding: at most {MAX_PEERS} ranks, got {self.world}")
+            if any(l.n_pad >= wire.O.SR_MAX_ELEMS for l in model.layers):
+                raise ValueError("stochastic_rounding: a padded bucket of 2^32 or more elements (element indices are "
+                                 "32-bit)")
+            prepack = False
         self.loss_scale = loss_scale
         # gradients are of the LOCAL mean loss; the all-reduce sums over ranks -> average with 1/N
         self.grad_scale = (1.0 / self.world) if average else 1.0
@@ -250,10 +282,13 @@ class DataParallelTrainer:
             self.last_on_producer = False
 
     def _opt_kw(self, l):
-        """The optimizer, clip-group and error-feedback arguments of layer l's request in the step being enqueued."""
+        """The optimizer, clip-group, error-feedback and stochastic-rounding arguments of layer l's request in the step
+        being enqueued."""
         kw = {} if self.grad_norm is None else dict(clip=self.grad_norm)
         if self.residuals is not None:
             kw["residual"] = self.residuals[self._index(l)]
+        if self.stochastic_rounding:
+            kw["sr_seed"] = self._sr_seed_of(l)
         if self.optimizer != "adamw":
             return kw
         kw.update(opt="adamw", var=l.var, betas=self.betas, eps=self.eps, step=self.opt_step)
@@ -270,20 +305,32 @@ class DataParallelTrainer:
 
     def _local_src(self, l):
         """(wire bytes, their codec) the engine-less update of layer l reads: the f32 gradient itself as raw_f32, or
-        with error feedback the one-slot wire ``_ef_local`` encoded this step."""
-        if self.residuals is None:
+        with error feedback or stochastic rounding the one-slot wire ``_ef_local`` / ``_sr_local`` encoded this step."""
+        if self.residuals is None and not self.stochastic_rounding:
             return wire.as_bytes(l.grad), "raw_f32"
         return self._ef_wire[self._index(l)], self.ef_codec
+
+    def _local_wire(self, l):
+        if self._ef_wire is None:
+            self._ef_wire = [torch.zeros(wire.shard_bytes(self.ef_codec, x.n_pad), dtype=torch.uint8,
+                                         device=x.grad.device) for x in self.m.layers]
+        return self._ef_wire[self._index(l)]
 
     def _ef_local(self, l):
         """Engine-less error feedback: layer l's gradient plus its residual through the codec's round trip at one
         slot (the owner stage alone, as a one-rank engine)."""
-        if self._ef_wire is None:
-            self._ef_wire = [torch.zeros(wire.shard_bytes(self.ef_codec, x.n_pad), dtype=torch.uint8,
-                                         device=x.grad.device) for x in self.m.layers]
-        i = self._index(l)
-        S = self._ef_wire[i]
-        wire.reduce_ef(S, 1, 0, l.grad, self.residuals[i], S, l.n_pad, self.ef_codec)
+        S = self._local_wire(l)
+        wire.reduce_ef(S, 1, 0, l.grad, self.residuals[self._index(l)], S, l.n_pad, self.ef_codec)
+
+    def _sr_seed_of(self, l):
+        """The seed of layer l's request in the step being enqueued."""
+        return wire.O.sr_step_seed(self.sr_seed, self.sr_step, self._index(l))
+
+    def _sr_local(self, l):
+        """Engine-less stochastic rounding: layer l's gradient through the stochastic round trip at one slot (the
+        owner stage alone, as a one-rank engine)."""
+        S = self._local_wire(l)
+        wire.reduce_sr(S, 1, 0, l.grad, S, l.n_pad, self.ef_codec, self._sr_seed_of(l), 0)
 
     def _n_adapt(self, l):
         """The adapted tensor of layer l's bucket: its weight matrix; the bias segment behind it takes ratio 1."""
@@ -386,7 +433,10 @@ class DataParallelTrainer:
         if self.optimizer == "adamw" and self.cuda and torch.cuda.is_current_stream_capturing():
             # the step's scalars are by-value kernel arguments: a captured graph would replay step 1's for ever
             raise RuntimeError("an AdamW step cannot be captured into a graph (its per-step scalars would be frozen)")
+        if self.stochastic_rounding and self.cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("a stochastically rounded step cannot be captured into a graph (its seed would be frozen)")
         self.opt_step += 1
+        self.sr_step += 1
         self._wait_updates()  # no-op after forward_pass; needed when backward passes run back to back
         t0 = time.perf_counter()
         with tracing.range("loss"):
@@ -444,6 +494,8 @@ class DataParallelTrainer:
                             self._gemm_grid(True)
                         elif self.residuals is not None:
                             self._ef_local(l)
+                        elif self.stochastic_rounding:
+                            self._sr_local(l)
                         m.backward_data(i)
                         if h is not None:
                             clipped = self.grad_norm is not None  # (commits with its group, below)

@@ -24,7 +24,7 @@ import torch
 from .. import _ext
 from ..ops import wire
 from .allreduce import (CLIP_GROUP_LIMIT, NUM_SLOTS, BucketLayout, ChecksumError, CommTimeoutError, adamw_request,
-                        clip_group_check, clip_request, residual_request)
+                        clip_group_check, clip_request, residual_request, sr_request)
 from .transport import NativeTransport, Transport
 
 _ALGOS = {"mesh": 0, "ring": 1}
@@ -259,7 +259,7 @@ class NativeAllReduce:
                       opt: str = "sgd", var: torch.Tensor | None = None, betas=(0.9, 0.999), eps: float = 1e-8,
                       step: int | None = None, trust_ratio: bool = False, n_adapt: int | None = None,
                       trust_out: torch.Tensor | None = None, clip: torch.Tensor | None = None,
-                      residual: torch.Tensor | None = None) -> NativeHandle:
+                      residual: torch.Tensor | None = None, sr_seed: int | None = None) -> NativeHandle:
         """``opt="adamw"``: AdamW instead of SGD, ``mom`` / ``var`` the first / second moment planes (both required),
         ``step`` the bucket's 1-based update count (as :meth:`CompressedAllReduce.allreduce_sgd`). ``trust_ratio`` /
         ``n_adapt`` / ``trust_out``: the layer-wise trust ratio (LAMB), as there; refused with the sharded update, a
@@ -273,9 +273,11 @@ class NativeAllReduce:
         :meth:`commit_group` (as :meth:`CompressedAllReduce.allreduce_sgd`); refused where the trust ratio is.
         ``residual`` (f32, ``layout(n).n_pad`` elements, zeroed before the bucket's first request): error feedback, as
         :meth:`CompressedAllReduce.allreduce_sgd`; mesh and BFP codecs only, not with ``prepacked``, a chunked layout
-        or the sharded update."""
+        or the sharded update. ``sr_seed`` (an int in [0, 2^64)): stochastic rounding under that request seed, as
+        :meth:`CompressedAllReduce.allreduce_sgd`; refused where ``residual`` is, and together with it."""
         n_valid = int(n_valid if n_valid is not None else master.numel())
         clip_request(clip, defer, self.device)
+        sr_seed = self._sr(sr_seed, n_valid, prepacked, layout, residual)
         residual = self._residual(residual, n_valid, prepacked, layout)
         scalars = adamw_request(opt, mom, var, lr=lr, weight_decay=weight_decay, momentum=momentum,
                                 nesterov=nesterov, betas=betas, eps=eps, step=step, trust_ratio=trust_ratio,
@@ -308,6 +310,8 @@ class NativeAllReduce:
             okw = dict(okw, clip=clip.view(-1))
         if residual is not None:
             okw = dict(okw, residual=residual)
+        if sr_seed is not None:
+            okw = dict(okw, sr=True, sr_seed=sr_seed)
         # an immediate request (no ordering after the producer's later work) is committed by the engine itself, so
         # a chunked bucket runs its per-chunk epilogues inside the pipeline (bounded scratch)
         eng_defer = defer or update_after is not None
@@ -347,15 +351,19 @@ class NativeAllReduce:
         return handles
 
     def allreduce(self, grad: torch.Tensor, out: torch.Tensor, *, n_valid: int | None = None,
-                  name: str = "bucket", prepacked=None, residual: torch.Tensor | None = None) -> NativeHandle:
+                  name: str = "bucket", prepacked=None, residual: torch.Tensor | None = None,
+                  sr_seed: int | None = None) -> NativeHandle:
         """Sum-only all-reduce: decoded f32 result written to ``out`` (padded length). ``residual``: the bucket's
-        error-feedback plane, as :meth:`allreduce_sgd`."""
+        error-feedback plane, ``sr_seed``: the request's stochastic-rounding seed, as :meth:`allreduce_sgd`."""
         n_valid = int(n_valid if n_valid is not None else grad.numel())
         if out.dtype != torch.float32:
             raise TypeError("native allreduce writes f32 sums")
         pre, pre_n = (None, 0) if prepacked is None else prepacked
+        sr_seed = self._sr(sr_seed, n_valid, prepacked, None, residual)
         residual = self._residual(residual, n_valid, prepacked, None)
         okw = {} if residual is None else dict(residual=residual)
+        if sr_seed is not None:
+            okw = dict(okw, sr=True, sr_seed=sr_seed)
         slot = self.C.submit(grad.view(-1), out.view(-1), None, None, n_valid, 0.0, 1.0, 0.0, 0.0, False, False,
                              False, out.view(-1), pre, int(pre_n), **okw)
         self._account(n_valid)
@@ -369,6 +377,15 @@ class NativeAllReduce:
         return residual_request(residual, self.layout(n_valid, ls, lc), codec_id=self.codec_id, algo=self.algo,
                                 world=self.world, device=self.device, prepacked=prepacked is not None,
                                 sharded=self.shard_update)
+
+    def _sr(self, sr_seed, n_valid, prepacked, layout, residual):
+        """A request's validated stochastic-rounding seed, or None."""
+        if sr_seed is None:
+            return None
+        ls, lc = (0, 0) if layout is None else (int(layout[0]), int(layout[1]))
+        return sr_request(sr_seed, self.layout(n_valid, ls, lc), codec_id=self.codec_id, algo=self.algo,
+                          world=self.world, prepacked=prepacked is not None, sharded=self.shard_update,
+                          residual=residual)
 
     def _account(self, n):
         self.stats["requests"] += 1

@@ -87,3 +87,23 @@ def mesh_allreduce_ef(grads: list[np.ndarray], residuals: list[np.ndarray], shar
         out[sl] = _enc_dec(y, codec)
         new[s][sl] = (y - out[sl]).astype(f32)
     return out, new
+
+
+def mesh_allreduce_sr(grads: list[np.ndarray], shard: int, codec="bfp_rne", seed: int = 0) -> np.ndarray:
+    """The mesh all-reduce with stochastic rounding under the request seed ``seed``: sender r encodes shard q != r of
+    its gradient with key (seed, r, 0), owner s sums the decoded slots in rank order (its own g_s[s] un-quantised) and
+    re-encodes the sum with key (seed, s, 1); element i of the padded bucket draws byte i & 3 of hash word i >> 2.
+    Returns the decoded result every rank ends up with. One rank: the owner stage alone."""
+    N = len(grads)
+    f32 = np.float32
+    out = np.zeros(shard * N, f32)
+    for s in range(N):
+        sl = slice(s * shard, (s + 1) * shard)
+        acc = np.zeros(shard, f32)
+        for r in range(N):
+            v = grads[r][sl].astype(f32)
+            if r != s:
+                v = O.sr_quantize(v, codec, O.sr_key(seed, r, 0), s * shard)
+            acc = (acc + v).astype(f32)
+        out[sl] = O.sr_quantize(acc, codec, O.sr_key(seed, s, 1), s * shard)
+    return out

@@ -6,7 +6,8 @@ defines the on-disk format as exactly that:
 
 * ``<path>.safetensors`` — tensors ``fc{i}.weight`` [C_i, C_{i+1}] and ``fc{i}.bias`` [C_{i+1}] in f32 (or bf16),
   optional ``fc{i}.momentum`` (flat, f32), or for an AdamW model ``fc{i}.exp_avg`` / ``fc{i}.exp_avg_sq`` (its two
-  moment planes, flat, f32; the index then carries ``optimizer`` and ``opt_step``, the updates applied so far);
+  moment planes, flat, f32; the index then carries ``optimizer`` and ``opt_step``, the updates applied so far; a
+  stochastically rounded run adds ``sr_step``, the update counter its request seeds are derived from);
 * ``<path>.json`` — index: layer shapes / dtypes / byte offsets into a plain concatenated ``.bin`` image, the
   libxsmm blocking ``bn/bk/bc`` as metadata, iteration counter, world size and engine settings.
 * ``<path>.bin`` — the raw concatenation (weight_0, bias_0, weight_1, ...) so a C/C++ consumer (e.g. the
@@ -25,7 +26,7 @@ from safetensors.torch import load_file, save_file
 
 
 def save(path: str, model, *, iteration: int = 0, dtype: str = "f32", meta: dict | None = None,
-         optimizer: str | None = None, opt_step: int | None = None):
+         optimizer: str | None = None, opt_step: int | None = None, sr_step: int | None = None):
     tdt = torch.float32 if dtype == "f32" else torch.bfloat16
     tensors, index, off = {}, [], 0
     blobs = []
@@ -55,6 +56,8 @@ def save(path: str, model, *, iteration: int = 0, dtype: str = "f32", meta: dict
         info["optimizer"] = optimizer
     if opt_step is not None:
         info["opt_step"] = int(opt_step)
+    if sr_step is not None:  # the stochastic-rounding trainer's update counter (the step of its request seeds)
+        info["sr_step"] = int(sr_step)
     info.update(meta or {})
     with open(path + ".json", "w") as f:
         json.dump(info, f, indent=1)
