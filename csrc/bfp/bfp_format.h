@@ -573,7 +573,9 @@ __device__ __forceinline__ int32_t bfp_encode_sr(float x, uint32_t E, uint32_t b
 
 // The mantissas of kVals (4 or 16) consecutive values of a group of shared exponent E, first element i of the padded
 // bucket (i % 4 == 0), packed as the wire holds them: 8-bit codec value j in byte j, 4-bit value j in nibble j.
-template <int C, int kVals>
+// kFloor1 (the 8-bit optimizer state's r = sqrt(v) plane, ops/bfp_oracle.py moment_encode): a positive value of a
+// finite group is never stored as 0, q = max(q, 1); the unflagged instantiation is the wire's encoder, unchanged.
+template <int C, int kVals, bool kFloor1 = false>
 __device__ __forceinline__ void sr_encode_vals(const float (&v)[kVals], uint32_t E, SrKey key, uint32_t i,
                                                uint32_t (&w)[(kVals * (C == kBfp4Rne ? 4 : 8) + 31) / 32]) {
   constexpr int kBits = C == kBfp4Rne ? 4 : 8;
@@ -587,7 +589,8 @@ __device__ __forceinline__ void sr_encode_vals(const float (&v)[kVals], uint32_t
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int e = 4 * g + j;
-        const int32_t q = bfp_encode_sr<C>(v[e], E, (h >> (8 * j)) & 0xFFu);
+        int32_t q = bfp_encode_sr<C>(v[e], E, (h >> (8 * j)) & 0xFFu);
+        if constexpr (kFloor1) q = v[e] > 0.0f ? max(q, 1) : q;
         w[(e * kBits) >> 5] |= ((uint32_t)q & kMask) << ((e * kBits) & 31);
       }
     }
@@ -838,6 +841,25 @@ void launch_wire_reduce_adamw(int codec, int local_dtype, const void* slots, siz
                               int self_pos, const void* local, float* master, float* mom, AdamWParams p,
                               size_t n_valid, const WirePtrs& dst, int n_dst, size_t n_s, bool peers,
                               hipStream_t stream);
+// AdamW with both moments in 8-bit block floating point (moment_codec "bfp8"; ops/bfp_oracle.py adamw_q defines the
+// bits). mom_q / var_q: the bucket's WHOLE planes, each [int8 mant[plane_elems]][u8 exp[plane_elems/16]] (the kBfpRne
+// shard layout of one shard of plane_elems elements, 16-B aligned, plane_elems % 256 == 0 and below 2^32), the first
+// holding m, the second r = sqrt(v). The wire region (launch_wire_adamw's traversal: every wire codec, shards, skipped
+// shards, shard_stride, the n_valid tail, the clip words' one product) starts at element elem_base (% 256 == 0) of the
+// bucket: region element e reads and writes mant[elem_base + e] and exp[(elem_base + e) / 16], and master / lp at e.
+// Per element: m_old, r_old decoded, v_old = r_old * r_old, adamw_update unchanged, m' and r' = sqrtf(v') encoded per
+// group with the stochastic encoder under sr_key(seed, 16, 0) / sr_key(seed, 16, 1), r' with the floor (kFloor1). In a
+// group that straddles n_valid the values at or past it enter the encode as 0; groups entirely past it keep their
+// bytes. The bits do not depend on the grid.
+constexpr int kMomentRank = 16;  // sr_key's rank slot of the state's random bytes (the wire uses ranks 0..15)
+void launch_wire_adamw_q(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
+                         float* master, bf16_t* lp, uint8_t* mom_q, uint8_t* var_q, size_t plane_elems,
+                         size_t elem_base, AdamWParams p, uint64_t seed, size_t n_valid, hipStream_t stream,
+                         size_t shard_stride = 0, const float* clip = nullptr);
+// Workgroup cap of launch_wire_adamw_q below the wire kernels' own (0, the default: none), settable at run time like
+// set_p2p_grid_cap: the bits do not depend on the grid, which is what a one-block launch shows.
+int moment_grid_cap();
+void set_moment_grid_cap(int blocks);
 // BFP codecs: the lane-contiguous form of that kernel, 4 values per lane (1, default) or one 16-value group per lane
 // (0) (FAN_WIRE_REDUCE4); bit-identical either way
 void set_wire_reduce4(int on);

@@ -452,6 +452,96 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
+// ---------------------------------------------------------------- AdamW with 8-bit moment planes (moment_codec bfp8)
+// wire_sgd_kernel's traversal (shards, skipped shards, shard stride, the n_valid tail, the clip words' one product)
+// with both moments read from and written to the bucket's 8-bit planes (bfp_format.h launch_wire_adamw_q). A lane owns
+// a whole 16-value group per trip: the planes' shared exponents then need no cross-lane exchange (the 8-per-lane body's
+// `continue` on e >= n_valid would leave lanes out of a shuffle), a plane's mantissas are ONE 16-B load and ONE 16-B
+// store, and the exponent bytes go as WireLane16's: a byte load per lane, and the 16 bytes of 16 consecutive lanes
+// leave as one 16-B store by lane 16k. A 16-lane segment covers 256 consecutive elements from a multiple of 256 (grid
+// and stride are multiples of 256 lanes, n_s, elem_base and plane_elems multiples of 256), so it is entirely inside the
+// `t` loop or outside it, and entirely inside the planes when its first group is below n_valid; its lanes past n_valid
+// carry their group's OLD exponent byte through the gather, so groups the update does not touch keep their bytes.
+// No atomics, no LDS, no scratch (every array index is a compile-time constant).
+template <int C, bool HAS_LP, bool CLIP>
+__global__ void __launch_bounds__(kBlock)
+    wire_adamw_q_kernel(const uint8_t* __restrict__ wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
+                        float* __restrict__ master, bf16_t* __restrict__ lp, uint8_t* mom_q, uint8_t* var_q,
+                        size_t plane_elems, size_t elem_base, AdamWParams p, SrKey key_m, SrKey key_r, size_t n_valid,
+                        size_t sb, const float* __restrict__ clip) {
+  if constexpr (CLIP) p.grad_scale = p.grad_scale * clip[0];  // (as wire_sgd_kernel)
+  const size_t tasks = n_s >> 4;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  uint8_t* const mom_e = mom_q + plane_elems;
+  uint8_t* const var_e = var_q + plane_elems;
+  const size_t seg_lane = (size_t)(threadIdx.x & 15) << 4;  // elements between the segment's first group and this one
+  for (int s = 0; s < n_shards; ++s) {
+    if (skip_shard >= 0 && (s % skip_period) == skip_shard) continue;
+    const uint8_t* src = wire + (size_t)s * sb;
+    const size_t base = (size_t)s * n_s;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
+      const size_t e = base + (t << 4);
+      if (e - seg_lane >= n_valid) continue;  // the whole 16-lane segment is past n_valid: all its lanes leave
+      const size_t i = elem_base + e;          // the group's first element in the padded bucket
+      const bool act = e < n_valid;
+      uint32_t Em = mom_e[i >> 4], Er = var_e[i >> 4];
+      if (act) {
+        float g[16], w[16], m[16], r[16];
+        WireLane16<C>::load16(src, n_s, t << 4, g);
+        DenseLane16<float>::load16(master, e, w);
+        const uint4 qm = *reinterpret_cast<const uint4*>(mom_q + i);
+        const uint4 qr = *reinterpret_cast<const uint4*>(var_q + i);
+        const uint32_t qmw[4] = {qm.x, qm.y, qm.z, qm.w}, qrw[4] = {qr.x, qr.y, qr.z, qr.w};
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          m[j] = bfp_decode_rne((int32_t)(int8_t)(uint8_t)(qmw[j >> 2] >> (8 * (j & 3))), Em);
+          const float ro = bfp_decode_rne((int32_t)(int8_t)(uint8_t)(qrw[j >> 2] >> (8 * (j & 3))), Er);
+          float v = ro * ro;
+          adamw_update(p, g[j], w[j], m[j], v);
+          r[j] = sqrtf(v);  // the value adamw_update's denominator used
+        }
+        if (e + 16 <= n_valid) {
+          DenseLane16<float>::store16(master, e, w);
+          if (HAS_LP) DenseLane16<bf16_t>::store16(lp, e, w);
+        } else {
+          // the group straddles n_valid: values at or past it keep their weights and enter the encode as 0
+#pragma unroll
+          for (int j = 0; j < 16; ++j) {
+            if (e + j < n_valid) {
+              master[e + j] = w[j];
+              if (HAS_LP) lp[e + j] = f32_to_bf16(w[j]);
+            } else {
+              m[j] = 0.0f;
+              r[j] = 0.0f;
+            }
+          }
+        }
+        Em = SrLanes<Lanes16<kBfpRne>>::exponent(m);
+        Er = SrLanes<Lanes16<kBfpRne>>::exponent(r);
+        uint32_t wm[4], wr[4];
+        sr_encode_vals<kBfpRne, 16>(m, Em, key_m, (uint32_t)i, wm);
+        sr_encode_vals<kBfpRne, 16, true>(r, Er, key_r, (uint32_t)i, wr);
+        *reinterpret_cast<uint4*>(mom_q + i) = make_uint4(wm[0], wm[1], wm[2], wm[3]);
+        *reinterpret_cast<uint4*>(var_q + i) = make_uint4(wr[0], wr[1], wr[2], wr[3]);
+      }
+      // exponent planes: 4 lanes -> one dword, 4 dwords -> one 16-B store by lane 16k (WireLane16); every lane of the
+      // segment is here
+      uint32_t a4 = Em | ((uint32_t)__shfl_down((int)Em, 1) << 8) | ((uint32_t)__shfl_down((int)Em, 2) << 16) |
+                    ((uint32_t)__shfl_down((int)Em, 3) << 24);
+      uint32_t b4 = Er | ((uint32_t)__shfl_down((int)Er, 1) << 8) | ((uint32_t)__shfl_down((int)Er, 2) << 16) |
+                    ((uint32_t)__shfl_down((int)Er, 3) << 24);
+      const uint32_t a4b = (uint32_t)__shfl_down((int)a4, 4), a4c = (uint32_t)__shfl_down((int)a4, 8),
+                     a4d = (uint32_t)__shfl_down((int)a4, 12);
+      const uint32_t b4b = (uint32_t)__shfl_down((int)b4, 4), b4c = (uint32_t)__shfl_down((int)b4, 8),
+                     b4d = (uint32_t)__shfl_down((int)b4, 12);
+      if ((threadIdx.x & 15) == 0) {
+        *reinterpret_cast<uint4*>(mom_e + (i >> 4)) = make_uint4(a4, a4b, a4c, a4d);
+        *reinterpret_cast<uint4*>(var_e + (i >> 4)) = make_uint4(b4, b4b, b4c, b4d);
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------- trust-ratio (LAMB) epilogue
 // Fixed-order fp64 sum over the workgroup: the wave's lanes by shuffles (32, 16, ... 1), then the waves' sums in wave
 // order by thread 0 through LDS. Every thread of the block must call it; the result is valid in thread 0.
@@ -825,6 +915,46 @@ void launch_wire_adamw(int codec, const void* wire, size_t n_s, int n_shards, in
     else FAN_ADAMW(false, false);
   });
 #undef FAN_ADAMW
+  FAN_HIP_CHECK(hipGetLastError());
+}
+
+static std::atomic<int>& moment_grid_flag() {
+  static std::atomic<int> g{0};
+  return g;
+}
+int moment_grid_cap() { return moment_grid_flag().load(std::memory_order_relaxed); }
+void set_moment_grid_cap(int blocks) { moment_grid_flag().store(blocks > 0 ? blocks : 0); }
+
+void launch_wire_adamw_q(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
+                         float* master, bf16_t* lp, uint8_t* mom_q, uint8_t* var_q, size_t plane_elems,
+                         size_t elem_base, AdamWParams p, uint64_t seed, size_t n_valid, hipStream_t stream,
+                         size_t shard_stride, const float* clip) {
+  FAN_CHECK(master != nullptr && mom_q != nullptr && var_q != nullptr, "wire_adamw_q: master and both moment planes");
+  FAN_CHECK(plane_elems % 256 == 0 && elem_base % 256 == 0, "wire_adamw_q: plane_elems and elem_base are multiples of 256");
+  FAN_CHECK((uint64_t)plane_elems < ((uint64_t)1 << 32),
+            "wire_adamw_q: a padded bucket of 2^32 or more elements (element indices are 32-bit)");
+  FAN_CHECK(((uintptr_t)mom_q | (uintptr_t)var_q) % 16 == 0, "wire_adamw_q: the planes are 16-byte aligned");
+  if (skip_period < 1) skip_period = 1 << 30;
+  check_ns(n_s);
+  if (n_s == 0 || n_shards == 0 || n_valid == 0) return;
+  FAN_CHECK(n_valid <= n_s * (size_t)n_shards, "wire_adamw_q: n_valid beyond the wire region");
+  FAN_CHECK(elem_base <= plane_elems && n_valid <= plane_elems - elem_base,
+            "wire_adamw_q: the region's valid elements must lie inside the planes");
+  const int cap = moment_grid_cap();
+  const int grid = stream_grid(n_s / 16, kBlock, cap > 0 ? std::min(cap, wire_max_blocks()) : wire_max_blocks());
+  const uint8_t* w = (const uint8_t*)wire;
+  const SrKey km = sr_key(seed, kMomentRank, 0), kr = sr_key(seed, kMomentRank, 1);
+#define FAN_ADAMW_Q(LP, CLIP)                                                                                    \
+  hipLaunchKernelGGL((wire_adamw_q_kernel<C, LP, CLIP>), grid, kBlock, 0, stream, w, n_s, n_shards, skip_shard,  \
+                     skip_period, master, lp, mom_q, var_q, plane_elems, elem_base, p, km, kr, n_valid, sb, clip)
+  FAN_CODEC_SWITCH(codec, {
+    const size_t sb = shard_stride ? shard_stride : wire_shard_bytes(C, n_s);
+    if (lp && clip) FAN_ADAMW_Q(true, true);
+    else if (lp) FAN_ADAMW_Q(true, false);
+    else if (clip) FAN_ADAMW_Q(false, true);
+    else FAN_ADAMW_Q(false, false);
+  });
+#undef FAN_ADAMW_Q
   FAN_HIP_CHECK(hipGetLastError());
 }
 

@@ -252,7 +252,8 @@ void register_engine(pybind11::module_& m) {
               int64_t layout_chunks, bool on_producer, int64_t opt, c10::optional<at::Tensor> var,
               c10::optional<std::vector<double>> adamw, c10::optional<std::vector<double>> lamb, int64_t n_adapt,
               c10::optional<at::Tensor> trust_out, c10::optional<at::Tensor> clip,
-              c10::optional<at::Tensor> residual, bool sr, uint64_t sr_seed) {
+              c10::optional<at::Tensor> residual, bool sr, uint64_t sr_seed, c10::optional<at::Tensor> mom_q,
+              c10::optional<at::Tensor> var_q, uint64_t moment_seed) {
              FAN_T_CUDA_CONTIG(grad);
              TORCH_CHECK(grad.scalar_type() == at::kFloat || grad.scalar_type() == at::kBFloat16,
                          "gradients must be f32 or bf16");
@@ -303,11 +304,31 @@ void register_engine(pybind11::module_& m) {
              }
              req.upd.sgd = SgdParams{(float)lr, (float)grad_scale, (float)wd, (float)momentum, nesterov ? 1 : 0};
              TORCH_CHECK(opt == kOptSgd || opt == kOptAdamW, "opt: 0 (SGD) or 1 (AdamW)");
+             TORCH_CHECK(opt == kOptAdamW || !(mom_q && mom_q->defined()),
+                         "moment_codec bfp8: AdamW only (SGD keeps no second moment)");
              if (opt == kOptAdamW) {
                TORCH_CHECK(adamw.has_value(), "AdamW needs its scalars");
-               TORCH_CHECK(!update || (req.mom != nullptr && var && var->defined()),
+               const bool mq = mom_q && mom_q->defined();
+               if (mq) {  // 8-bit state: the two uint8 planes stand in for mom / var
+                 TORCH_CHECK(update, "moment_codec bfp8: update requests only");
+                 TORCH_CHECK(!lamb.has_value(), "moment_codec bfp8: not with the trust ratio (its pass 2 recomputes from "
+                                                "the stored moments)");
+                 TORCH_CHECK(req.mom == nullptr && !(var && var->defined()),
+                             "moment_codec bfp8: the state lives in mom_q / var_q, not in f32 planes (mom, var)");
+                 TORCH_CHECK(var_q && var_q->defined(), "moment_codec bfp8: both moment planes (mom_q, var_q)");
+                 TORCH_CHECK(master.numel() >= L.n_pad, "AdamW: master must be padded to the layout's ", L.n_pad,
+                             " elements");
+                 req.mom_q = fan_moment_plane(*mom_q, L.n_pad, grad);
+                 req.var_q = fan_moment_plane(*var_q, L.n_pad, grad);
+                 req.upd.kind = kOptAdamW;
+                 req.upd.adamw = fan_adamw_scalars(*adamw, grad_scale, wd);
+                 req.moment_q = true;
+                 req.moment_seed = moment_seed;
+                 req.moment_elems = L.n_pad;
+               }
+               TORCH_CHECK(!update || mq || (req.mom != nullptr && var && var->defined()),
                            "AdamW needs both moment planes (mom, var)");
-               if (update) {
+               if (update && !mq) {
                  // the kernels read the planes a whole lane (and, in the owner reduce, a whole shard) at a time
                  TORCH_CHECK(var->numel() >= L.n_pad && mom->numel() >= L.n_pad && master.numel() >= L.n_pad,
                              "AdamW: master, mom and var must be padded to the layout's ", L.n_pad, " elements");
@@ -351,7 +372,8 @@ void register_engine(pybind11::module_& m) {
            py::arg("on_producer") = false, py::arg("opt") = 0, py::arg("var") = py::none(),
            py::arg("adamw") = py::none(), py::arg("lamb") = py::none(), py::arg("n_adapt") = -1,
            py::arg("trust_out") = py::none(), py::arg("clip") = py::none(), py::arg("residual") = py::none(),
-           py::arg("sr") = false, py::arg("sr_seed") = 0,
+           py::arg("sr") = false, py::arg("sr_seed") = 0, py::arg("mom_q") = py::none(),
+           py::arg("var_q") = py::none(), py::arg("moment_seed") = 0,
            py::call_guard<py::gil_scoped_release>())
       .def("prepack_shape", [](AllReduceEngine& e, int64_t n) {
         const auto s = e.prepack_shape(n);

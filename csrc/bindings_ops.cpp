@@ -522,6 +522,63 @@ void wire_reduce_sr(const at::Tensor& slots, int64_t n_slots, int64_t self_pos, 
                         to, (int)dsts.size(), (size_t)shard_elems, key, (size_t)base, peers, fan_stream());
 }
 
+// AdamW with 8-bit moment planes (bfp_format.h launch_wire_adamw_q): `mom_q` / `var_q` are the bucket's whole planes
+// (uint8, plane_elems * 17 / 16 bytes), `elem_base` the bucket index of the wire region's element 0.
+void wire_adamw_q(const at::Tensor& wire, int64_t shard_elems, int64_t n_shards, int64_t skip_shard, int64_t skip_period,
+                  at::Tensor& master, const c10::optional<at::Tensor>& lp, at::Tensor& mom_q, at::Tensor& var_q,
+                  const std::vector<double>& scalars, double grad_scale, double weight_decay, pybind11::int_ seed,
+                  int64_t n_valid, int64_t codec, int64_t shard_stride, const c10::optional<at::Tensor>& clip,
+                  int64_t elem_base) {
+  FAN_T_CUDA_CONTIG(wire);
+  FAN_T_CUDA_CONTIG(master);
+  FAN_T_CUDA_CONTIG(mom_q);
+  FAN_T_CUDA_CONTIG(var_q);
+  TORCH_CHECK(shard_elems > 0 && shard_elems % 256 == 0 && n_shards > 0, "shard_elems: a positive multiple of 256");
+  TORCH_CHECK(n_valid >= 0 && n_valid <= shard_elems * n_shards, "n_valid beyond the wire region");
+  TORCH_CHECK(master.scalar_type() == at::kFloat, "master weights must be float32");
+  TORCH_CHECK(master.numel() >= (n_valid + 15) / 16 * 16, "master must hold n_valid rounded up to 16 elements");
+  TORCH_CHECK(mom_q.scalar_type() == at::kByte && var_q.scalar_type() == at::kByte && mom_q.numel() == var_q.numel() &&
+                  mom_q.numel() % (17 * 16) == 0,
+              "moment planes: two uint8 tensors of n_pad * 17 / 16 bytes (n_pad a multiple of 256)");
+  TORCH_CHECK(mom_q.device() == master.device() && var_q.device() == master.device() &&
+                  wire.device() == master.device(),
+              "moment planes: on the master weights' device");
+  const int64_t plane_elems = mom_q.numel() / 17 * 16;
+  TORCH_CHECK(plane_elems < ((int64_t)1 << 32), "moment planes: a padded bucket of 2^32 or more elements");
+  TORCH_CHECK(elem_base >= 0 && elem_base % 256 == 0 && elem_base + n_valid <= plane_elems,
+              "elem_base: a multiple of 256 with the region's valid elements inside the planes");
+  const size_t sb = wire_shard_bytes((int)codec, shard_elems);
+  TORCH_CHECK(shard_stride == 0 || (size_t)shard_stride >= sb, "shard_stride below the packed shard size");
+  TORCH_CHECK(shard_stride % 16 == 0, "shard_stride must keep 16-byte alignment");
+  const size_t need = shard_stride ? (size_t)shard_stride * (n_shards - 1) + sb : sb * n_shards;
+  TORCH_CHECK((size_t)wire.numel() * wire.element_size() >= need, "wire buffer too small");
+  bf16_t* lpp = nullptr;
+  if (lp) {
+    FAN_T_CUDA_CONTIG((*lp));
+    TORCH_CHECK(lp->scalar_type() == at::kBFloat16 && lp->numel() >= n_valid, "bad lp weights");
+    lpp = reinterpret_cast<bf16_t*>(lp->data_ptr());
+  }
+  const float* cw = nullptr;
+  if (clip) {
+    FAN_T_CUDA_CONTIG((*clip));
+    TORCH_CHECK(clip->scalar_type() == at::kFloat && clip->numel() >= 4, "clip: f32[4]");
+    cw = clip->data_ptr<float>();
+  }
+  uint64_t s = 0;
+  try {
+    s = seed.cast<uint64_t>();
+  } catch (const std::exception&) {
+    TORCH_CHECK(false, "moment_codec: the seed is an int in [0, 2^64)");
+  }
+  const AdamWParams p = fan_adamw_scalars(scalars, grad_scale, weight_decay);
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(mom_q.data_ptr()) | reinterpret_cast<uintptr_t>(var_q.data_ptr())) % 16 == 0,
+              "moment planes: 16-byte aligned");
+  launch_wire_adamw_q((int)codec, wire.data_ptr(), (size_t)shard_elems, (int)n_shards, (int)skip_shard,
+                      (int)skip_period, master.data_ptr<float>(), lpp, mom_q.data_ptr<uint8_t>(),
+                      var_q.data_ptr<uint8_t>(), (size_t)plane_elems, (size_t)elem_base, p, s, (size_t)n_valid,
+                      fan_stream(), (size_t)shard_stride, cw);
+}
+
 }  // namespace
 
 void register_gemm(pybind11::module_& m) {
@@ -625,6 +682,12 @@ void register_nn(pybind11::module_& m) {
         pybind11::arg("slots"), pybind11::arg("n_slots"), pybind11::arg("self_pos"), pybind11::arg("local"),
         pybind11::arg("dsts"), pybind11::arg("shard_elems"), pybind11::arg("codec"), pybind11::arg("seed"),
         pybind11::arg("rank"), pybind11::arg("base") = 0, pybind11::arg("peers") = false);
+  m.def("wire_adamw_q", &wire_adamw_q, "fused decode + AdamW in place with both moments in 8-bit BFP planes",
+        pybind11::arg("wire"), pybind11::arg("shard_elems"), pybind11::arg("n_shards"), pybind11::arg("skip_shard"),
+        pybind11::arg("skip_period"), pybind11::arg("master"), pybind11::arg("lp"), pybind11::arg("mom_q"),
+        pybind11::arg("var_q"), pybind11::arg("scalars"), pybind11::arg("grad_scale"), pybind11::arg("weight_decay"),
+        pybind11::arg("seed"), pybind11::arg("n_valid"), pybind11::arg("codec"), pybind11::arg("shard_stride") = 0,
+        pybind11::arg("clip") = pybind11::none(), pybind11::arg("elem_base") = 0);
 }
 
 void register_planner(pybind11::module_& m) {

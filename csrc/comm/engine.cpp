@@ -246,7 +246,12 @@ static void update_at(const EngineRequest& req, int codec, const void* wire, siz
                       int skip_period, int64_t off, size_t nv, hipStream_t st, size_t shard_stride = 0) {
   bf16_t* lp = req.lp ? req.lp + off : nullptr;
   FAN_CHECK(!req.upd.trust, "a trust-ratio update is the two-pass epilogue (lamb_region), never a single launch");
-  if (req.upd.kind == kOptAdamW) {
+  if (req.moment_q) {
+    // the 8-bit planes are passed whole: the region's bucket offset addresses them (and keys the random bytes)
+    launch_wire_adamw_q(codec, wire, n_s, n_shards, skip_shard, skip_period, req.master + off, lp, req.mom_q, req.var_q,
+                        req.moment_elems, (size_t)off, req.upd.adamw, req.moment_seed, nv, st, shard_stride,
+                        req.clip_words);
+  } else if (req.upd.kind == kOptAdamW) {
     AdamWParams a = req.upd.adamw;
     a.var += off;
     launch_wire_adamw(codec, wire, n_s, n_shards, skip_shard, skip_period, req.master + off, lp, req.mom + off, a, nv,
@@ -1098,8 +1103,24 @@ void AllReduceEngine::hop_mark(int point) {
 int AllReduceEngine::submit(const EngineRequest& req, hipStream_t producer) {
   RoctxRange rr("fan/allreduce/submit");
   cur_ = Current{};
-  FAN_CHECK(req.upd.kind != kOptAdamW || !req.update || (req.mom != nullptr && req.upd.adamw.var != nullptr),
+  FAN_CHECK(req.upd.kind != kOptAdamW || !req.update || req.moment_q ||
+                (req.mom != nullptr && req.upd.adamw.var != nullptr),
             "AdamW needs both moment planes");
+  if (req.moment_q) {
+    // The 8-bit state is read and written by update_at's one launch (refused before the request takes a slot).
+    FAN_CHECK(req.upd.kind == kOptAdamW && req.update,
+              "moment_codec bfp8: AdamW update requests only (SGD keeps no second moment; its momentum stays f32)");
+    FAN_CHECK(!req.upd.trust, "moment_codec bfp8: not with the trust ratio (its pass 2 recomputes the direction from the "
+                              "stored moments)");
+    FAN_CHECK(!sharded(req), "moment_codec bfp8: not with the sharded update (shard_update), whose owner kernels keep "
+                             "f32 moment shards");
+    FAN_CHECK(req.mom_q != nullptr && req.var_q != nullptr, "moment_codec bfp8: both moment planes (uint8)");
+    const EngineLayout ML = layout(req.n_valid, req.layout_shard, req.layout_chunks);
+    FAN_CHECK((uint64_t)ML.n_pad < ((uint64_t)1 << 32),
+              "moment_codec bfp8: a padded bucket of 2^32 or more elements (element indices are 32-bit)");
+    FAN_CHECK(req.moment_elems == ML.n_pad, "moment_codec bfp8: the planes hold exactly the layout's n_pad = " +
+                                                std::to_string(ML.n_pad) + " elements (n_pad * 17 / 16 bytes each)");
+  }
   if (trust(req)) {
     // Every weight of the bucket waits for two norms over the whole bucket, so a schedule that updates part of it
     // before the rest is reduced cannot carry the request (refused before the request takes a slot).

@@ -181,6 +181,16 @@ struct EngineRequest {
   // the gathered wire keeps its format. Refused where `residual` is, and together with it.
   bool sr = false;
   uint64_t sr_seed = 0;
+  // 8-bit AdamW state (moment_codec "bfp8", kOptAdamW update requests): both moments live in the bucket's two uint8
+  // planes mom_q / var_q (bfp_format.h launch_wire_adamw_q: layout().n_pad * 17 / 16 bytes each, the first m, the second
+  // sqrt(v)) instead of `mom` / upd.adamw.var, and every update launch of the request is launch_wire_adamw_q under the
+  // 64-bit request seed moment_seed, with the region's bucket offset as elem_base. The planes are flat, so every
+  // schedule that updates through update_at carries it. Refused with the trust ratio and the sharded update.
+  bool moment_q = false;
+  uint64_t moment_seed = 0;
+  uint8_t* mom_q = nullptr;
+  uint8_t* var_q = nullptr;
+  int64_t moment_elems = 0;  // the planes' element count: layout().n_pad of the request (checked by submit())
   float* out_sum = nullptr;
   const uint8_t* prepacked = nullptr;
   int64_t prepacked_elems = 0;

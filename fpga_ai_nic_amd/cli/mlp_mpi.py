@@ -103,7 +103,8 @@ def run(argv=None, out=sys.stdout):
     else:  # reference fuse_type mapping (sw:479-489)
         bias, relu = {1: (True, "none"), 2: (False, "all"), 3: (True, "all")}.get(a.fuse_type, (False, "none"))
     model = MLP(sizes, dtype=dtype, device=device, pad_fn=pad_fn, seed=cfg.seed, momentum=cfg.momentum > 0,
-                bias=bias, relu=relu, adam=cfg.optimizer == "adamw")
+                bias=bias, relu=relu, adam=cfg.optimizer == "adamw",
+                moment_codec=cfg.moment_codec if cfg.optimizer == "adamw" else "f32")
     if world > 1:  # reference C3/C4: broadcast weights + bias from rank 0
         for l in model.layers:
             transport.broadcast_(l.master, 0)
@@ -121,7 +122,8 @@ def run(argv=None, out=sys.stdout):
                                   max_grad_norm=cfg.clip_grad_norm if cfg.clip_grad_norm > 0 else None,
                                   error_feedback=cfg.error_feedback,
                                   error_feedback_codec=f"bfp_{cfg.rounding}",
-                                  stochastic_rounding=cfg.stochastic_rounding, sr_seed=cfg.sr_seed)
+                                  stochastic_rounding=cfg.stochastic_rounding, sr_seed=cfg.sr_seed,
+                                  moment_codec=cfg.moment_codec)
     trainer.opt_step = opt_step
     trainer.sr_step = sr_step
     x, y = make_data(mb, sizes[0], sizes[-1], rank, cfg.seed, device, dtype)

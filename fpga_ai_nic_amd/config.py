@@ -45,6 +45,7 @@ class TrainConfig:
     error_feedback: bool = False   # BFP mesh: each encoder keeps what it drops and adds it to the next step's input
     stochastic_rounding: bool = False  # rne BFP mesh: each encoder rounds up with probability = the dropped fraction
     sr_seed: int = 0               # the run's base seed of the stochastic rounding, an int in [0, 2^64)
+    moment_codec: str = "f32"      # adamw: f32 | bfp8 (both moments in 8-bit block floating point, 2.125 B / parameter)
     beta1: float = 0.9
     beta2: float = 0.999
     eps: float = 1e-8
@@ -98,6 +99,10 @@ def add_named_flags(ap: argparse.ArgumentParser):
                          "itself (no GEMM-fused encode). The update counter its seeds come from is checkpointed")
     ap.add_argument("--sr-seed", type=int, default=d.sr_seed,
                     help="base seed of --stochastic-rounding, an int in [0, 2^64)")
+    ap.add_argument("--moment-codec", default=d.moment_codec, choices=["f32", "bfp8"],
+                    help="--optimizer adamw: keep both moments in 8-bit block floating point (2.125 B per parameter "
+                         "instead of 8; stored with stochastic rounding under --sr-seed, the second as sqrt(v)); not "
+                         "with --trust-ratio. Checkpointed with the codec's name: --resume needs the same codec")
     ap.add_argument("--beta1", type=float, default=d.beta1, help="AdamW first-moment decay")
     ap.add_argument("--beta2", type=float, default=d.beta2, help="AdamW second-moment decay")
     ap.add_argument("--eps", type=float, default=d.eps, help="AdamW denominator term")

@@ -66,8 +66,10 @@ class MLP:
 
     def __init__(self, sizes, *, dtype=torch.bfloat16, device="cpu", pad_fn=None, seed: int = 1,
                  momentum: bool = False, init_scale: float | None = None, bias: bool = True,
-                 relu: str = "hidden", adam: bool = False):
-        """``adam``: allocate both AdamW moment planes per layer (``mom`` the first, ``var`` the second).
+                 relu: str = "hidden", adam: bool = False, moment_codec: str = "f32"):
+        """``adam``: allocate both AdamW moment planes per layer (``mom`` the first, ``var`` the second);
+        ``moment_codec="bfp8"``: as 8-bit planes (uint8, ``n_pad * 17 / 16`` bytes each, ``var`` holding sqrt(v):
+        ``ops/bfp_oracle.py`` adamw_q), zeroed — the zero state.
         ``bias`` / ``relu`` select the layer epilogue. ``relu``: 'hidden' (every layer but the classifier,
         the default model), 'all' or 'none'. The reference's fuse_type (sw:479-489) maps to
         0 -> (bias=False, relu='none'), 1 -> (True, 'none'), 2 -> (False, 'all'), 3 -> (True, 'all')."""
@@ -75,6 +77,11 @@ class MLP:
             raise ValueError("need at least one layer")
         if relu not in ("hidden", "all", "none"):
             raise ValueError(f"relu must be hidden|all|none, got {relu!r}")
+        if moment_codec not in ("f32", "bfp8"):
+            raise ValueError(f"moment_codec must be f32|bfp8, got {moment_codec!r}")
+        if moment_codec == "bfp8" and not adam:
+            raise ValueError("moment_codec='bfp8' stores AdamW's moments: adam=True")
+        self.moment_codec = moment_codec
         self.bias, self.relu = bias, relu
         self.sizes = list(sizes)
         self.L = len(sizes) - 1
@@ -97,6 +104,8 @@ class MLP:
             grad = torch.zeros(n_pad, dtype=torch.float32, device=self.device)
             mom = torch.zeros(n_pad, dtype=torch.float32, device=self.device) if momentum or adam else None
             var = torch.zeros(n_pad, dtype=torch.float32, device=self.device) if adam else None
+            if moment_codec == "bfp8":
+                mom, var = (torch.zeros(n_pad + n_pad // 16, dtype=torch.uint8, device=self.device) for _ in range(2))
             self.layers.append(LayerBucket(cin, cout, n, n_pad, master, grad, lp, mom, var))
         self._act_mb = None
         self._zero_b: dict[int, torch.Tensor] = {}
@@ -152,6 +161,11 @@ class MLP:
         def grow(t):
             if t is None:
                 return None
+            if t.dtype == torch.uint8:  # an 8-bit moment plane: mantissas, then the exponent bytes behind n_pad
+                u = torch.zeros(n_pad + n_pad // 16, dtype=t.dtype, device=t.device)
+                u[: l.n_pad] = t[: l.n_pad]
+                u[n_pad: n_pad + l.n_pad // 16] = t[l.n_pad:]
+                return u
             u = torch.zeros(n_pad, dtype=t.dtype, device=t.device)
             u[: l.n_pad] = t
             return u

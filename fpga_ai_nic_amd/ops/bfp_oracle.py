@@ -454,6 +454,97 @@ def adamw(w: np.ndarray, g: np.ndarray, m: np.ndarray, v: np.ndarray, scalars: A
     return w2, m2, v2
 
 
+# --------------------------------------------------------------------------- 8-bit AdamW state (moment_codec="bfp8")
+# Both moments of a bucket of n_pad elements live in one uint8 plane each, exactly ``pack(x, n_pad, "bfp_rne")`` of one
+# shard of n_pad elements: bytes [0, n_pad) the int8 mantissas (element-indexed), bytes [n_pad, n_pad + n_pad/16) the
+# groups' biased exponents. The layout is flat (no schedule, shard geometry or wire codec in it), a zeroed plane is the
+# zero state, decoding is the bfp_rne decoder. The first plane holds m, the second r = sqrt(v): with beta2 = 0.999 the
+# second moment moves 0.1 % a step, below an 8-bit mantissa's resolution, so both are stored with stochastic rounding
+# (rank slot 16 of ``sr_key``: the wire's stochastic rounding uses ranks 0..15), and a positive r is never stored as 0
+# (``m / (0 + eps)`` explodes; one quantum at least only makes that element's step smaller).
+MOMENT_CODECS = ("f32", "bfp8")
+MOMENT_RANK = 16            # the sr_key rank slot of the state's random bytes; stage 0: m, stage 1: r
+
+
+def moment_codec_check(name) -> str:
+    if name not in MOMENT_CODECS:
+        raise ValueError(f"moment_codec: one of {MOMENT_CODECS}, got {name!r}")
+    return name
+
+
+def moment_plane_bytes(n_pad: int) -> int:
+    """Bytes of one moment plane of a padded bucket of ``n_pad`` elements (a multiple of 256, below 2^32)."""
+    n_pad = int(n_pad)
+    if n_pad < 0 or n_pad % 256:
+        raise ValueError(f"moment plane: the padded bucket is a multiple of 256 elements, got {n_pad}")
+    if n_pad >= SR_MAX_ELEMS:
+        raise ValueError(f"moment plane: a padded bucket of 2^32 or more elements ({n_pad}; element indices are 32-bit)")
+    return n_pad + n_pad // 16
+
+
+def moment_encode(x: np.ndarray, key, base: int = 0, floor1: bool = False):
+    """The stochastic group encoder of the state: ``sr_encode_groups(x, bfp_rne, key, base)``; with ``floor1`` then
+    q = max(q, 1) wherever x > 0 in a finite group (E != 255). Returns (q int8 [n], E uint8 [n/16])."""
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    q, E = sr_encode_groups(x, 1, key, base)
+    if floor1:
+        lift = (x > 0) & (np.repeat(E, GROUP) != 255)
+        q = np.where(lift, np.maximum(q, 1), q).astype(np.int8)
+    return q, E
+
+
+def moment_decode(plane: np.ndarray) -> np.ndarray:
+    """f32 values of a whole moment plane (the bfp_rne decoder, q * 2^(E-133); E = 255 -> NaN)."""
+    plane = np.ascontiguousarray(plane, dtype=np.uint8).reshape(-1)
+    if plane.size % 17:
+        raise ValueError(f"moment plane: {plane.size} bytes is not n_pad * 17 / 16")
+    n = plane.size // 17 * 16
+    return decode_groups(plane[:n].view(np.int8), plane[n:], "rne")
+
+
+def adamw_q(w: np.ndarray, g: np.ndarray, mom_q: np.ndarray, var_q: np.ndarray, scalars: AdamWScalars,
+            grad_scale: float = 1.0, seed: int = 0, n_valid: int | None = None, base: int = 0):
+    """AdamW over a region of a bucket whose moments are 8-bit planes. ``w`` / ``g``: the region's weights and decoded
+    gradient (size % 16 == 0), element j being element ``base + j`` (base % 16 == 0) of the padded bucket; ``mom_q`` /
+    ``var_q``: the bucket's whole planes. Per element below ``n_valid`` (default all), in f32: m_old = dec, r_old = dec,
+    v_old = r_old * r_old (one multiply), ``adamw`` unchanged, then m' and r' = sqrt(v') (the value ``adamw`` uses in
+    its denominator) are encoded per group with keys sr_key(seed, 16, 0) and sr_key(seed, 16, 1), the latter with the
+    floor. In a group that straddles n_valid the elements at or past it enter the encode as 0 and keep their weights;
+    groups entirely at or past it are not touched. Returns (w', mom_q', var_q'); the inputs are not modified."""
+    w2 = np.array(w, dtype=np.float32).reshape(-1)
+    g = np.ascontiguousarray(g, dtype=np.float32).reshape(-1)
+    mq = np.array(mom_q, dtype=np.uint8).reshape(-1)
+    vq = np.array(var_q, dtype=np.uint8).reshape(-1)
+    n = w2.size
+    n_valid = n if n_valid is None else int(n_valid)
+    base = int(base)
+    n_pad = mq.size // 17 * 16
+    if mq.size != moment_plane_bytes(n_pad) or vq.size != mq.size:
+        raise ValueError("adamw_q: both planes are n_pad * 17 / 16 bytes of one padded bucket")
+    if n % GROUP or g.size < n or base % GROUP or base < 0 or base + n > n_pad or not 0 <= n_valid <= n:
+        raise ValueError(f"adamw_q: region [{base}, {base + n}) with n_valid {n_valid} in a bucket of {n_pad}")
+    seed = sr_seed_check(seed)
+    k = -(-n_valid // GROUP) * GROUP     # the groups the update touches: [0, k)
+    if k == 0:
+        return w2, mq, vq
+    ms, es = slice(base, base + k), slice(n_pad + base // GROUP, n_pad + (base + k) // GROUP)
+    m_old = decode_groups(mq[ms].view(np.int8), mq[es], "rne")
+    r_old = decode_groups(vq[ms].view(np.int8), vq[es], "rne")
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        v_old = (r_old * r_old).astype(np.float32)
+        wn, m2, v2 = adamw(w2[:k], g[:k], m_old, v_old, scalars, grad_scale)
+        r2 = np.sqrt(v2.astype(np.float64)).astype(np.float32)
+    m2 = np.array(m2, np.float32)
+    m2[n_valid:] = 0
+    r2[n_valid:] = 0
+    w2[:n_valid] = wn[:n_valid]
+    for plane, x, stage in ((mq, m2, 0), (vq, r2, 1)):
+        q, E = moment_encode(x, sr_key(seed, MOMENT_RANK, stage), base, floor1=stage == 1)
+        plane[ms] = q.view(np.uint8)
+        plane[es] = E
+    return w2, mq, vq
+
+
 class LambScalars(tuple):
     """The per-step scalars of AdamW with the layer-wise trust ratio (``lamb_scalars``), each already rounded to f32:
     AdamW's moment scalars, ``rbc1 = 1 / (1 - beta1^t)``, and ``wd`` / ``lr`` themselves (the step size is multiplied

@@ -290,6 +290,97 @@ def adamw(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Ten
             lp.view(-1)[lo:hi].copy_(master.view(-1)[lo:hi].to(lp.dtype))
 
 
+def moment_plane(n_pad: int, device) -> torch.Tensor:
+    """A zeroed 8-bit moment plane (the zero state) of a padded bucket of ``n_pad`` elements: uint8,
+    ``n_pad * 17 / 16`` bytes (``bfp_oracle.moment_plane_bytes``)."""
+    return torch.zeros(O.moment_plane_bytes(n_pad), dtype=torch.uint8, device=device)
+
+
+def moment_check(plane, ref: torch.Tensor, n_pad: int | None = None, what: str = "moment plane") -> int:
+    """Validate one 8-bit moment plane against the tensor it updates (``ref``: its device) and, when given, the
+    bucket's ``n_pad``; returns the plane's element count."""
+    if not (isinstance(plane, torch.Tensor) and plane.dtype == torch.uint8):
+        raise ValueError(f"moment_codec bfp8: the {what} is a uint8 tensor, got "
+                         f"{getattr(plane, 'dtype', type(plane).__name__)}")
+    if not plane.is_contiguous():
+        raise ValueError(f"moment_codec bfp8: the {what} must be contiguous")
+    if plane.device != ref.device:
+        raise ValueError(f"moment_codec bfp8: the {what} lives on {plane.device}, the weights on {ref.device}")
+    nb = plane.numel()
+    if nb % (17 * 16) or (n_pad is not None and nb != O.moment_plane_bytes(n_pad)):
+        want = "n_pad * 17 / 16" if n_pad is None else f"exactly n_pad * 17 / 16 = {O.moment_plane_bytes(n_pad)}"
+        raise ValueError(f"moment_codec bfp8: the {what} has {nb} bytes, not {want}")
+    if plane.data_ptr() % 16:
+        raise ValueError(f"moment_codec bfp8: the {what} must be 16-byte aligned (a slice of a larger tensor may not be)")
+    n = nb // 17 * 16
+    O.moment_plane_bytes(n)  # (refuses 2^32 elements or more)
+    return n
+
+
+def moment_decode(plane: torch.Tensor) -> torch.Tensor:
+    """The f32 values of a whole 8-bit moment plane (``bfp_oracle.moment_decode``), on the plane's device."""
+    n = moment_check(plane, plane)
+    out = torch.empty(n, dtype=torch.float32, device=plane.device)
+    if n:
+        unpack(plane, out, n, "bfp_rne")
+    return out
+
+
+def adamw_q(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Tensor, *, codec,
+            mom_q: torch.Tensor, var_q: torch.Tensor, scalars: O.AdamWScalars, seed: int,
+            lp: torch.Tensor | None = None, grad_scale: float = 1.0, n_valid: int | None = None,
+            skip_shard: int = -1, skip_period: int = 0, shard_stride: int = 0, clip: torch.Tensor | None = None,
+            elem_base: int = 0):
+    """:func:`adamw` with both moments in 8-bit block floating point (``bfp_oracle.adamw_q`` defines the bits):
+    ``mom_q`` / ``var_q`` are the bucket's whole planes (:func:`moment_plane`; the second holds sqrt(v)), ``seed`` the
+    request's 64-bit seed of the state's stochastic rounding, ``elem_base`` (a multiple of 256) the bucket index of the
+    wire region's element 0. ``codec`` is the *wire's*; the other arguments are :func:`adamw`'s."""
+    c = codec_id(codec)
+    if c not in O.CODEC_NAMES:
+        raise ValueError(f"unknown wire codec {codec!r}")
+    if not isinstance(scalars, O.AdamWScalars):
+        raise TypeError(f"wire.adamw_q takes bfp_oracle.adamw_scalars, got {type(scalars).__name__}")
+    seed = O.sr_seed_check(seed)
+    n_pad = moment_check(mom_q, master, what="first-moment plane")
+    moment_check(var_q, master, n_pad, what="second-moment plane")
+    n_valid = master.numel() if n_valid is None else int(n_valid)
+    n = shard_elems * n_shards
+    elem_base = int(elem_base)
+    if shard_elems <= 0 or shard_elems % 256 or n_shards <= 0 or not 0 <= n_valid <= n:
+        raise ValueError(f"adamw_q: {n_shards} shards of {shard_elems} elements (a multiple of 256), n_valid {n_valid}")
+    if elem_base < 0 or elem_base % 256 or elem_base + n_valid > n_pad:
+        raise ValueError(f"adamw_q: elem_base {elem_base} must be a multiple of 256 with the region's {n_valid} valid "
+                         f"elements inside the planes' {n_pad}")
+    if master.is_cuda:
+        _ext.require().wire_adamw_q(wire, int(shard_elems), int(n_shards), int(skip_shard), int(skip_period), master,
+                                    lp, mom_q, var_q, scalars.kernel_args(), float(grad_scale), float(scalars.wd),
+                                    seed, n_valid, c, int(shard_stride), clip, elem_base)
+        return
+    if clip is not None:
+        grad_scale = O.clip_scale(grad_scale, _np_f32(clip))
+    sb = O.shard_bytes(c, shard_elems)
+    raw = _np_u8(wire)
+    if shard_stride:
+        raw = np.concatenate([raw[s * shard_stride: s * shard_stride + sb] for s in range(n_shards)])
+    g = O.unpack(raw, n, shard_elems, c)
+    w = master.view(-1).numpy()
+    mq, vq = mom_q.view(-1).numpy(), var_q.view(-1).numpy()
+    period = skip_period if skip_period >= 1 else (1 << 30)
+    for s in range(n_shards):
+        if skip_shard >= 0 and s % period == skip_shard:
+            continue
+        lo, hi = s * shard_elems, min((s + 1) * shard_elems, n_valid)
+        if hi <= lo:
+            continue
+        top = lo + -(-(hi - lo) // 16) * 16          # whole groups: the oracle zeroes the tail of the last one
+        wpad = np.zeros(top - lo, np.float32)
+        wpad[:hi - lo] = w[lo:hi]
+        w2, mq[:], vq[:] = O.adamw_q(wpad, g[lo:top], mq, vq, scalars, grad_scale, seed, hi - lo, elem_base + lo)
+        w[lo:hi] = w2[:hi - lo]
+        if lp is not None:
+            lp.view(-1)[lo:hi].copy_(master.view(-1)[lo:hi].to(lp.dtype))
+
+
 def _lamb_ranges(shard_elems, n_shards, n_valid, skip_shard, skip_period):
     """The flat [lo, hi) ranges one trust-ratio launch covers: every shard but the skipped ones, cut at n_valid."""
     period = skip_period if skip_period >= 1 else (1 << 30)

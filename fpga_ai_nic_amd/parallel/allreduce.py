@@ -172,6 +172,35 @@ def sr_request(sr_seed, L, *, codec_id, algo, world, prepacked=False, sharded=Fa
     return wire.O.sr_seed_check(sr_seed)
 
 
+def moment_request(moment_codec, moment_seed, mom, var, L, master, *, opt, trust_ratio=False, sharded=False):
+    """Validate one request's ``moment_codec=`` (``"f32"``: today's planes, returns None; ``"bfp8"``: AdamW's two
+    moments live in 8-bit block-floating-point planes, ``mom`` holding m and ``var`` sqrt(v), each a uint8 tensor of
+    exactly ``L.n_pad * 17 / 16`` bytes — ``wire.moment_plane`` — stored with stochastic rounding under the 64-bit
+    request seed ``moment_seed``, which every rank passes alike). Returns the seed as an int."""
+    wire.O.moment_codec_check(moment_codec)
+    if moment_codec == "f32":
+        if moment_seed is not None:
+            raise ValueError("moment_seed belongs to moment_codec='bfp8'")
+        return None
+    if opt != "adamw":
+        raise ValueError("moment_codec='bfp8': AdamW only (opt='sgd' keeps no second moment; its momentum stays f32)")
+    if trust_ratio:
+        raise ValueError("moment_codec='bfp8': not with trust_ratio (LAMB's pass 2 recomputes the direction from the "
+                         "stored moments)")
+    if sharded:
+        raise ValueError("moment_codec='bfp8': not with a sharded-update engine (its owner kernels keep f32 moment "
+                         "shards)")
+    if L.n_pad >= wire.O.SR_MAX_ELEMS:
+        raise ValueError(f"moment_codec='bfp8': a padded bucket of 2^32 or more elements ({L.n_pad}; element indices "
+                         f"are 32-bit)")
+    if moment_seed is None:
+        raise ValueError("moment_codec='bfp8' needs moment_seed, an int in [0, 2^64)")
+    seed = wire.O.sr_seed_check(moment_seed)
+    wire.moment_check(mom, master, L.n_pad, what="first-moment plane (mom)")
+    wire.moment_check(var, master, L.n_pad, what="second-moment plane (var)")
+    return seed
+
+
 def adamw_request(opt, mom, var, *, lr, weight_decay, momentum, nesterov, betas, eps, step, trust_ratio=False,
                   n_adapt=None, n_valid=None):
     """Validate one request's optimizer arguments; the step's ``bfp_oracle.AdamWScalars`` for ``opt="adamw"``
@@ -429,7 +458,8 @@ class CompressedAllReduce:
                       betas=(0.9, 0.999), eps: float = 1e-8, step: int | None = None, trust_ratio: bool = False,
                       n_adapt: int | None = None, trust_out: torch.Tensor | None = None,
                       clip: torch.Tensor | None = None, residual: torch.Tensor | None = None,
-                      sr_seed: int | None = None) -> Handle:
+                      sr_seed: int | None = None, moment_codec: str = "f32",
+                      moment_seed: int | None = None) -> Handle:
         """All-reduce ``grad`` (flat, padded to ``layout(n).n_pad``) and apply SGD to ``master`` (+bf16 ``lp``).
         ``opt="adamw"``: AdamW instead, ``mom`` / ``var`` the first / second moment planes (both required), ``step``
         the bucket's 1-based update count. ``trust_ratio`` (AdamW): scale the step of the bucket's first ``n_adapt``
@@ -443,7 +473,9 @@ class CompressedAllReduce:
         the gathered wire keeps its format, so every epilogue runs unchanged. Mesh schedule and BFP codecs only.
         ``sr_seed`` (an int in [0, 2^64); not with ``residual``): stochastic rounding — the same two encoders round up
         with probability equal to the dropped fraction (``bfp_oracle.sr_pack`` / ``sr_reduce``), stateless; every rank
-        passes the same seed. Mesh schedule, ``bfp_rne`` / ``bfp4_rne`` only."""
+        passes the same seed. Mesh schedule, ``bfp_rne`` / ``bfp4_rne`` only. ``moment_codec="bfp8"`` (AdamW): ``mom`` /
+        ``var`` are 8-bit moment planes (``wire.moment_plane(layout(n).n_pad, device)``; ``var`` holds sqrt(v)) updated
+        by ``wire.adamw_q`` under the request seed ``moment_seed``, on every schedule; not with ``trust_ratio``."""
         clip_request(clip, defer, self.device)
         if clip is not None and self.compat_owner_fp32 and self.algo == "ring":
             raise ValueError("clip: not with compat_owner_fp32 (the owner's slices would be updated from another "
@@ -459,6 +491,8 @@ class CompressedAllReduce:
         n_adapt = n_valid if n_adapt is None else int(n_adapt)
         L = self.layout(n_valid)
         self._check(grad, L)
+        mq_seed = moment_request(moment_codec, moment_seed, mom, var, L, master, opt=opt, trust_ratio=trust_ratio,
+                                 sharded=bool(getattr(self, "shard_update", False)))
         sr_seed = sr_request(sr_seed, L, codec_id=self.codec_id, algo=self.algo, world=self.world, residual=residual)
         residual = residual_request(residual, L, codec_id=self.codec_id, algo=self.algo, world=self.world,
                                     device=self.device)
@@ -471,6 +505,13 @@ class CompressedAllReduce:
                 cl["count"] += wire.sumsq(G, shard, n_shards, codec=codec, partials=cl["partials"],
                                           partials_base=cl["count"], n_valid=nv, skip_shard=skip[0],
                                           skip_period=skip[1])
+                return
+            if mq_seed is not None:  # 8-bit state: the planes go whole, the region's offset addresses them
+                wire.adamw_q(G, shard, n_shards, master.view(-1)[off:off + length], codec=codec, mom_q=mom.view(-1),
+                             var_q=var.view(-1), scalars=scalars, seed=mq_seed,
+                             lp=None if lp is None else lp.view(-1)[off:off + length], grad_scale=grad_scale,
+                             n_valid=nv, skip_shard=skip[0], skip_period=skip[1],
+                             clip=None if cl is None else cl["words"], elem_base=off)
                 return
             planes = dict(lp=None if lp is None else lp.view(-1)[off:off + length],
                           mom=None if mom is None else mom.view(-1)[off:off + length],

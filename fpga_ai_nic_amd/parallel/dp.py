@@ -88,8 +88,18 @@ class DataParallelTrainer:
                  gemm_inflight: str | None = None, wgrad_pair: bool | str | None = None, optimizer: str = "sgd",
                  betas=(0.9, 0.999), eps: float = 1e-8, trust_ratio: bool = False,
                  max_grad_norm: float | None = None, error_feedback: bool = False,
-                 error_feedback_codec: str = "bfp_rne", stochastic_rounding: bool = False, sr_seed: int = 0):
-        """``stochastic_rounding``: stochastic rounding for the compressed mesh all-reduce — every layer's request
+                 error_feedback_codec: str = "bfp_rne", stochastic_rounding: bool = False, sr_seed: int = 0,
+                 moment_codec: str = "f32"):
+        """``moment_codec``: 'f32' (the model's f32 moment planes) or 'bfp8' (AdamW only): both moments of every layer
+        live in 8-bit block-floating-point planes (``wire.moment_plane``: 2.125 B per parameter instead of 8, the
+        second holding sqrt(v)), which the trainer allocates zeroed in place of the model's ``mom`` / ``var`` unless
+        the model already holds them (``MLP(..., adam=True, moment_codec="bfp8")``, a resumed run). Every layer's
+        request carries ``moment_seed=bfp_oracle.sr_step_seed(sr_seed, opt_step, layer)``, under which the update
+        stores the new moments with stochastic rounding (``bfp_oracle.adamw_q``); ``opt_step`` is already checkpointed,
+        so a resumed run's next step is bit-identical. With ``stochastic_rounding``, ``error_feedback`` and
+        ``max_grad_norm`` (they act before the update); not with ``trust_ratio`` or a sharded-update engine.
+
+        ``stochastic_rounding``: stochastic rounding for the compressed mesh all-reduce — every layer's request
         carries ``sr_seed=bfp_oracle.sr_step_seed(sr_seed, sr_step, layer)``, under which this rank's two encoders round
         up with probability equal to the dropped fraction; ``sr_step`` is the trainer's update counter (1-based,
         advanced once per ``backward_pass``, checkpointed by the CLI). Stateless: no plane, no extra traffic; one
@@ -157,8 +167,26 @@ class DataParallelTrainer:
             if momentum or nesterov:
                 raise ValueError("momentum / nesterov belong to SGD: AdamW's first moment is governed by betas[0]")
             wire.O.adamw_scalars(lr, weight_decay, self.betas[0], self.betas[1], self.eps, 1)  # validates
-            if any(l.mom is None or l.var is None for l in model.layers):
+            if moment_codec != "bfp8" and any(l.mom is None or l.var is None for l in model.layers):
                 raise ValueError("optimizer='adamw' needs a model with both moment planes: MLP(..., adam=True)")
+        self.moment_codec = wire.O.moment_codec_check(moment_codec)
+        if moment_codec == "bfp8":
+            if optimizer != "adamw":
+                raise ValueError("moment_codec='bfp8': optimizer='adamw' only (SGD keeps no second moment; its "
+                                 "momentum stays f32)")
+            if trust_ratio:
+                raise ValueError("moment_codec='bfp8': not with trust_ratio (LAMB's pass 2 recomputes the direction "
+                                 "from the stored moments)")
+            if bool(getattr(engine, "shard_update", False)):
+                raise ValueError("moment_codec='bfp8': not with a sharded-update engine (its owner kernels keep f32 "
+                                 "moment shards)")
+            for l in model.layers:
+                n_pad = engine.layout(l.n).n_pad if engine is not None else l.n_pad
+                nb = wire.O.moment_plane_bytes(n_pad)
+                if not all(t is not None and t.dtype == torch.uint8 and t.numel() == nb for t in (l.mom, l.var)):
+                    l.mom, l.var = wire.moment_plane(n_pad, model.device), wire.moment_plane(n_pad, model.device)
+        elif any(t is not None and t.dtype == torch.uint8 for l in model.layers for t in (l.mom, l.var)):
+            raise ValueError("the model holds 8-bit moment planes: moment_codec='bfp8'")
         self.trust_ratio = bool(trust_ratio)
         if self.trust_ratio and optimizer != "adamw":
             raise ValueError("trust_ratio is a flag of optimizer='adamw'")
@@ -292,6 +320,8 @@ class DataParallelTrainer:
         if self.optimizer != "adamw":
             return kw
         kw.update(opt="adamw", var=l.var, betas=self.betas, eps=self.eps, step=self.opt_step)
+        if self.moment_codec == "bfp8":
+            kw.update(moment_codec="bfp8", moment_seed=self._moment_seed_of(l))
         if self.trust_ratio:
             kw.update(trust_ratio=True, n_adapt=self._n_adapt(l), trust_out=self._trust_row(l))
         return kw
@@ -325,6 +355,10 @@ class DataParallelTrainer:
     def _sr_seed_of(self, l):
         """The seed of layer l's request in the step being enqueued."""
         return wire.O.sr_step_seed(self.sr_seed, self.sr_step, self._index(l))
+
+    def _moment_seed_of(self, l):
+        """The seed of layer l's 8-bit state in the update being enqueued (``opt_step`` is its 1-based count)."""
+        return wire.O.sr_step_seed(self.sr_seed, self.opt_step, self._index(l))
 
     def _sr_local(self, l):
         """Engine-less stochastic rounding: layer l's gradient through the stochastic round trip at one slot (the
@@ -366,6 +400,11 @@ class DataParallelTrainer:
             return
         if self.optimizer == "adamw":
             scalars = wire.O.adamw_scalars(self.lr, self.wd, self.betas[0], self.betas[1], self.eps, self.opt_step)
+            if self.moment_codec == "bfp8":
+                wire.adamw_q(src, l.n_pad, 1, l.master, codec=codec, lp=l.lp, mom_q=l.mom, var_q=l.var,
+                             scalars=scalars, seed=self._moment_seed_of(l), grad_scale=self.grad_scale, n_valid=l.n,
+                             clip=clip)
+                return
             wire.adamw(src, l.n_pad, 1, l.master, codec=codec, lp=l.lp, mom=l.mom, var=l.var,
                        scalars=scalars, grad_scale=self.grad_scale, n_valid=l.n, clip=clip)
             return

@@ -24,7 +24,7 @@ import torch
 from .. import _ext
 from ..ops import wire
 from .allreduce import (CLIP_GROUP_LIMIT, NUM_SLOTS, BucketLayout, ChecksumError, CommTimeoutError, adamw_request,
-                        clip_group_check, clip_request, residual_request, sr_request)
+                        clip_group_check, clip_request, moment_request, residual_request, sr_request)
 from .transport import NativeTransport, Transport
 
 _ALGOS = {"mesh": 0, "ring": 1}
@@ -259,7 +259,8 @@ class NativeAllReduce:
                       opt: str = "sgd", var: torch.Tensor | None = None, betas=(0.9, 0.999), eps: float = 1e-8,
                       step: int | None = None, trust_ratio: bool = False, n_adapt: int | None = None,
                       trust_out: torch.Tensor | None = None, clip: torch.Tensor | None = None,
-                      residual: torch.Tensor | None = None, sr_seed: int | None = None) -> NativeHandle:
+                      residual: torch.Tensor | None = None, sr_seed: int | None = None,
+                      moment_codec: str = "f32", moment_seed: int | None = None) -> NativeHandle:
         """``opt="adamw"``: AdamW instead of SGD, ``mom`` / ``var`` the first / second moment planes (both required),
         ``step`` the bucket's 1-based update count (as :meth:`CompressedAllReduce.allreduce_sgd`). ``trust_ratio`` /
         ``n_adapt`` / ``trust_out``: the layer-wise trust ratio (LAMB), as there; refused with the sharded update, a
@@ -274,7 +275,10 @@ class NativeAllReduce:
         ``residual`` (f32, ``layout(n).n_pad`` elements, zeroed before the bucket's first request): error feedback, as
         :meth:`CompressedAllReduce.allreduce_sgd`; mesh and BFP codecs only, not with ``prepacked``, a chunked layout
         or the sharded update. ``sr_seed`` (an int in [0, 2^64)): stochastic rounding under that request seed, as
-        :meth:`CompressedAllReduce.allreduce_sgd`; refused where ``residual`` is, and together with it."""
+        :meth:`CompressedAllReduce.allreduce_sgd`; refused where ``residual`` is, and together with it.
+        ``moment_codec="bfp8"`` / ``moment_seed``: AdamW's moments in 8-bit planes (``mom`` / ``var`` are then
+        ``wire.moment_plane`` tensors), as :meth:`CompressedAllReduce.allreduce_sgd`; every schedule carries it, the
+        trust ratio and the sharded update refuse it."""
         n_valid = int(n_valid if n_valid is not None else master.numel())
         clip_request(clip, defer, self.device)
         sr_seed = self._sr(sr_seed, n_valid, prepacked, layout, residual)
@@ -284,7 +288,12 @@ class NativeAllReduce:
                                 n_adapt=n_adapt, n_valid=n_valid)
         pre, pre_n = (None, 0) if prepacked is None else prepacked
         ls, lc = (0, 0) if layout is None else (int(layout[0]), int(layout[1]))
+        mq_seed = moment_request(moment_codec, moment_seed, mom, var, self.layout(n_valid, ls, lc), master, opt=opt,
+                                 trust_ratio=trust_ratio, sharded=self.shard_update)
         okw = {} if scalars is None else dict(opt=1, var=var.view(-1), adamw=scalars.kernel_args())
+        if mq_seed is not None:  # the 8-bit planes stand in for mom / var
+            okw = dict(opt=1, adamw=scalars.kernel_args(), mom_q=mom.view(-1), var_q=var.view(-1), moment_seed=mq_seed)
+            mom = None
         if trust_ratio:
             if self.shard_update:
                 raise ValueError("trust_ratio: not with a sharded-update engine (each owner updates its shard before "

@@ -7,7 +7,9 @@ defines the on-disk format as exactly that:
 * ``<path>.safetensors`` — tensors ``fc{i}.weight`` [C_i, C_{i+1}] and ``fc{i}.bias`` [C_{i+1}] in f32 (or bf16),
   optional ``fc{i}.momentum`` (flat, f32), or for an AdamW model ``fc{i}.exp_avg`` / ``fc{i}.exp_avg_sq`` (its two
   moment planes, flat, f32; the index then carries ``optimizer`` and ``opt_step``, the updates applied so far; a
-  stochastically rounded run adds ``sr_step``, the update counter its request seeds are derived from);
+  stochastically rounded run adds ``sr_step``, the update counter its request seeds are derived from; a model with
+  8-bit moment planes stores each plane's bytes whole under the same two names, uint8, and the index carries
+  ``moment_codec`` = "bfp8" and the planes' ``moment_n_pad``);
 * ``<path>.json`` — index: layer shapes / dtypes / byte offsets into a plain concatenated ``.bin`` image, the
   libxsmm blocking ``bn/bk/bc`` as metadata, iteration counter, world size and engine settings.
 * ``<path>.bin`` — the raw concatenation (weight_0, bias_0, weight_1, ...) so a C/C++ consumer (e.g. the
@@ -35,7 +37,10 @@ def save(path: str, model, *, iteration: int = 0, dtype: str = "f32", meta: dict
         b = l.b_master.detach().to("cpu", tdt).contiguous()
         tensors[f"fc{i}.weight"] = w
         tensors[f"fc{i}.bias"] = b
-        if getattr(l, "var", None) is not None:
+        if getattr(l, "var", None) is not None and l.var.dtype == torch.uint8:  # 8-bit planes: their bytes, whole
+            tensors[f"fc{i}.exp_avg"] = l.mom.detach().to("cpu").contiguous()
+            tensors[f"fc{i}.exp_avg_sq"] = l.var.detach().to("cpu").contiguous()
+        elif getattr(l, "var", None) is not None:
             tensors[f"fc{i}.exp_avg"] = l.mom[: l.n].detach().to("cpu").contiguous()
             tensors[f"fc{i}.exp_avg_sq"] = l.var[: l.n].detach().to("cpu").contiguous()
         elif l.mom is not None:
@@ -52,6 +57,9 @@ def save(path: str, model, *, iteration: int = 0, dtype: str = "f32", meta: dict
             f.write(raw)
     info = {"format": "fpga_ai_nic_amd/mlp-v1", "sizes": model.sizes, "iteration": iteration, "dtype": dtype,
             "layout": "row-major C[i] x C[i+1] (reference fil_libxsmm order)", "tensors": index}
+    if any(getattr(l, "var", None) is not None and l.var.dtype == torch.uint8 for l in model.layers):
+        info["moment_codec"] = "bfp8"
+        info["moment_n_pad"] = [int(l.var.numel() // 17 * 16) for l in model.layers]
     if optimizer is not None:
         info["optimizer"] = optimizer
     if opt_step is not None:
@@ -70,10 +78,25 @@ def load(path: str, model) -> dict:
     if list(info["sizes"]) != list(model.sizes):
         raise ValueError(f"checkpoint sizes {info['sizes']} != model sizes {model.sizes}")
     sd = load_file(path + ".safetensors")
+    saved = info.get("moment_codec", "f32")
+    for i, l in enumerate(model.layers):
+        if getattr(l, "var", None) is None or f"fc{i}.exp_avg_sq" not in sd:
+            continue
+        have = "bfp8" if l.var.dtype == torch.uint8 else "f32"
+        if have != saved:
+            raise ValueError(f"checkpoint moments were saved under moment_codec={saved!r}; the model holds {have!r} "
+                             f"planes (resume under the codec the checkpoint was written with)")
+        if have == "bfp8" and sd[f"fc{i}.exp_avg"].numel() != l.mom.numel():
+            raise ValueError(f"checkpoint fc{i}: 8-bit moment planes of n_pad = {sd[f'fc{i}.exp_avg'].numel() // 17 * 16}"
+                             f" elements; the model's bucket is padded to {l.mom.numel() // 17 * 16} (the plane layout "
+                             f"depends on n_pad: resume under the same engine layout)")
     for i, l in enumerate(model.layers):
         l.w_master.copy_(sd[f"fc{i}.weight"].to(l.master.device, torch.float32))
         l.b_master.copy_(sd[f"fc{i}.bias"].to(l.master.device, torch.float32))
-        if getattr(l, "var", None) is not None and f"fc{i}.exp_avg_sq" in sd:
+        if getattr(l, "var", None) is not None and l.var.dtype == torch.uint8 and f"fc{i}.exp_avg_sq" in sd:
+            l.mom.copy_(sd[f"fc{i}.exp_avg"].to(l.mom.device))
+            l.var.copy_(sd[f"fc{i}.exp_avg_sq"].to(l.var.device))
+        elif getattr(l, "var", None) is not None and f"fc{i}.exp_avg_sq" in sd:
             l.mom[: l.n].copy_(sd[f"fc{i}.exp_avg"].to(l.mom.device))
             l.var[: l.n].copy_(sd[f"fc{i}.exp_avg_sq"].to(l.var.device))
         elif l.mom is not None and f"fc{i}.momentum" in sd:
