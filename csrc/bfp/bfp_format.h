@@ -315,6 +315,24 @@ struct WireLane16 {
   }
 };
 
+// The shared exponent of a 16-value group one lane holds whole: the largest magnitude's exponent field.
+__device__ __forceinline__ uint32_t bfp_group_exponent(const float* v) {
+  uint32_t mx = 0;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) mx = max(mx, __float_as_uint(v[j]) & 0x7FFFFFFFu);
+  return mx >> 23;
+}
+
+// The exponent bytes E of 16 consecutive lanes as the 16 B lane 16k stores: 4 lanes -> one dword, 4 dwords -> one
+// uint4 (valid in lane 16k; all 16 lanes must be active).
+__device__ __forceinline__ uint4 bfp_gather_exponents(uint32_t E) {
+  uint32_t e4 = E | ((uint32_t)__shfl_down((int)E, 1) << 8) | ((uint32_t)__shfl_down((int)E, 2) << 16) |
+                ((uint32_t)__shfl_down((int)E, 3) << 24);
+  const uint32_t e4b = (uint32_t)__shfl_down((int)e4, 4), e4c = (uint32_t)__shfl_down((int)e4, 8),
+                 e4d = (uint32_t)__shfl_down((int)e4, 12);
+  return make_uint4(e4, e4b, e4c, e4d);
+}
+
 template <int C>
 struct BfpLane16 {
   __device__ static __forceinline__ void load16(const uint8_t* shard, size_t n_s, size_t le, float v[16]) {
@@ -328,10 +346,7 @@ struct BfpLane16 {
     }
   }
   __device__ static __forceinline__ void store16(uint8_t* shard, size_t n_s, size_t le, const float v[16]) {
-    uint32_t mx = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) mx = max(mx, __float_as_uint(v[j]) & 0x7FFFFFFFu);
-    const uint32_t E = mx >> 23;
+    const uint32_t E = bfp_group_exponent(v);
     uint32_t w[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
@@ -339,12 +354,8 @@ struct BfpLane16 {
       w[j >> 2] |= ((uint32_t)q & 0xFFu) << (8 * (j & 3));
     }
     *reinterpret_cast<uint4*>(shard + le) = make_uint4(w[0], w[1], w[2], w[3]);
-    // exponent plane: 4 lanes -> one dword, 4 dwords -> one 16-B store by lane 16k
-    uint32_t e4 = E | ((uint32_t)__shfl_down((int)E, 1) << 8) | ((uint32_t)__shfl_down((int)E, 2) << 16) |
-                  ((uint32_t)__shfl_down((int)E, 3) << 24);
-    const uint32_t e4b = (uint32_t)__shfl_down((int)e4, 4), e4c = (uint32_t)__shfl_down((int)e4, 8),
-                   e4d = (uint32_t)__shfl_down((int)e4, 12);
-    if ((threadIdx.x & 15) == 0) *reinterpret_cast<uint4*>(shard + n_s + (le >> 4)) = make_uint4(e4, e4b, e4c, e4d);
+    const uint4 e16 = bfp_gather_exponents(E);  // the exponent plane: one 16-B store by lane 16k
+    if ((threadIdx.x & 15) == 0) *reinterpret_cast<uint4*>(shard + n_s + (le >> 4)) = e16;
   }
 };
 
@@ -364,20 +375,13 @@ struct WireLane16<kBfp4Rne> {
     for (int j = 0; j < 16; ++j) v[j] = bfp4_decode_rne(bfp4_nibble(j < 8 ? m.x : m.y, j & 7), E);
   }
   __device__ static __forceinline__ void store16(uint8_t* shard, size_t n_s, size_t le, const float v[16]) {
-    uint32_t mx = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) mx = max(mx, __float_as_uint(v[j]) & 0x7FFFFFFFu);
-    const uint32_t E = mx >> 23;
+    const uint32_t E = bfp_group_exponent(v);
     uint32_t w[2] = {0u, 0u};
 #pragma unroll
     for (int j = 0; j < 16; ++j) w[j >> 3] |= ((uint32_t)bfp4_encode_rne(v[j], E) & 0xFu) << (4 * (j & 7));
     *reinterpret_cast<uint2*>(shard + (le >> 1)) = make_uint2(w[0], w[1]);
-    uint32_t e4 = E | ((uint32_t)__shfl_down((int)E, 1) << 8) | ((uint32_t)__shfl_down((int)E, 2) << 16) |
-                  ((uint32_t)__shfl_down((int)E, 3) << 24);
-    const uint32_t e4b = (uint32_t)__shfl_down((int)e4, 4), e4c = (uint32_t)__shfl_down((int)e4, 8),
-                   e4d = (uint32_t)__shfl_down((int)e4, 12);
-    if ((threadIdx.x & 15) == 0)
-      *reinterpret_cast<uint4*>(shard + (n_s >> 1) + (le >> 4)) = make_uint4(e4, e4b, e4c, e4d);
+    const uint4 e16 = bfp_gather_exponents(E);
+    if ((threadIdx.x & 15) == 0) *reinterpret_cast<uint4*>(shard + (n_s >> 1) + (le >> 4)) = e16;
   }
 };
 
@@ -450,10 +454,7 @@ struct Lanes16 {
   }
   __device__ static __forceinline__ void roundtrip(float v[16]) {
     if constexpr (codec_shared_exp(C)) {
-      uint32_t mx = 0;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) mx = max(mx, __float_as_uint(v[j]) & 0x7FFFFFFFu);
-      const uint32_t E = mx >> 23;
+      const uint32_t E = bfp_group_exponent(v);
 #pragma unroll
       for (int j = 0; j < 16; ++j) v[j] = bfp_roundtrip<C>(v[j], E);
     } else if constexpr (C == kRawBf16) {
@@ -617,33 +618,23 @@ struct SrLanes;
 template <int C>
 struct SrLanes<Lanes16<C>> {
   static constexpr int kWords = C == kBfp4Rne ? 2 : 4;
-  __device__ static __forceinline__ uint32_t exponent(const float (&v)[16]) {
-    uint32_t mx = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) mx = max(mx, __float_as_uint(v[j]) & 0x7FFFFFFFu);
-    return mx >> 23;
-  }
   __device__ static __forceinline__ void store_wire(uint8_t* const* to, int n_dst, size_t n_s, size_t le,
                                                     const float (&v)[16], SrKey key, uint32_t i) {
-    const uint32_t E = exponent(v);
+    const uint32_t E = bfp_group_exponent(v);
     uint32_t w[kWords];
     sr_encode_vals<C, 16>(v, E, key, i, w);
-    // exponent plane: 4 lanes -> one dword, 4 dwords -> one 16-B store by lane 16k (WireLane16)
-    uint32_t e4 = E | ((uint32_t)__shfl_down((int)E, 1) << 8) | ((uint32_t)__shfl_down((int)E, 2) << 16) |
-                  ((uint32_t)__shfl_down((int)E, 3) << 24);
-    const uint32_t e4b = (uint32_t)__shfl_down((int)e4, 4), e4c = (uint32_t)__shfl_down((int)e4, 8),
-                   e4d = (uint32_t)__shfl_down((int)e4, 12);
+    const uint4 e16 = bfp_gather_exponents(E);  // the exponent plane: one 16-B store by lane 16k (WireLane16)
     const size_t mant = C == kBfp4Rne ? n_s >> 1 : n_s;  // bytes of the mantissa plane
     for (int k = 0; k < n_dst; ++k) {                    // (wave-uniform condition)
       uint8_t* shard = to[k];
       if (shard == nullptr) continue;
       if constexpr (C == kBfp4Rne) *reinterpret_cast<uint2*>(shard + (le >> 1)) = make_uint2(w[0], w[1]);
       else *reinterpret_cast<uint4*>(shard + le) = make_uint4(w[0], w[1], w[2], w[3]);
-      if ((threadIdx.x & 15) == 0) *reinterpret_cast<uint4*>(shard + mant + (le >> 4)) = make_uint4(e4, e4b, e4c, e4d);
+      if ((threadIdx.x & 15) == 0) *reinterpret_cast<uint4*>(shard + mant + (le >> 4)) = e16;
     }
   }
   __device__ static __forceinline__ void roundtrip(float (&v)[16], SrKey key, uint32_t i) {
-    const uint32_t E = exponent(v);
+    const uint32_t E = bfp_group_exponent(v);
     uint32_t w[kWords];
     sr_encode_vals<C, 16>(v, E, key, i, w);
 #pragma unroll
@@ -783,48 +774,39 @@ void launch_wire_lamb_apply(float* master, bf16_t* lp, const float* mom, LambPar
 // Decode to f32/bf16 from a strided wire (as launch_wire_sgd's shard_stride).
 void launch_wire_unpack_strided(int codec, int out_dtype, const void* in, size_t shard_stride, void* out, size_t n_s,
                                 int n_shards, hipStream_t stream);
-// Pack shards 0..n_shards-1 of `in`, shard s stored at dst.p[s] (skipped when nullptr); ends with a system-scope
-// release so a peer may read the stores once the (stream-ordered) ready flag is set.
+// The encoder of the mesh schedule's two stages (the sender's pack, the owner's re-encode), one record for both
+// launchers below. plain: the codec's own rounding. feedback (BFP codecs only): residual compensation; `residual` is
+// this rank's f32 plane of the elements the launch covers (16-B aligned, zeroed by the caller before the bucket's first
+// request), updated in place; ops/bfp_oracle.py ef_pack / ef_reduce define the bits. stochastic (kBfpRne and kBfp4Rne
+// only): stateless unbiased rounding under `key` = sr_key(seed, rank, stage); `base` is the bucket index of the
+// launch's first element and the launch's last index must be below 2^32; the wire format is unchanged and the bits
+// (ops/bfp_oracle.py sr_pack / sr_reduce) do not depend on the grid or the lane layout.
+struct WireEncoder {
+  enum Kind : int { kPlain, kFeedback, kStochastic };
+  Kind kind = kPlain;
+  float* residual = nullptr;
+  SrKey key{};
+  size_t base = 0;
+  static WireEncoder feedback(float* residual) { return {kFeedback, residual, {}, 0}; }
+  static WireEncoder stochastic(SrKey key, size_t base) { return {kStochastic, nullptr, key, base}; }
+};
+// Sender stage: pack shards 0..n_shards-1 of `in`, shard s stored at dst.p[s]; a null destination skips its shard
+// entirely (neither encoded nor fed back). plain: every shard alike. feedback: x = f32(in) + residual (one f32 add; the
+// group exponent comes from x), residual' = x - dec(enc(x)) (one f32 subtract; dec is the decoder's real output).
+// feedback and stochastic: shard self_shard (-1: none) takes the plain encoder, from `in` alone, and its residual is
+// left alone. peers: the destinations are peers' receive slots — the P2P grid cap, and a system-scope release at the
+// end so a peer may read the stores once the (stream-ordered) ready flag is set; otherwise a local buffer, the
+// ordinary grid and no release.
 void launch_wire_pack_to(int codec, int in_dtype, const void* in, const WirePtrs& dst, size_t n_s, int n_shards,
-                         hipStream_t stream);
-// launch_wire_reduce whose encoded output is stored to every non-null dst.p[i] (i < n_dst), with a system-scope
-// release at the end (the owner's reduced shard goes straight into every peer's receive slot).
+                         int self_shard, const WireEncoder& enc, bool peers, hipStream_t stream);
+// Owner stage: launch_wire_reduce (local operand required) whose encoded output is stored to every non-null dst.p[i]
+// (i < n_dst; `peers` as above: the owner's reduced shard goes straight into every peer's receive slot). feedback:
+// y = (the slots' sum) + residual, the add after the slot sum, residual' = y - dec(enc(y)); `residual` is the owner
+// shard's n_s elements of the plane. stochastic: the sum is encoded once, every destination receives the same words;
+// `base` is the owner shard's first element in the bucket. Both lane layouts (set_wire_reduce4), the same bits.
 void launch_wire_reduce_to(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
-                           const void* local, const WirePtrs& dst, int n_dst, size_t n_s, hipStream_t stream);
-// Error feedback (residual compensation) for the two encoders of the mesh schedule, BFP codecs only. `residual` is the
-// bucket's f32 plane on this rank (16-B aligned, zeroed by the caller before the bucket's first request), updated in
-// place; ops/bfp_oracle.py ef_pack / ef_reduce define the bits.
-// Sender stage: launch_wire_pack_to over x = f32(in) + residual (one f32 add; the group exponent comes from x) with
-// residual' = x - dec(enc(x)) (one f32 subtract; dec is the decoder's real output). Shard self_shard (-1: none) is
-// encoded from `in` alone and its residual is left alone; a null destination skips its shard entirely (neither encoded
-// nor fed back). peers: the destinations are peers' receive slots (the P2P grid cap and release of
-// launch_wire_pack_to); otherwise a local buffer, the ordinary grid and no release.
-void launch_wire_pack_ef(int codec, int in_dtype, const void* in, float* residual, const WirePtrs& dst, size_t n_s,
-                         int n_shards, int self_shard, bool peers, hipStream_t stream);
-// Owner stage: launch_wire_reduce_to (local operand required) over y = (the slots' sum) + residual, the add after the
-// slot sum; residual' = y - dec(enc(y)). `residual` is the owner shard's n_s elements of the plane. Both lane layouts
-// (set_wire_reduce4), the same bits. The output goes to every non-null dst.p[i] (i < n_dst; `peers` as above) or, in
-// the second form, to the one local buffer out_wire.
-void launch_wire_reduce_ef(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
-                           const void* local, float* residual, const WirePtrs& dst, int n_dst, size_t n_s, bool peers,
-                           hipStream_t stream);
-void launch_wire_reduce_ef(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
-                           const void* local, float* residual, void* out_wire, size_t n_s, hipStream_t stream);
-// Stochastic rounding for the two encoders of the mesh schedule, kBfpRne and kBfp4Rne only; stateless, and the wire
-// format is unchanged. ops/bfp_oracle.py sr_pack / sr_reduce define the bits, which do not depend on the grid or the
-// lane layout. `base` is the bucket index of the launch's first element; the launch's last index must be below 2^32.
-// Sender stage: launch_wire_pack_to with key = sr_key(seed, rank, 0). Shard self_shard (-1: none) takes the plain rne
-// encoder; a null destination skips its shard. `peers` as launch_wire_pack_ef.
-void launch_wire_pack_sr(int codec, int in_dtype, const void* in, const WirePtrs& dst, size_t n_s, int n_shards,
-                         int self_shard, SrKey key, size_t base, bool peers, hipStream_t stream);
-// Owner stage: launch_wire_reduce_to (local operand required) with key = sr_key(seed, rank, 1); `base` is the owner
-// shard's first element in the bucket. Both lane layouts (set_wire_reduce4), the same bits. The output goes to every
-// non-null dst.p[i] (i < n_dst) or, in the second form, to the one local buffer out_wire.
-void launch_wire_reduce_sr(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
-                           const void* local, const WirePtrs& dst, int n_dst, size_t n_s, SrKey key, size_t base,
+                           const void* local, const WirePtrs& dst, int n_dst, size_t n_s, const WireEncoder& enc,
                            bool peers, hipStream_t stream);
-void launch_wire_reduce_sr(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
-                           const void* local, void* out_wire, size_t n_s, SrKey key, size_t base, hipStream_t stream);
 // Sharded update of the owner's shard (engine shard_update mode, ZeRO-1 style): sum the N received wire shards
 // (slot self_pos replaced by the dense local operand), take the sum through the wire codec's round trip in registers
 // (exactly the values every rank would decode from the re-encoded owner shard in the unsharded schedule), apply SGD to

@@ -20,10 +20,13 @@
 //   trust ratio  = AdamW scaled per bucket by ||w|| / ||update|| (LAMB): no element may move before two norms over
 //                  the whole bucket exist, so three launches — wire_lamb_moments (pass 1), lamb_ratio,
 //                  wire_lamb_apply (pass 2) — with a deterministic fp64 reduction in between (no atomics).
-//   error feedback = no counterpart in the reference (what its adapter drops is gone): wire_pack_ef and wire_reduce_ef,
-//                  the mesh schedule's two encoders with a per-rank f32 residual plane beside the unchanged wire.
-//   stochastic rounding = no counterpart either: wire_pack_sr and wire_reduce_sr, the same two encoders rounding up
-//                  with probability equal to the dropped fraction (a counter-based hash per 4 values, no state).
+//   wire_pack_to, wire_reduce_to = the mesh schedule's two encoders, each one kernel (traversal, destination table,
+//                  release) over an encoder policy: EncPlain, the codec as it is, and two forms without a counterpart
+//                  in the reference —
+//   error feedback = EncFeedback (what the reference's adapter drops is gone): a per-rank f32 residual plane beside the
+//                  unchanged wire;
+//   stochastic rounding = EncStochastic: rounding up with probability equal to the dropped fraction (a counter-based
+//                  hash per 4 values, no state).
 #include "bfp/bfp_format.h"
 
 #include <algorithm>
@@ -181,40 +184,129 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
-// Direct-transport variants: pack / reduce store their encoded output into a table of destinations (peers'
-// receive slots over xGMI), then release at system scope before the kernel retires.
-template <typename TIN, int C>
-__global__ void __launch_bounds__(kBlock) wire_pack_to_kernel(const TIN* __restrict__ in, WirePtrs dst, size_t n_s,
-                                                             int n_shards, int rel) {
+// ---------------------------------------------------------------- the mesh schedule's two encoders
+// Pack and reduce with the encoded output stored into a table of destinations (the copying transports' buffers, or
+// peers' receive slots over xGMI), then the release before the kernel retires. Each kernel holds its traversal once and
+// is instantiated over an encoder policy Enc, the device side of bfp_format.h WireEncoder: the form's arguments by
+// value, and what happens between "the lane's values are in registers" and the end of the loop trip, chosen at compile
+// time (`if constexpr` in the kernel bodies: as device functions of the policy structs the same statements cost the
+// feedback kernels registers and one of them a wave, profiles/wire_encoder_fold_resources.txt). No form uses atomics
+// or LDS; the arithmetic and the store order of each are its own and are NOT shared.
+enum EncForm { kEncPlain, kEncFeedback, kEncStochastic };
+
+struct EncPlain {  // the codec as it is
+  static constexpr EncForm kForm = kEncPlain;
+  template <int C>
+  static constexpr bool kHas = true;
+};
+
+// Error feedback (bfp_oracle.ef_pack / ef_reduce): both encoders keep what they drop. The f32 residual plane enters the
+// encoder's input with one f32 add, and x - dec(enc(x)) (one f32 subtract; dec is the decoder's real output,
+// Lanes*::roundtrip) is stored back at the same elements. A lane reads and writes only its own elements of the plane,
+// and the two stages cover disjoint shards of it. resid: the sender's whole plane / the owner shard's part of it.
+struct EncFeedback {
+  static constexpr EncForm kForm = kEncFeedback;
+  template <int C>
+  static constexpr bool kHas = codec_shared_exp(C);  // (a raw codec drops nothing)
+  float* resid;
+};
+
+// Stochastic rounding (bfp_oracle.sr_pack / sr_reduce): the unbiased rounding of bfp_format.h SrLanes, no state; the
+// element index that selects the random byte is base + (offset in the launch), whatever the grid.
+struct EncStochastic {
+  static constexpr EncForm kForm = kEncStochastic;
+  template <int C>
+  static constexpr bool kHas = codec_sr(C);
+  SrKey key;
+  uint32_t base;
+};
+
+// Sender stage: a group per lane; a null destination skips its shard entirely. Plain: every shard alike, and the
+// release is unconditional (p2p_release of a negative mode does nothing). The other two: shard self_shard takes the
+// plain encoder (a grid-uniform branch) from `in` alone, its residual neither read nor written; rel < 0 (a local
+// output) skips the release.
+template <typename TIN, int C, typename Enc>
+__global__ void __launch_bounds__(kBlock)
+    wire_pack_to_kernel(const TIN* __restrict__ in, WirePtrs dst, size_t n_s, int n_shards, int rel, int self_shard,
+                        Enc enc) {
+  static_assert(Enc::template kHas<C>, "not a form of this codec");
   const size_t tasks = n_s >> 4;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (int s = 0; s < n_shards; ++s) {
     uint8_t* d = dst.p[s];
     if (d == nullptr) continue;
-    const TIN* src = in + (size_t)s * n_s;
+    const size_t se = (size_t)s * n_s;  // the shard's first element
+    const TIN* src = in + se;
+    const bool self = s == self_shard;  // (uniform over the grid)
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
       float v[16];
       DenseLane16<TIN>::load16(src, t << 4, v);
-      WireLane16<C>::store16(d, n_s, t << 4, v);
+      if constexpr (Enc::kForm == kEncFeedback) {
+        float* e = enc.resid + se;
+        if (!self) {
+          float r[16];
+          DenseLane16<float>::load16(e, t << 4, r);
+#pragma unroll
+          for (int j = 0; j < 16; ++j) v[j] = v[j] + r[j];
+        }
+        WireLane16<C>::store16(d, n_s, t << 4, v);
+        if (!self) {
+          float q[16];
+#pragma unroll
+          for (int j = 0; j < 16; ++j) q[j] = v[j];
+          Lanes16<C>::roundtrip(q);
+#pragma unroll
+          for (int j = 0; j < 16; ++j) q[j] = v[j] - q[j];
+          DenseLane16<float>::store16(e, t << 4, q);
+        }
+      } else if constexpr (Enc::kForm == kEncStochastic) {
+        const uint32_t i = enc.base + (uint32_t)se + (uint32_t)(t << 4);  // the group's first element in the bucket
+        if (self) WireLane16<C>::store16(d, n_s, t << 4, v);
+        else SrLanes<Lanes16<C>>::store_wire(&d, 1, n_s, t << 4, v, enc.key, i);
+      } else {
+        WireLane16<C>::store16(d, n_s, t << 4, v);
+      }
     }
   }
-  p2p_release(rel);
+  if (Enc::kForm == kEncPlain || rel >= 0) p2p_release(rel);
 }
 
-template <typename L, typename TL>
+// Owner stage, in either lane layout (same operations per value, so the same bits): the slots' sum to every non-null
+// destination (a wave-uniform condition: every lane of a group's segment stores). Plain: one encode per destination.
+// Feedback: y = sum + residual to the destinations, then y - roundtrip(y) stored back. Stochastic: the sum is encoded
+// once and the same words go to every destination. The release as in the sender.
+template <typename L, typename TL, typename Enc>
 __global__ void __launch_bounds__(kBlock)
     wire_reduce_to_kernel(const uint8_t* __restrict__ slots, size_t slot_stride, int n_slots, int self_pos,
-                          const TL* __restrict__ local, WirePtrs dst, int n_dst, size_t n_s, int rel) {
+                          const TL* __restrict__ local, WirePtrs dst, int n_dst, size_t n_s, int rel, Enc enc) {
   const size_t tasks = n_s / L::kVals;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
     const size_t le = t * L::kVals;
     float acc[L::kVals];
     sum_slots<L>(slots, slot_stride, n_slots, self_pos, local, n_s, le, acc);
-    for (int i = 0; i < n_dst; ++i)  // wave-uniform condition: every lane of a group's segment stores
-      if (dst.p[i] != nullptr) L::store_wire(dst.p[i], n_s, le, acc);
+    if constexpr (Enc::kForm == kEncStochastic) {
+      SrLanes<L>::store_wire(dst.p, n_dst, n_s, le, acc, enc.key, enc.base + (uint32_t)le);
+    } else {
+      float e[L::kVals];
+      if constexpr (Enc::kForm == kEncFeedback) {
+        L::load_dense(enc.resid, le, e);
+#pragma unroll
+        for (int j = 0; j < L::kVals; ++j) acc[j] = acc[j] + e[j];
+      }
+      for (int i = 0; i < n_dst; ++i)
+        if (dst.p[i] != nullptr) L::store_wire(dst.p[i], n_s, le, acc);
+      if constexpr (Enc::kForm == kEncFeedback) {
+#pragma unroll
+        for (int j = 0; j < L::kVals; ++j) e[j] = acc[j];
+        L::roundtrip(e);
+#pragma unroll
+        for (int j = 0; j < L::kVals; ++j) e[j] = acc[j] - e[j];
+        L::store_f32(enc.resid, le, e);
+      }
+    }
   }
-  p2p_release(rel);
+  if (Enc::kForm == kEncPlain || rel >= 0) p2p_release(rel);
 }
 
 // The merged reduce-and-update of the owner's shard: the slots' sum through the codec's round trip, then the update
@@ -255,124 +347,6 @@ __global__ void __launch_bounds__(kBlock)
     }
     for (int i = 0; i < n_dst; ++i)
       if (dst.p[i] != nullptr) L::store_bf16(reinterpret_cast<bf16_t*>(dst.p[i]), le, w);
-  }
-  if (rel >= 0) p2p_release(rel);
-}
-
-// ---------------------------------------------------------------- error feedback (bfp_oracle.ef_pack / ef_reduce)
-// Both encoders of the mesh schedule keep what they drop: the f32 residual plane of the bucket enters the encoder's
-// input with one f32 add, and x - dec(enc(x)) (one f32 subtract; dec is the decoder's real output, Lanes*::roundtrip)
-// is stored back at the same elements. A lane reads and writes only its own elements of the plane, the two kernels
-// cover disjoint shards of it, and neither uses atomics or LDS.
-
-// Sender stage: wire_pack_to_kernel's traversal (a group per lane, destination table, release mode; rel < 0: a local
-// output, no release). Shard self_shard is encoded from `in` alone and its residual is neither read nor written; a
-// null destination skips its shard entirely.
-template <typename TIN, int C>
-__global__ void __launch_bounds__(kBlock)
-    wire_pack_ef_kernel(const TIN* __restrict__ in, float* __restrict__ resid, WirePtrs dst, size_t n_s, int n_shards,
-                        int self_shard, int rel) {
-  const size_t tasks = n_s >> 4;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (int s = 0; s < n_shards; ++s) {
-    uint8_t* d = dst.p[s];
-    if (d == nullptr) continue;
-    const TIN* src = in + (size_t)s * n_s;
-    float* e = resid + (size_t)s * n_s;
-    const bool fed = s != self_shard;  // (uniform over the grid)
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
-      float v[16];
-      DenseLane16<TIN>::load16(src, t << 4, v);
-      if (fed) {
-        float r[16];
-        DenseLane16<float>::load16(e, t << 4, r);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) v[j] = v[j] + r[j];
-      }
-      WireLane16<C>::store16(d, n_s, t << 4, v);
-      if (fed) {
-        float q[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) q[j] = v[j];
-        Lanes16<C>::roundtrip(q);
-#pragma unroll
-        for (int j = 0; j < 16; ++j) q[j] = v[j] - q[j];
-        DenseLane16<float>::store16(e, t << 4, q);
-      }
-    }
-  }
-  if (rel >= 0) p2p_release(rel);
-}
-
-// Owner stage: wire_reduce_to_kernel's body with y = (the slots' sum) + residual encoded to every destination and
-// y - roundtrip(y) stored back, in either lane layout (same operations per value, so the same bits). `resid` is the
-// owner shard's part of the plane.
-template <typename L, typename TL>
-__global__ void __launch_bounds__(kBlock)
-    wire_reduce_ef_kernel(const uint8_t* __restrict__ slots, size_t slot_stride, int n_slots, int self_pos,
-                          const TL* __restrict__ local, float* __restrict__ resid, WirePtrs dst, int n_dst, size_t n_s,
-                          int rel) {
-  const size_t tasks = n_s / L::kVals;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
-    const size_t le = t * L::kVals;
-    float acc[L::kVals], e[L::kVals];
-    sum_slots<L>(slots, slot_stride, n_slots, self_pos, local, n_s, le, acc);
-    L::load_dense(resid, le, e);
-#pragma unroll
-    for (int j = 0; j < L::kVals; ++j) acc[j] = acc[j] + e[j];
-    for (int i = 0; i < n_dst; ++i)  // wave-uniform condition: every lane of a group's segment stores
-      if (dst.p[i] != nullptr) L::store_wire(dst.p[i], n_s, le, acc);
-#pragma unroll
-    for (int j = 0; j < L::kVals; ++j) e[j] = acc[j];
-    L::roundtrip(e);
-#pragma unroll
-    for (int j = 0; j < L::kVals; ++j) e[j] = acc[j] - e[j];
-    L::store_f32(resid, le, e);
-  }
-  if (rel >= 0) p2p_release(rel);
-}
-
-// ---------------------------------------------------------------- stochastic rounding (bfp_oracle.sr_pack / sr_reduce)
-// The same two encoders with the unbiased rounding of bfp_format.h SrLanes: no state, no atomics, no LDS; the element
-// index that selects the random byte is base + (offset in the launch), whatever the grid.
-
-// Sender stage: wire_pack_to_kernel's traversal; shard self_shard takes the plain rne store (grid-uniform branch).
-template <typename TIN, int C>
-__global__ void __launch_bounds__(kBlock)
-    wire_pack_sr_kernel(const TIN* __restrict__ in, WirePtrs dst, size_t n_s, int n_shards, int self_shard, SrKey key,
-                        uint32_t base, int rel) {
-  const size_t tasks = n_s >> 4;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (int s = 0; s < n_shards; ++s) {
-    uint8_t* d = dst.p[s];
-    if (d == nullptr) continue;
-    const TIN* src = in + (size_t)s * n_s;
-    const uint32_t sbase = base + (uint32_t)((size_t)s * n_s);
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
-      float v[16];
-      DenseLane16<TIN>::load16(src, t << 4, v);
-      if (s == self_shard) WireLane16<C>::store16(d, n_s, t << 4, v);
-      else SrLanes<Lanes16<C>>::store_wire(&d, 1, n_s, t << 4, v, key, sbase + (uint32_t)(t << 4));
-    }
-  }
-  if (rel >= 0) p2p_release(rel);
-}
-
-// Owner stage: wire_reduce_to_kernel's body, the sum encoded once and stored to every destination, in either lane
-// layout (same operations per value, so the same bits).
-template <typename L, typename TL>
-__global__ void __launch_bounds__(kBlock)
-    wire_reduce_sr_kernel(const uint8_t* __restrict__ slots, size_t slot_stride, int n_slots, int self_pos,
-                          const TL* __restrict__ local, WirePtrs dst, int n_dst, size_t n_s, SrKey key, uint32_t base,
-                          int rel) {
-  const size_t tasks = n_s / L::kVals;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
-    const size_t le = t * L::kVals;
-    float acc[L::kVals];
-    sum_slots<L>(slots, slot_stride, n_slots, self_pos, local, n_s, le, acc);
-    SrLanes<L>::store_wire(dst.p, n_dst, n_s, le, acc, key, base + (uint32_t)le);
   }
   if (rel >= 0) p2p_release(rel);
 }
@@ -516,54 +490,48 @@ __global__ void __launch_bounds__(kBlock)
             }
           }
         }
-        Em = SrLanes<Lanes16<kBfpRne>>::exponent(m);
-        Er = SrLanes<Lanes16<kBfpRne>>::exponent(r);
+        Em = bfp_group_exponent(m);
+        Er = bfp_group_exponent(r);
         uint32_t wm[4], wr[4];
         sr_encode_vals<kBfpRne, 16>(m, Em, key_m, (uint32_t)i, wm);
         sr_encode_vals<kBfpRne, 16, true>(r, Er, key_r, (uint32_t)i, wr);
         *reinterpret_cast<uint4*>(mom_q + i) = make_uint4(wm[0], wm[1], wm[2], wm[3]);
         *reinterpret_cast<uint4*>(var_q + i) = make_uint4(wr[0], wr[1], wr[2], wr[3]);
       }
-      // exponent planes: 4 lanes -> one dword, 4 dwords -> one 16-B store by lane 16k (WireLane16); every lane of the
-      // segment is here
-      uint32_t a4 = Em | ((uint32_t)__shfl_down((int)Em, 1) << 8) | ((uint32_t)__shfl_down((int)Em, 2) << 16) |
-                    ((uint32_t)__shfl_down((int)Em, 3) << 24);
-      uint32_t b4 = Er | ((uint32_t)__shfl_down((int)Er, 1) << 8) | ((uint32_t)__shfl_down((int)Er, 2) << 16) |
-                    ((uint32_t)__shfl_down((int)Er, 3) << 24);
-      const uint32_t a4b = (uint32_t)__shfl_down((int)a4, 4), a4c = (uint32_t)__shfl_down((int)a4, 8),
-                     a4d = (uint32_t)__shfl_down((int)a4, 12);
-      const uint32_t b4b = (uint32_t)__shfl_down((int)b4, 4), b4c = (uint32_t)__shfl_down((int)b4, 8),
-                     b4d = (uint32_t)__shfl_down((int)b4, 12);
+      // exponent planes: one 16-B store each by lane 16k (WireLane16); every lane of the segment is here
+      const uint4 em16 = bfp_gather_exponents(Em), er16 = bfp_gather_exponents(Er);
       if ((threadIdx.x & 15) == 0) {
-        *reinterpret_cast<uint4*>(mom_e + (i >> 4)) = make_uint4(a4, a4b, a4c, a4d);
-        *reinterpret_cast<uint4*>(var_e + (i >> 4)) = make_uint4(b4, b4b, b4c, b4d);
+        *reinterpret_cast<uint4*>(mom_e + (i >> 4)) = em16;
+        *reinterpret_cast<uint4*>(var_e + (i >> 4)) = er16;
       }
     }
   }
 }
 
 // ---------------------------------------------------------------- trust-ratio (LAMB) epilogue
-// Fixed-order fp64 sum over the workgroup: the wave's lanes by shuffles (32, 16, ... 1), then the waves' sums in wave
-// order by thread 0 through LDS. Every thread of the block must call it; the result is valid in thread 0.
-__device__ __forceinline__ void lamb_block_sum(double& a, double& b) {
-  __shared__ double red[2][kBlock / 64];
+// Fixed-order fp64 sums of kN values over the workgroup: the wave's lanes by shuffles (32, 16, ... 1), then the waves'
+// sums in wave order by thread 0 through LDS (an array per instantiation). Every thread of the block must call it; the
+// results are valid in thread 0.
+template <int kN>
+__device__ __forceinline__ void block_sum(double (&a)[kN]) {
+  __shared__ double red[kN][kBlock / 64];
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) {
-    a += __shfl_down(a, off);
-    b += __shfl_down(b, off);
+#pragma unroll
+    for (int k = 0; k < kN; ++k) a[k] += __shfl_down(a[k], off);
   }
   if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = a;
-    red[1][threadIdx.x >> 6] = b;
+#pragma unroll
+    for (int k = 0; k < kN; ++k) red[k][threadIdx.x >> 6] = a[k];
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    a = red[0][0];
-    b = red[1][0];
+#pragma unroll
+    for (int k = 0; k < kN; ++k) a[k] = red[k][0];
 #pragma unroll
     for (int i = 1; i < kBlock / 64; ++i) {
-      a += red[0][i];
-      b += red[1][i];
+#pragma unroll
+      for (int k = 0; k < kN; ++k) a[k] += red[k][i];
     }
   }
 }
@@ -616,22 +584,24 @@ __global__ void __launch_bounds__(kBlock)
       }
     }
   }
-  lamb_block_sum(sw, sr);
+  double sums[2] = {sw, sr};
+  block_sum(sums);
   if (threadIdx.x == 0) {
-    partials[2 * (size_t)blockIdx.x] = sw;
-    partials[2 * (size_t)blockIdx.x + 1] = sr;
+    partials[2 * (size_t)blockIdx.x] = sums[0];
+    partials[2 * (size_t)blockIdx.x + 1] = sums[1];
   }
 }
 
 __global__ void __launch_bounds__(kBlock)
     lamb_ratio_kernel(const double* __restrict__ partials, int n_pairs, float lr, float* __restrict__ words) {
-  double sw = 0.0, sr = 0.0;
+  double sums[2] = {0.0, 0.0};
   for (int i = threadIdx.x; i < n_pairs; i += kBlock) {
-    sw += partials[2 * (size_t)i];
-    sr += partials[2 * (size_t)i + 1];
+    sums[0] += partials[2 * (size_t)i];
+    sums[1] += partials[2 * (size_t)i + 1];
   }
-  lamb_block_sum(sw, sr);
+  block_sum(sums);
   if (threadIdx.x == 0) {
+    const double sw = sums[0], sr = sums[1];
     const bool ok = sw > 0.0 && sr > 0.0 && sw < __builtin_huge_val() && sr < __builtin_huge_val();
     const float phi = ok ? (float)sqrt(sw / sr) : 1.0f;
     words[0] = lr * phi;
@@ -677,21 +647,6 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 // ---------------------------------------------------------------- global-norm clipping
-// lamb_block_sum for one value: the same fixed order (lanes by shuffles 32 .. 1, then the waves in wave order by
-// thread 0). Every thread of the block must call it; the result is valid in thread 0.
-__device__ __forceinline__ void clip_block_sum(double& a) {
-  __shared__ double red[kBlock / 64];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) a += __shfl_down(a, off);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    a = red[0];
-#pragma unroll
-    for (int i = 1; i < kBlock / 64; ++i) a += red[i];
-  }
-}
-
 // The norm pass of a clip group over one gathered wire region: wire_sgd_kernel's traversal (shards, shard stride,
 // skipped shards, the n_valid tail inside a group), read-only. A lane owns a whole 16-value group per trip — the BFP
 // codecs' 17 bytes per 16 values arrive as ONE 16-B mantissa load plus the exponent byte, half the load instructions
@@ -722,8 +677,9 @@ __global__ void __launch_bounds__(kBlock)
       }
     }
   }
-  clip_block_sum(sum);
-  if (threadIdx.x == 0) partials[blockIdx.x] = sum;
+  double sums[1] = {sum};
+  block_sum(sums);
+  if (threadIdx.x == 0) partials[blockIdx.x] = sums[0];
 }
 
 // One block: S = the sum of every segment's partials — each lane takes, segment by segment in the order given,
@@ -739,8 +695,10 @@ __global__ void __launch_bounds__(kBlock)
     const int n = seg.n[k];
     for (int i = threadIdx.x; i < n; i += kBlock) sum += p[i];
   }
-  clip_block_sum(sum);
+  double sums[1] = {sum};
+  block_sum(sums);
   if (threadIdx.x == 0) {
+    sum = sums[0];
     const bool finite = sum < __builtin_huge_val();  // (false for NaN too; the squares' sum is never negative)
     const double total = sqrt(sum) * gs_abs;
     const double coef = finite ? fmin(1.0, max_norm / (total + 1e-6)) : __builtin_nan("");
@@ -1055,40 +1013,13 @@ void launch_wire_unpack_strided(int codec, int out_dtype, const void* in, size_t
   FAN_HIP_CHECK(hipGetLastError());
 }
 
-void launch_wire_pack_to(int codec, int in_dtype, const void* in, const WirePtrs& dst, size_t n_s, int n_shards,
-                         hipStream_t stream) {
-  check_ns(n_s);
-  FAN_CHECK(n_shards <= kMaxPeers, "pack_to: at most 16 destinations");
-  if (n_s == 0 || n_shards == 0) return;
-  const int grid = stream_grid(n_s / 16, kBlock, std::min(wire_max_blocks(), p2p_grid_cap()));
-  FAN_CODEC_SWITCH(codec, {
-    if (in_dtype == kF32)
-      hipLaunchKernelGGL((wire_pack_to_kernel<float, C>), grid, kBlock, 0, stream, (const float*)in, dst, n_s,
-                         n_shards, p2p_release_mode());
-    else
-      hipLaunchKernelGGL((wire_pack_to_kernel<bf16_t, C>), grid, kBlock, 0, stream, (const bf16_t*)in, dst, n_s,
-                         n_shards, p2p_release_mode());
-  });
-  FAN_HIP_CHECK(hipGetLastError());
-}
-
-void launch_wire_reduce_to(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
-                           const void* local, const WirePtrs& dst, int n_dst, size_t n_s, hipStream_t stream) {
-  check_ns(n_s);
-  FAN_CHECK(n_dst <= kMaxPeers && local != nullptr, "reduce_to: local operand and at most 16 destinations");
-  if (n_s == 0) return;
-  const uint8_t* sl = (const uint8_t*)slots;
-  const int cap = std::min(wire_max_blocks(), p2p_grid_cap());
-  FAN_CODEC_SWITCH(codec, with_lanes<C>(n_slots, n_s, cap, [&](auto lanes, int grid) {
-    using L = decltype(lanes);
-    if (local_dtype == kF32)
-      hipLaunchKernelGGL((wire_reduce_to_kernel<L, float>), grid, kBlock, 0, stream, sl, slot_stride, n_slots, self_pos,
-                         (const float*)local, dst, n_dst, n_s, p2p_release_mode());
-    else
-      hipLaunchKernelGGL((wire_reduce_to_kernel<L, bf16_t>), grid, kBlock, 0, stream, sl, slot_stride, n_slots,
-                         self_pos, (const bf16_t*)local, dst, n_dst, n_s, p2p_release_mode());
-  }));
-  FAN_HIP_CHECK(hipGetLastError());
+// Grid cap and release mode of a kernel whose destinations are peers' receive slots, or a local buffer's (no release).
+struct PeerLaunch {
+  int cap, rel;
+};
+static PeerLaunch peer_launch(bool peers) {
+  if (!peers) return {wire_max_blocks(), -1};
+  return {std::min(wire_max_blocks(), p2p_grid_cap()), p2p_release_mode()};
 }
 
 static void check_ef(int codec, const float* residual) {
@@ -1097,152 +1028,83 @@ static void check_ef(int codec, const float* residual) {
             "error feedback: a 16-B aligned f32 residual plane");
 }
 
-void launch_wire_pack_ef(int codec, int in_dtype, const void* in, float* residual, const WirePtrs& dst, size_t n_s,
-                         int n_shards, int self_shard, bool peers, hipStream_t stream) {
-  check_ns(n_s);
-  check_ef(codec, residual);
-  FAN_CHECK(n_shards <= kMaxPeers, "pack_ef: at most 16 destinations");
-  if (n_s == 0 || n_shards == 0) return;
-  const int cap = peers ? std::min(wire_max_blocks(), p2p_grid_cap()) : wire_max_blocks();
-  const int rel = peers ? p2p_release_mode() : -1;
-  const int grid = stream_grid(n_s / 16, kBlock, cap);
-#define FAN_PACK_EF(C)                                                                                              \
-  do {                                                                                                              \
-    if (in_dtype == kF32)                                                                                           \
-      hipLaunchKernelGGL((wire_pack_ef_kernel<float, C>), grid, kBlock, 0, stream, (const float*)in, residual, dst, \
-                         n_s, n_shards, self_shard, rel);                                                           \
-    else                                                                                                            \
-      hipLaunchKernelGGL((wire_pack_ef_kernel<bf16_t, C>), grid, kBlock, 0, stream, (const bf16_t*)in, residual,    \
-                         dst, n_s, n_shards, self_shard, rel);                                                      \
-  } while (0)
-  if (codec == kBfpTrunc) FAN_PACK_EF(kBfpTrunc);
-  else if (codec == kBfp4Rne) FAN_PACK_EF(kBfp4Rne);
-  else FAN_PACK_EF(kBfpRne);
-#undef FAN_PACK_EF
-  FAN_HIP_CHECK(hipGetLastError());
-}
-
-template <int C>
-static void reduce_ef_dispatch(int local_dtype, const uint8_t* sl, size_t slot_stride, int n_slots, int self_pos,
-                               const void* local, float* residual, const WirePtrs& dst, int n_dst, size_t n_s, int cap,
-                               int rel, hipStream_t stream) {
-  with_lanes<C>(n_slots, n_s, cap, [&](auto lanes, int grid) {
-    using L = decltype(lanes);
-    if (local_dtype == kF32)
-      hipLaunchKernelGGL((wire_reduce_ef_kernel<L, float>), grid, kBlock, 0, stream, sl, slot_stride, n_slots, self_pos,
-                         (const float*)local, residual, dst, n_dst, n_s, rel);
-    else
-      hipLaunchKernelGGL((wire_reduce_ef_kernel<L, bf16_t>), grid, kBlock, 0, stream, sl, slot_stride, n_slots,
-                         self_pos, (const bf16_t*)local, residual, dst, n_dst, n_s, rel);
-  });
-}
-
-void launch_wire_reduce_ef(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
-                           const void* local, float* residual, const WirePtrs& dst, int n_dst, size_t n_s, bool peers,
-                           hipStream_t stream) {
-  check_ns(n_s);
-  check_ef(codec, residual);
-  FAN_CHECK(n_dst >= 1 && n_dst <= kMaxPeers && local != nullptr,
-            "reduce_ef: local operand and 1 to 16 destinations");
-  FAN_CHECK(self_pos >= 0 && self_pos < n_slots, "reduce_ef: self_pos names the slot the local operand stands for");
-  if (n_s == 0) return;
-  const int cap = peers ? std::min(wire_max_blocks(), p2p_grid_cap()) : wire_max_blocks();
-  const int rel = peers ? p2p_release_mode() : -1;
-  const uint8_t* sl = (const uint8_t*)slots;
-  if (codec == kBfpTrunc)
-    reduce_ef_dispatch<kBfpTrunc>(local_dtype, sl, slot_stride, n_slots, self_pos, local, residual, dst, n_dst, n_s,
-                                  cap, rel, stream);
-  else if (codec == kBfp4Rne)
-    reduce_ef_dispatch<kBfp4Rne>(local_dtype, sl, slot_stride, n_slots, self_pos, local, residual, dst, n_dst, n_s, cap,
-                                 rel, stream);
-  else
-    reduce_ef_dispatch<kBfpRne>(local_dtype, sl, slot_stride, n_slots, self_pos, local, residual, dst, n_dst, n_s, cap,
-                                rel, stream);
-  FAN_HIP_CHECK(hipGetLastError());
-}
-
-void launch_wire_reduce_ef(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
-                           const void* local, float* residual, void* out_wire, size_t n_s, hipStream_t stream) {
-  WirePtrs dst{};
-  dst.p[0] = (uint8_t*)out_wire;
-  FAN_CHECK(out_wire != nullptr, "reduce_ef needs an output");
-  launch_wire_reduce_ef(codec, local_dtype, slots, slot_stride, n_slots, self_pos, local, residual, dst, 1, n_s, false,
-                        stream);
-}
-
 static void check_sr(int codec, size_t base, size_t n) {
   FAN_CHECK(codec_sr(codec), "stochastic rounding: bfp_rne and bfp4_rne only");
   FAN_CHECK(base % 16 == 0 && base <= ((size_t)1 << 32) && n <= ((size_t)1 << 32) - base,
             "stochastic rounding: element indices must stay below 2^32");
 }
 
-void launch_wire_pack_sr(int codec, int in_dtype, const void* in, const WirePtrs& dst, size_t n_s, int n_shards,
-                         int self_shard, SrKey key, size_t base, bool peers, hipStream_t stream) {
+static const char* enc_suffix(const WireEncoder& enc) {
+  return enc.kind == WireEncoder::kFeedback ? "ef" : enc.kind == WireEncoder::kStochastic ? "sr" : "to";
+}
+
+// launch(e) with e the device policy of `enc`; only the forms codec C has are instantiated (check_ef / check_sr have
+// refused the others).
+template <int C, typename F>
+static void with_encoder(const WireEncoder& enc, F&& launch) {
+  if (enc.kind == WireEncoder::kPlain) return launch(EncPlain{});
+  if constexpr (EncFeedback::kHas<C>) {
+    if (enc.kind == WireEncoder::kFeedback) return launch(EncFeedback{enc.residual});
+  }
+  if constexpr (EncStochastic::kHas<C>) {
+    if (enc.kind == WireEncoder::kStochastic) return launch(EncStochastic{enc.key, (uint32_t)enc.base});
+  }
+  FAN_CHECK(false, "wire encoder: not a form of this codec");
+}
+
+void launch_wire_pack_to(int codec, int in_dtype, const void* in, const WirePtrs& dst, size_t n_s, int n_shards,
+                         int self_shard, const WireEncoder& enc, bool peers, hipStream_t stream) {
+  const bool sr = enc.kind == WireEncoder::kStochastic;
   check_ns(n_s);
-  FAN_CHECK(n_shards >= 0 && n_shards <= kMaxPeers, "pack_sr: at most 16 destinations");
-  check_sr(codec, base, n_s * (size_t)n_shards);
+  if (enc.kind == WireEncoder::kFeedback) check_ef(codec, enc.residual);
+  FAN_CHECK((!sr || n_shards >= 0) && n_shards <= kMaxPeers,
+            std::string("pack_") + enc_suffix(enc) + ": at most 16 destinations");
+  if (sr) check_sr(codec, enc.base, n_s * (size_t)n_shards);
   if (n_s == 0 || n_shards == 0) return;
-  const int cap = peers ? std::min(wire_max_blocks(), p2p_grid_cap()) : wire_max_blocks();
-  const int rel = peers ? p2p_release_mode() : -1;
-  const int grid = stream_grid(n_s / 16, kBlock, cap);
-#define FAN_PACK_SR(C)                                                                                               \
-  do {                                                                                                               \
-    if (in_dtype == kF32)                                                                                            \
-      hipLaunchKernelGGL((wire_pack_sr_kernel<float, C>), grid, kBlock, 0, stream, (const float*)in, dst, n_s,       \
-                         n_shards, self_shard, key, (uint32_t)base, rel);                                            \
-    else                                                                                                             \
-      hipLaunchKernelGGL((wire_pack_sr_kernel<bf16_t, C>), grid, kBlock, 0, stream, (const bf16_t*)in, dst, n_s,     \
-                         n_shards, self_shard, key, (uint32_t)base, rel);                                            \
-  } while (0)
-  if (codec == kBfp4Rne) FAN_PACK_SR(kBfp4Rne);
-  else FAN_PACK_SR(kBfpRne);
-#undef FAN_PACK_SR
+  const PeerLaunch pl = peer_launch(peers);
+  const int grid = stream_grid(n_s / 16, kBlock, pl.cap);
+  FAN_CODEC_SWITCH(codec, with_encoder<C>(enc, [&](auto e) {
+    using Enc = decltype(e);
+    if (in_dtype == kF32)
+      hipLaunchKernelGGL((wire_pack_to_kernel<float, C, Enc>), grid, kBlock, 0, stream, (const float*)in, dst, n_s,
+                         n_shards, pl.rel, self_shard, e);
+    else
+      hipLaunchKernelGGL((wire_pack_to_kernel<bf16_t, C, Enc>), grid, kBlock, 0, stream, (const bf16_t*)in, dst, n_s,
+                         n_shards, pl.rel, self_shard, e);
+  }));
   FAN_HIP_CHECK(hipGetLastError());
 }
 
-template <int C>
-static void reduce_sr_dispatch(int local_dtype, const uint8_t* sl, size_t slot_stride, int n_slots, int self_pos,
-                               const void* local, const WirePtrs& dst, int n_dst, size_t n_s, SrKey key, uint32_t base,
-                               int cap, int rel, hipStream_t stream) {
-  with_lanes<C>(n_slots, n_s, cap, [&](auto lanes, int grid) {
-    using L = decltype(lanes);
-    if (local_dtype == kF32)
-      hipLaunchKernelGGL((wire_reduce_sr_kernel<L, float>), grid, kBlock, 0, stream, sl, slot_stride, n_slots, self_pos,
-                         (const float*)local, dst, n_dst, n_s, key, base, rel);
-    else
-      hipLaunchKernelGGL((wire_reduce_sr_kernel<L, bf16_t>), grid, kBlock, 0, stream, sl, slot_stride, n_slots,
-                         self_pos, (const bf16_t*)local, dst, n_dst, n_s, key, base, rel);
-  });
-}
-
-void launch_wire_reduce_sr(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
-                           const void* local, const WirePtrs& dst, int n_dst, size_t n_s, SrKey key, size_t base,
+void launch_wire_reduce_to(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
+                           const void* local, const WirePtrs& dst, int n_dst, size_t n_s, const WireEncoder& enc,
                            bool peers, hipStream_t stream) {
   check_ns(n_s);
-  check_sr(codec, base, n_s);
-  FAN_CHECK(n_dst >= 1 && n_dst <= kMaxPeers && local != nullptr,
-            "reduce_sr: local operand and 1 to 16 destinations");
-  FAN_CHECK(self_pos >= 0 && self_pos < n_slots, "reduce_sr: self_pos names the slot the local operand stands for");
+  if (enc.kind == WireEncoder::kPlain) {
+    FAN_CHECK(n_dst <= kMaxPeers && local != nullptr, "reduce_to: local operand and at most 16 destinations");
+  } else {
+    const std::string name = std::string("reduce_") + enc_suffix(enc);
+    if (enc.kind == WireEncoder::kFeedback) check_ef(codec, enc.residual);
+    else check_sr(codec, enc.base, n_s);
+    FAN_CHECK(n_dst >= 1 && n_dst <= kMaxPeers && local != nullptr,
+              name + ": local operand and 1 to 16 destinations");
+    FAN_CHECK(self_pos >= 0 && self_pos < n_slots, name + ": self_pos names the slot the local operand stands for");
+  }
   if (n_s == 0) return;
-  const int cap = peers ? std::min(wire_max_blocks(), p2p_grid_cap()) : wire_max_blocks();
-  const int rel = peers ? p2p_release_mode() : -1;
   const uint8_t* sl = (const uint8_t*)slots;
-  if (codec == kBfp4Rne)
-    reduce_sr_dispatch<kBfp4Rne>(local_dtype, sl, slot_stride, n_slots, self_pos, local, dst, n_dst, n_s, key,
-                                 (uint32_t)base, cap, rel, stream);
-  else
-    reduce_sr_dispatch<kBfpRne>(local_dtype, sl, slot_stride, n_slots, self_pos, local, dst, n_dst, n_s, key,
-                                (uint32_t)base, cap, rel, stream);
+  const PeerLaunch pl = peer_launch(peers);
+  FAN_CODEC_SWITCH(codec, with_encoder<C>(enc, [&](auto e) {
+    using Enc = decltype(e);
+    with_lanes<C>(n_slots, n_s, pl.cap, [&](auto lanes, int grid) {
+      using L = decltype(lanes);
+      if (local_dtype == kF32)
+        hipLaunchKernelGGL((wire_reduce_to_kernel<L, float, Enc>), grid, kBlock, 0, stream, sl, slot_stride, n_slots,
+                           self_pos, (const float*)local, dst, n_dst, n_s, pl.rel, e);
+      else
+        hipLaunchKernelGGL((wire_reduce_to_kernel<L, bf16_t, Enc>), grid, kBlock, 0, stream, sl, slot_stride, n_slots,
+                           self_pos, (const bf16_t*)local, dst, n_dst, n_s, pl.rel, e);
+    });
+  }));
   FAN_HIP_CHECK(hipGetLastError());
-}
-
-void launch_wire_reduce_sr(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots, int self_pos,
-                           const void* local, void* out_wire, size_t n_s, SrKey key, size_t base, hipStream_t stream) {
-  WirePtrs dst{};
-  dst.p[0] = (uint8_t*)out_wire;
-  FAN_CHECK(out_wire != nullptr, "reduce_sr needs an output");
-  launch_wire_reduce_sr(codec, local_dtype, slots, slot_stride, n_slots, self_pos, local, dst, 1, n_s, key, base, false,
-                        stream);
 }
 
 static std::atomic<int>& reduce4_flag() {
@@ -1265,12 +1127,11 @@ static void launch_reduce_update(int codec, int local_dtype, const void* slots, 
             "reduce_sgd: local operand, master shard and at most 16 destinations");
   if (n_s == 0) return;
   const uint8_t* sl = (const uint8_t*)slots;
-  const int cap = peers ? std::min(wire_max_blocks(), p2p_grid_cap()) : wire_max_blocks();
-  const int rel = peers ? p2p_release_mode() : -1;
+  const PeerLaunch pl = peer_launch(peers);
 #define FAN_RSGD(TL, MOM)                                                                                         \
   hipLaunchKernelGGL((wire_reduce_sgd_kernel<L, TL, MOM, P>), grid, kBlock, 0, stream, sl, slot_stride, n_slots, \
-                     self_pos, (const TL*)local, master, mom, p, n_valid, dst, n_dst, n_s, rel)
-  FAN_CODEC_SWITCH(codec, with_lanes<C>(n_slots, n_s, cap, [&](auto lanes, int grid) {
+                     self_pos, (const TL*)local, master, mom, p, n_valid, dst, n_dst, n_s, pl.rel)
+  FAN_CODEC_SWITCH(codec, with_lanes<C>(n_slots, n_s, pl.cap, [&](auto lanes, int grid) {
     using L = decltype(lanes);
     if (local_dtype == kF32) {
       if (kAdam || mom) FAN_RSGD(float, true);

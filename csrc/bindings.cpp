@@ -37,22 +37,25 @@ void wire_pack(const at::Tensor& x, at::Tensor& out, int64_t shard_elems, int64_
                         fan_stream());
 }
 
-// shard s of x encoded straight into dsts[s] (each a uint8 view, e.g. a peer's receive-arena slot); ends with a
-// system-scope release (the direct P2P transport's producer kernel)
-void wire_pack_to(const at::Tensor& x, const std::vector<at::Tensor>& dsts, int64_t shard_elems, int64_t codec) {
+// shard s of x encoded straight into dsts[s] (each a uint8 view, e.g. a peer's receive-arena slot; a None entry is a
+// null destination: its shard is skipped); ends with a system-scope release (the direct P2P transport's producer kernel)
+void wire_pack_to(const at::Tensor& x, const std::vector<c10::optional<at::Tensor>>& dsts, int64_t shard_elems,
+                  int64_t codec) {
   FAN_T_CUDA_CONTIG(x);
   TORCH_CHECK(x.numel() == shard_elems * (int64_t)dsts.size(), "one destination per shard");
   TORCH_CHECK(dsts.size() <= (size_t)fan::kMaxPeers, "at most 16 destinations");
   fan::WirePtrs to{};
   for (size_t i = 0; i < dsts.size(); ++i) {
-    TORCH_CHECK(dsts[i].is_cuda() && dsts[i].scalar_type() == at::kByte &&
-                    (size_t)dsts[i].numel() >= fan::wire_shard_bytes((int)codec, shard_elems) &&
-                    ((uintptr_t)dsts[i].data_ptr() & 15) == 0,
+    if (!dsts[i] || !dsts[i]->defined()) continue;
+    const at::Tensor& d = *dsts[i];
+    TORCH_CHECK(d.is_cuda() && d.scalar_type() == at::kByte &&
+                    (size_t)d.numel() >= fan::wire_shard_bytes((int)codec, shard_elems) &&
+                    ((uintptr_t)d.data_ptr() & 15) == 0,
                 "destination ", i, ": 16-B aligned uint8 buffer of one wire shard");
-    to.p[i] = dsts[i].data_ptr<uint8_t>();
+    to.p[i] = d.data_ptr<uint8_t>();
   }
-  fan::launch_wire_pack_to((int)codec, dtype_code(x), x.data_ptr(), to, (size_t)shard_elems, (int)dsts.size(),
-                           fan_stream());
+  fan::launch_wire_pack_to((int)codec, dtype_code(x), x.data_ptr(), to, (size_t)shard_elems, (int)dsts.size(), -1, {},
+                           true, fan_stream());
 }
 
 void wire_pack_range(const at::Tensor& x, at::Tensor& out, int64_t shard_elems, int64_t begin, int64_t end,

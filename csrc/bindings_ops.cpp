@@ -418,7 +418,8 @@ void col_sum(const at::Tensor& x, at::Tensor& out, double scale, bool accumulate
                  workspace.data_ptr<float>(), fan_stream());
 }
 
-// The error-feedback wire ops (bfp_format.h launch_wire_pack_ef / launch_wire_reduce_ef). Every destination is one wire
+// The error-feedback wire ops (bfp_format.h launch_wire_pack_to / launch_wire_reduce_to with WireEncoder::feedback).
+// Every destination is one wire
 // shard's uint8 buffer, 16-B aligned; a None entry is a null destination.
 float* ef_plane(at::Tensor& residual, int64_t need) {
   FAN_T_CUDA_CONTIG(residual);
@@ -449,8 +450,8 @@ void wire_pack_ef(const at::Tensor& x, at::Tensor& residual, const std::vector<c
   TORCH_CHECK(residual.device() == x.device(), "residual: on the gradient's device");
   float* e = ef_plane(residual, x.numel());
   const WirePtrs to = ef_dsts(dsts, wire_shard_bytes((int)codec, (size_t)shard_elems), x);
-  launch_wire_pack_ef((int)codec, dcode(x), x.data_ptr(), e, to, (size_t)shard_elems, (int)dsts.size(),
-                      (int)self_shard, false, fan_stream());
+  launch_wire_pack_to((int)codec, dcode(x), x.data_ptr(), to, (size_t)shard_elems, (int)dsts.size(), (int)self_shard,
+                      WireEncoder::feedback(e), false, fan_stream());
 }
 
 void wire_reduce_ef(const at::Tensor& slots, int64_t n_slots, int64_t self_pos, const at::Tensor& local,
@@ -470,11 +471,11 @@ void wire_reduce_ef(const at::Tensor& slots, int64_t n_slots, int64_t self_pos, 
   TORCH_CHECK(!dsts.empty(), "reduce_ef needs an output");
   float* e = ef_plane(residual, shard_elems);
   const WirePtrs to = ef_dsts(dsts, sb, local);
-  launch_wire_reduce_ef((int)codec, dcode(local), slots.data_ptr(), sb, (int)n_slots, (int)self_pos, local.data_ptr(),
-                        e, to, (int)dsts.size(), (size_t)shard_elems, false, fan_stream());
+  launch_wire_reduce_to((int)codec, dcode(local), slots.data_ptr(), sb, (int)n_slots, (int)self_pos, local.data_ptr(),
+                        to, (int)dsts.size(), (size_t)shard_elems, WireEncoder::feedback(e), false, fan_stream());
 }
 
-// The stochastic-rounding wire ops (bfp_format.h launch_wire_pack_sr / launch_wire_reduce_sr): destinations as above;
+// The stochastic-rounding wire ops (the same launchers with WireEncoder::stochastic): destinations as above;
 // `seed` is the request's 64-bit seed, `rank` the encoding rank and `base` the bucket index of the first element;
 // `peers` launches as the direct-P2P engine does (the P2P grid cap and release mode; the bits do not depend on it).
 SrKey sr_key_of(int64_t codec, const pybind11::int_& seed, int64_t rank, int stage, int64_t base, int64_t n) {
@@ -498,8 +499,8 @@ void wire_pack_sr(const at::Tensor& x, const std::vector<c10::optional<at::Tenso
   TORCH_CHECK(x.numel() == shard_elems * (int64_t)dsts.size(), "one destination per shard");
   const SrKey key = sr_key_of(codec, seed, rank, 0, base, x.numel());
   const WirePtrs to = ef_dsts(dsts, wire_shard_bytes((int)codec, (size_t)shard_elems), x);
-  launch_wire_pack_sr((int)codec, dcode(x), x.data_ptr(), to, (size_t)shard_elems, (int)dsts.size(), (int)self_shard,
-                      key, (size_t)base, peers, fan_stream());
+  launch_wire_pack_to((int)codec, dcode(x), x.data_ptr(), to, (size_t)shard_elems, (int)dsts.size(), (int)self_shard,
+                      WireEncoder::stochastic(key, (size_t)base), peers, fan_stream());
 }
 
 void wire_reduce_sr(const at::Tensor& slots, int64_t n_slots, int64_t self_pos, const at::Tensor& local,
@@ -518,8 +519,9 @@ void wire_reduce_sr(const at::Tensor& slots, int64_t n_slots, int64_t self_pos, 
   TORCH_CHECK(slots.device() == local.device(), "one device");
   TORCH_CHECK(!dsts.empty(), "reduce_sr needs an output");
   const WirePtrs to = ef_dsts(dsts, sb, local);
-  launch_wire_reduce_sr((int)codec, dcode(local), slots.data_ptr(), sb, (int)n_slots, (int)self_pos, local.data_ptr(),
-                        to, (int)dsts.size(), (size_t)shard_elems, key, (size_t)base, peers, fan_stream());
+  launch_wire_reduce_to((int)codec, dcode(local), slots.data_ptr(), sb, (int)n_slots, (int)self_pos, local.data_ptr(),
+                        to, (int)dsts.size(), (size_t)shard_elems, WireEncoder::stochastic(key, (size_t)base), peers,
+                        fan_stream());
 }
 
 // AdamW with 8-bit moment planes (bfp_format.h launch_wire_adamw_q): `mom_q` / `var_q` are the bucket's whole planes

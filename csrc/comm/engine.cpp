@@ -358,6 +358,16 @@ std::array<int64_t, 3> AllReduceEngine::prepack_shape(int64_t n) const {
   return {L.shard, world_ * L.chunks, local ? -1 : rank_};
 }
 
+// The request's encoder (bfp_format.h WireEncoder) at stage 0, sender `rank`'s pack of the whole bucket, or stage 1,
+// owner `rank`'s re-encode of its shard of `shard` elements: the stage's part of the residual plane, or the stochastic
+// key (sr_seed, rank, stage) with the stage's first element index in the padded bucket.
+static WireEncoder encoder_of(const EngineRequest& req, int rank, int stage, int64_t shard) {
+  const size_t first = stage ? (size_t)rank * (size_t)shard : 0;
+  if (req.residual) return WireEncoder::feedback(req.residual + first);
+  if (req.sr) return WireEncoder::stochastic(sr_key(req.sr_seed, rank, stage), first);
+  return {};
+}
+
 std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const EngineRequest& req) {
   const int N = world_, r = rank_, c = cfg_.codec, gdt = req.grad_dtype;
   const int64_t s = L.shard;
@@ -373,11 +383,10 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const Eng
   // there, the previous step's on-producer communication phase included; an on-producer request makes the producer
   // stream wait for everything on the comm stream so far. Inline engines run every request in the producer stream's
   // order. A caller that moves a bucket between producer streams orders them itself, as for the gradient buffer.
-  float* ef = req.residual;
   // Stochastic rounding: req.sr (submit(): an rne BFP codec, mesh, no prepacked input, one chunk, not sharded, no
-  // residual) swaps the same two encoders for their stateless stochastic forms; sender r draws from key
-  // (sr_seed, r, 0), owner r from key (sr_seed, r, 1), element indices are those of the padded bucket.
-  const bool sr = req.sr;
+  // residual) swaps the same two encoders for their stateless stochastic forms (encoder_of). With neither, the copying
+  // paths below keep the contiguous pack and the plain reduce.
+  const bool enc = req.residual != nullptr || req.sr;
   if (req.prepacked) {  // encode what the producer did not (bias gradient + padding)
     launch_wire_pack_range(c, gdt, req.grad, const_cast<uint8_t*>(req.prepacked), (size_t)s,
                            (size_t)req.prepacked_elems, (size_t)L.n_pad, st);
@@ -386,8 +395,8 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const Eng
     // the producer's encoding IS the (single-rank) result: no reduce pass
     if (req.prepacked) return {make_epilogue(req, req.prepacked, s, 1, 0, s)};
     uint8_t* S = epi_scratch("mesh_S" + std::to_string(sb), sb);
-    if (ef) launch_wire_reduce_ef(c, gdt, S, sb, 1, 0, g, ef, S, (size_t)s, st);  // one rank: the owner stage alone
-    else if (sr) launch_wire_reduce_sr(c, gdt, S, sb, 1, 0, g, S, (size_t)s, sr_key(req.sr_seed, 0, 1), 0, st);
+    if (enc)  // one rank: the owner stage alone
+      launch_wire_reduce_to(c, gdt, S, sb, 1, 0, g, WirePtrs{{S}}, 1, (size_t)s, encoder_of(req, 0, 1, s), false, st);
     else launch_wire_reduce(c, gdt, S, sb, 1, 0, g, S, nullptr, (size_t)s, st);
     return {make_epilogue(req, S, s, 1, 0, s)};
   }
@@ -398,15 +407,12 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const Eng
   if (!zero_copy(c, gdt) && !req.prepacked) {
     RoctxRange rr("fan/mesh/pack");
     uint8_t* Pb = scratch("mesh_P" + std::to_string(sb * N), sb * N, st);
-    if (ef) {
-      // (shard r's row is the plain encoding of g, as without feedback: the owner reduce reads g itself)
+    if (enc) {
+      // (shard r's row is the plain encoding of g, as without feedback or stochastic rounding: the owner reduce reads
+      // g itself)
       WirePtrs to{};
       for (int q = 0; q < N; ++q) to.p[q] = Pb + (size_t)q * sb;
-      launch_wire_pack_ef(c, gdt, g, ef, to, (size_t)s, N, r, false, st);
-    } else if (sr) {  // (shard r's row: plain rne, as above)
-      WirePtrs to{};
-      for (int q = 0; q < N; ++q) to.p[q] = Pb + (size_t)q * sb;
-      launch_wire_pack_sr(c, gdt, g, to, (size_t)s, N, r, sr_key(req.sr_seed, r, 0), 0, false, st);
+      launch_wire_pack_to(c, gdt, g, to, (size_t)s, N, r, encoder_of(req, r, 0, s), false, st);
     } else {
       launch_wire_pack(c, gdt, g, Pb, (size_t)s, N, st);
     }
@@ -450,10 +456,9 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh(const EngineLayout& L, const Eng
     RoctxRange rr("fan/mesh/reduce");
     // (1-rank group: the reduced shard is the gathered bucket, so the reduce writes the epilogue's buffer directly)
     const uint8_t* own = g + (size_t)r * s * esize(gdt);
-    if (ef) launch_wire_reduce_ef(c, gdt, R, sb, N, r, own, ef + (size_t)r * s, ident ? G : S, (size_t)s, st);
-    else if (sr)
-      launch_wire_reduce_sr(c, gdt, R, sb, N, r, own, ident ? G : S, (size_t)s, sr_key(req.sr_seed, r, 1),
-                            (size_t)r * s, st);
+    if (enc)
+      launch_wire_reduce_to(c, gdt, R, sb, N, r, own, WirePtrs{{ident ? G : S}}, 1, (size_t)s, encoder_of(req, r, 1, s),
+                            false, st);
     else launch_wire_reduce(c, gdt, R, sb, N, r, own, ident ? G : S, nullptr, (size_t)s, st);
   }
   mark(kTpReduced);
@@ -539,11 +544,8 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineL
       else if (raw) segs.push_back({g + (size_t)q * s * esize(gdt), to.p[q], sb});
     }
     if (req.prepacked || raw) d->move(segs, st);
-    // error feedback (ordering: run_mesh): to.p[r] is null, so shard r is neither encoded nor fed back here
-    else if (req.residual) launch_wire_pack_ef(c, gdt, g, req.residual, to, (size_t)s, N, r, true, st);
-    // stochastic rounding: to.p[r] is null as well, so shard r is not encoded here
-    else if (req.sr) launch_wire_pack_sr(c, gdt, g, to, (size_t)s, N, r, sr_key(req.sr_seed, r, 0), 0, true, st);
-    else launch_wire_pack_to(c, gdt, g, to, (size_t)s, N, st);
+    // to.p[r] is null, so shard r is not encoded here — nor fed back (error feedback; ordering: run_mesh)
+    else launch_wire_pack_to(c, gdt, g, to, (size_t)s, N, r, encoder_of(req, r, 0, s), true, st);
     tag_sent(r1, "mesh_pack", sb);
   }
   mark(kTpPacked);
@@ -590,14 +592,8 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineL
     WirePtrs out{};
     for (int q = 0; q < N; ++q) out.p[q] = d->dst(r2, q);  // q == r: this rank's own copy (its own slot)
     const uint8_t* own = g + (size_t)r * s * esize(gdt);
-    if (req.residual)
-      launch_wire_reduce_ef(c, gdt, d->src_base(r1), d->src_stride(), N, r, own, req.residual + (size_t)r * s, out, N,
-                            (size_t)s, true, st);
-    else if (req.sr)
-      launch_wire_reduce_sr(c, gdt, d->src_base(r1), d->src_stride(), N, r, own, out, N, (size_t)s,
-                            sr_key(req.sr_seed, r, 1), (size_t)r * s, true, st);
-    else
-      launch_wire_reduce_to(c, gdt, d->src_base(r1), d->src_stride(), N, r, own, out, N, (size_t)s, st);
+    launch_wire_reduce_to(c, gdt, d->src_base(r1), d->src_stride(), N, r, own, out, N, (size_t)s,
+                          encoder_of(req, r, 1, s), true, st);
     d->release(r1, st);
     tag_sent(r2, "mesh_reduce", sb);
   }
@@ -976,7 +972,7 @@ std::vector<EpiThunk> AllReduceEngine::run_ring_direct(P2PComm* d, const EngineL
             } else {
               WirePtrs w{};
               w.p[0] = to;
-              launch_wire_pack_to(c, gdt, local(rs, row.send_slice, s), w, (size_t)Sp, 1, st);
+              launch_wire_pack_to(c, gdt, local(rs, row.send_slice, s), w, (size_t)Sp, 1, -1, {}, true, st);
             }
           } else if (row.send_src == kSendReduce) {
             const Rx* part = nullptr;
@@ -987,7 +983,8 @@ std::vector<EpiThunk> AllReduceEngine::run_ring_direct(P2PComm* d, const EngineL
             w.p[0] = to;
             int nd = 1;
             if (row.owned >= 0) w.p[nd++] = gsub(rs, row.send_slice, s);  // this rank's fully reduced sub-slice
-            launch_wire_reduce_to(c, gdt, part->ptr, 0, 2, 1, local(rs, row.send_slice, s), w, nd, (size_t)Sp, st);
+            launch_wire_reduce_to(c, gdt, part->ptr, 0, 2, 1, local(rs, row.send_slice, s), w, nd, (size_t)Sp, {}, true,
+                                  st);
           } else {  // kSendForward: the full sub-slice received last round goes on downstream
             const Rx* full = nullptr;
             for (const Rx& x : prev[i])

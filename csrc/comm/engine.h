@@ -172,12 +172,12 @@ struct EngineRequest {
   const float* clip_words = nullptr;
   // error feedback (mesh, BFP codecs): the bucket's f32 residual plane on this rank, layout().n_pad elements, zeroed by
   // the caller before the bucket's first request. Non-null: the sender's pack and the owner's re-encode run their
-  // error-fed forms (bfp_format.h launch_wire_pack_ef / launch_wire_reduce_ef), which update it in place; the gathered
+  // error-fed forms (bfp_format.h WireEncoder::feedback), which update it in place; the gathered
   // wire keeps its format, so every epilogue runs unchanged. Refused with prepacked input, the ring schedule, chunked
   // layouts, the sharded update and more than kMaxPeers ranks.
   float* residual = nullptr;
   // stochastic rounding (mesh, bfp_rne / bfp4_rne): the sender's pack and the owner's re-encode run their stochastic
-  // forms (bfp_format.h launch_wire_pack_sr / launch_wire_reduce_sr) under the 64-bit request seed sr_seed; stateless,
+  // forms (bfp_format.h WireEncoder::stochastic) under the 64-bit request seed sr_seed; stateless,
   // the gathered wire keeps its format. Refused where `residual` is, and together with it.
   bool sr = false;
   uint64_t sr_seed = 0;
