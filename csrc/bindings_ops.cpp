@@ -668,6 +668,8 @@ void register_nn(pybind11::module_& m) {
   m.def("softmax_xent", &softmax_xent, "fused softmax + cross-entropy fwd/bwd");
   m.def("softmax_xent_slabs", &softmax_xent_slabs,
         "softmax + cross-entropy over the classifier GEMM's unreduced split-K slabs (+ bias; logits written)");
+  m.def("softmax_xent_slabs_supported", [](int64_t C) { return C <= INT32_MAX && softmax_xent_slabs_supported((int)C); },
+        "class counts softmax_xent_slabs folds (a split-K classifier GEMM of another width keeps its own slab reduce)");
   m.def("col_sum", &col_sum, "bias-gradient column sum");
   m.def("col_sum_workspace_floats", [](int64_t M, int64_t N) { return (int64_t)col_sum_workspace_floats((int)M, (int)N); });
   m.def("wire_pack_ef", &wire_pack_ef, "wire_pack with error feedback: encode x + residual per shard, keep the rest",

@@ -16,6 +16,7 @@ from __future__ import annotations
 import torch
 
 from .. import _ext
+from . import nn as _nn
 
 EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_RELU_MASK, EPI_WIRE = 0, 1, 2, 3, 4
 
@@ -69,7 +70,8 @@ def gemm(A, a_t: bool, B, b_t: bool, C, epilogue: int = EPI_NONE, bias=None, aux
     stream instead of launched — the next split-K wire reduce of the stream runs it in its first blocks, and
     :func:`flush_colsum` launches what is left in one grouped launch (the partials get a workspace of their own);
     ``colsum`` and the bias update are only complete after that.
-    ``defer_reduce`` (a dict; f32 ``EPI_BIAS`` output, bf16 operands): when the plan splits K, the slab reduce is not
+    ``defer_reduce`` (a dict; f32 ``EPI_BIAS`` output, bf16 operands): when the plan splits K and the consumer takes C's
+    width and leading dimension (``ops.nn.softmax_xent_slabs_supported``), the slab reduce is not
     launched and C is NOT written — the dict receives ``ws`` (the slabs, [sk][M][N] f32) and ``sk`` for a consumer
     that folds them (:func:`fpga_ai_nic_amd.ops.nn.softmax_xent_slabs`); it stays empty when C was written."""
     if wire is not None:
@@ -83,8 +85,6 @@ def gemm(A, a_t: bool, B, b_t: bool, C, epilogue: int = EPI_NONE, bias=None, aux
     if C.is_cuda:
         Cx = _ext.require()
         if colsum is not None and (A.dtype != torch.bfloat16 or b_t):
-            from . import nn as _nn
-
             gemm(A, a_t, B, b_t, C, epilogue, bias, aux, accumulate, split_k, tile)
             _nn.col_sum(B.t().contiguous() if b_t else B, colsum)  # (col_sum takes unit column stride)
             return C
@@ -327,9 +327,11 @@ def _bf16(Cx, A, a_t, B, b_t, C, epilogue, bias, aux, accumulate, split_k, tile,
         bm, bn, sk = plan  # launch exactly this tile (re-planning with an explicit split_k differs)
         need = _bf16_ws_floats(M, N, sk, bm, colsum)
         defer = bool(defer_colsum and upd is not None and colsum is not None and sk == 1)
-        # (not in the tuner's trial launches: their timing must include the reduce)
+        # (not in the tuner's trial launches: their timing must include the reduce; nor at a width or leading
+        # dimension the folding softmax does not take: the GEMM then reduces its slabs itself and writes C)
         dred = bool(final and defer_reduce is not None and sk > 1 and epilogue == EPI_BIAS and colsum is None
-                    and C.dtype == torch.float32 and not accumulate)
+                    and C.dtype == torch.float32 and not accumulate
+                    and _nn.softmax_xent_slabs_supported(N, C.stride(0)))
         if dred:
             ws = _slab_ws(C.device, need)
         else:

@@ -22,6 +22,13 @@ def softmax_xent(logits: torch.Tensor, labels: torch.Tensor, dlogits: torch.Tens
     dlogits.copy_((p * grad_scale).to(dlogits.dtype))
 
 
+def softmax_xent_slabs_supported(C: int, ld: int | None = None) -> bool:
+    """The class counts (and leading dimensions of the logits / dlogits) :func:`softmax_xent_slabs` folds, as
+    csrc/nn/nn_kernels.hip ``softmax_xent_slabs_supported`` and its launcher check them (tests/test_step_numerics_cpu.py
+    holds the two together). A split-K classifier GEMM of any other width keeps its own slab reduce (ops/gemm.py)."""
+    return C % 8 == 0 and C <= 2048 and (ld is None or ld % 8 == 0)
+
+
 def softmax_xent_slabs(slabs: dict, bias: torch.Tensor, logits: torch.Tensor, labels: torch.Tensor,
                        dlogits: torch.Tensor, loss_rows: torch.Tensor, grad_scale: float):
     """:func:`softmax_xent` over the classifier GEMM's unreduced split-K slabs (``slabs`` from ``ops.gemm.gemm``'s
@@ -32,7 +39,7 @@ def softmax_xent_slabs(slabs: dict, bias: torch.Tensor, logits: torch.Tensor, la
         _ext.require().softmax_xent_slabs(ws, sk, bias, logits, labels, dlogits, loss_rows, float(grad_scale))
         return
     M, C = logits.shape
-    if C % 8 or C > 2048 or sk < 1 or ws.numel() < sk * M * C:
+    if not softmax_xent_slabs_supported(C) or sk < 1 or ws.numel() < sk * M * C:
         raise ValueError(f"softmax_xent_slabs: C % 8 == 0, C <= 2048 and {sk} slabs of {M} x {C} needed")
     s = ws.reshape(-1)[: sk * M * C].view(sk, M, C).float()
     acc = s[0].clone()
