@@ -59,7 +59,7 @@ def measure(eng, dev, world, tokens=4096, layers=12, rounds=5, only="", last_on_
     scatter-add — are modelled as the encode of their buckets). Timed as compute only (GEMMs + encodes), comm only
     (the all-reduces of the encoded buckets) and both; medians over ``rounds`` (max over ranks). Also called by
     bench.py (``extra.config5``). ``optimizer='adamw'``: every bucket's update is AdamW (two moment planes per bucket,
-    the step count advancing per round) instead of plain SGD."""
+    the step count advancing per round) instead of plain SGD; ``'lion'``: Lion, one moment plane per bucket."""
     from fpga_ai_nic_amd import _ext
 
     C = _ext.require()
@@ -82,7 +82,9 @@ def measure(eng, dev, world, tokens=4096, layers=12, rounds=5, only="", last_on_
         prepacked_buckets += tgt is not None
         bufs.append((b, g, w, w.to(torch.bfloat16), L, tgt, _offsets(b)))
     adam = optimizer == "adamw"
-    moments = [(torch.zeros_like(w), torch.zeros_like(w)) if adam else None for _, _, w, *_ in bufs]
+    lion = optimizer == "lion"
+    moments = [(torch.zeros_like(w), torch.zeros_like(w)) if adam else (torch.zeros_like(w), None) if lion else None
+               for _, _, w, *_ in bufs]
     steps = [0] * len(bufs)
 
     def encode_range(g, tgt, lo, hi):
@@ -135,6 +137,9 @@ def measure(eng, dev, world, tokens=4096, layers=12, rounds=5, only="", last_on_
             return eng.allreduce_sgd(g, w, lp, moments[bi][0], n_valid=b.numel, lr=1e-4, grad_scale=1.0 / world,
                                      name=b.name, opt="adamw", var=moments[bi][1], weight_decay=1e-2, step=steps[bi],
                                      **kw)
+        if lion:
+            return eng.allreduce_sgd(g, w, lp, moments[bi][0], n_valid=b.numel, lr=1e-4, grad_scale=1.0 / world,
+                                     name=b.name, opt="lion", weight_decay=1e-2, **kw)
         return eng.allreduce_sgd(g, w, lp, n_valid=b.numel, lr=1e-4, grad_scale=1.0 / world, name=b.name, **kw)
 
     enq = {}
@@ -192,7 +197,7 @@ def main():
     ap.add_argument("--engine", default="native", choices=["python", "native"])
     ap.add_argument("--forced", action="store_true",
                     help="world 1 through the multi-rank path (1-rank RCCL group, sharded update: bench.py extra.config5)")
-    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw"],
+    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw", "lion"],
                     help="the update fused into every bucket's all-reduce")
     ap.add_argument("--only", default="", choices=["", "compute", "comm", "overlap"],
                     help="profiling: run only rounds of this kind (one kernel trace per kind, for tools/overlap_report.py)")

@@ -88,6 +88,31 @@ __device__ __forceinline__ void adamw_update(const AdamWParams& p, float g, floa
   w = fmaf(-p.step_size, m / d, p.weight_decay != 0.0f ? w * p.decay : w);
 }
 
+// Lion (Chen et al. 2023: sign of the interpolated momentum, decoupled decay) of the update kernels. One moment plane,
+// the launchers' `mom`, so it reads and writes exactly SGD-momentum's planes; no divide, no square root, no step
+// counter. The scalars are computed on the host in float64 and rounded once to f32 (ops/bfp_oracle.py lion_scalars):
+// omb1 = 1 - beta1, omb2 = 1 - beta2, decay = 1 - lr * wd.
+struct LionParams {
+  float grad_scale;
+  float beta1, omb1;
+  float beta2, omb2;
+  float lr;
+  float weight_decay;  // only tested against 0: the decay itself is `decay`
+  float decay;
+};
+
+// One element's Lion step, all f32, in the order bfp_oracle.lion emulates (change both together):
+//   g = g * grad_scale; c = fma(beta1, m, omb1 * g); s = c > 0 ? 1 : c < 0 ? -1 : c
+//   w' = fma(-lr, s, wd != 0 ? w * decay : w); m' = fma(beta2, m, omb2 * g)
+// c == +-0 leaves the weight on w * decay (and -lr * +-0 adds nothing); a NaN c propagates into w'.
+__device__ __forceinline__ void lion_update(const LionParams& p, float g, float& w, float& m) {
+  g = g * p.grad_scale;
+  const float c = fmaf(p.beta1, m, p.omb1 * g);
+  const float s = c > 0.0f ? 1.0f : c < 0.0f ? -1.0f : c;
+  w = fmaf(-p.lr, s, p.weight_decay != 0.0f ? w * p.decay : w);
+  m = fmaf(p.beta2, m, p.omb2 * g);
+}
+
 // AdamW with a layer-wise trust ratio (LAMB), the two-pass update of the all-reduce epilogues. The host scalars are
 // ops/bfp_oracle.py lamb_scalars (float64, rounded once to f32): AdamW's beta1, omb1, beta2, omb2, rsbc2, eps, plus
 // rbc1 = 1 / (1 - beta1^t), the decay coefficient and lr themselves (the step size is not folded into a scalar: it is
@@ -725,6 +750,10 @@ void launch_wire_sgd(int codec, const void* wire, size_t n_s, int n_shards, int 
 void launch_wire_adamw(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
                        float* master, bf16_t* lp, float* mom, AdamWParams p, size_t n_valid, hipStream_t stream,
                        size_t shard_stride = 0, const float* clip = nullptr);
+// launch_wire_sgd with the Lion step: `mom` is its one moment plane, required.
+void launch_wire_lion(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
+                      float* master, bf16_t* lp, float* mom, LionParams p, size_t n_valid, hipStream_t stream,
+                      size_t shard_stride = 0, const float* clip = nullptr);
 // Global-norm gradient clipping of a clip group (the update requests of one optimizer step), three kinds of launch
 // on one stream. The update launchers above and launch_wire_lamb_moments take `clip`, the group's four f32 device
 // words {coef, f32(total), f32(max_norm), nonfinite ? 1 : 0}: non-null, the kernel uses grad_scale * clip[0] (one f32
@@ -823,6 +852,12 @@ void launch_wire_reduce_adamw(int codec, int local_dtype, const void* slots, siz
                               int self_pos, const void* local, float* master, float* mom, AdamWParams p,
                               size_t n_valid, const WirePtrs& dst, int n_dst, size_t n_s, bool peers,
                               hipStream_t stream);
+// launch_wire_reduce_sgd with the Lion step (`mom`: this shard's moment plane, required): bit-identical to
+// wire_reduce (re-encode) + wire_lion.
+void launch_wire_reduce_lion(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots,
+                             int self_pos, const void* local, float* master, float* mom, LionParams p,
+                             size_t n_valid, const WirePtrs& dst, int n_dst, size_t n_s, bool peers,
+                             hipStream_t stream);
 // AdamW with both moments in 8-bit block floating point (moment_codec "bfp8"; ops/bfp_oracle.py adamw_q defines the
 // bits). mom_q / var_q: the bucket's WHOLE planes, each [int8 mant[plane_elems]][u8 exp[plane_elems/16]] (the kBfpRne
 // shard layout of one shard of plane_elems elements, 16-B aligned, plane_elems % 256 == 0 and below 2^32), the first

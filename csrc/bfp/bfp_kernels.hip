@@ -311,14 +311,17 @@ __global__ void __launch_bounds__(kBlock)
 
 // The merged reduce-and-update of the owner's shard: the slots' sum through the codec's round trip, then the update
 // per value (the same operations as wire_reduce's re-encode + wire_sgd_kernel, so the same bits), the new weights in
-// bf16 to every destination. P: SgdParams, or AdamWParams (HAS_MOM: mom is the first moment, p.var the second).
+// bf16 to every destination. P: SgdParams, AdamWParams (HAS_MOM: mom is the first moment, p.var the second), or
+// LionParams (HAS_MOM: mom is its one moment plane).
 template <typename L, typename TL, bool HAS_MOM, typename P = SgdParams>
 __global__ void __launch_bounds__(kBlock)
     wire_reduce_sgd_kernel(const uint8_t* __restrict__ slots, size_t slot_stride, int n_slots, int self_pos,
                            const TL* __restrict__ local, float* __restrict__ master, float* __restrict__ mom,
                            P p, size_t n_valid, WirePtrs dst, int n_dst, size_t n_s, int rel) {
   constexpr bool kAdam = std::is_same<P, AdamWParams>::value;
+  constexpr bool kLion = std::is_same<P, LionParams>::value;
   static_assert(!kAdam || HAS_MOM, "AdamW needs both moment planes");
+  static_assert(!kLion || HAS_MOM, "Lion needs its moment plane");
   const size_t tasks = n_s / L::kVals;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < tasks; t += stride) {
@@ -336,6 +339,10 @@ __global__ void __launch_bounds__(kBlock)
       for (int j = 0; j < L::kVals; ++j)
         if (le + j < n_valid) adamw_update(p, acc[j], w[j], m[j], v2[j]);
       if (le < n_valid) L::store_f32(p.var, le, v2);
+    } else if constexpr (kLion) {
+#pragma unroll
+      for (int j = 0; j < L::kVals; ++j)
+        if (le + j < n_valid) lion_update(p, acc[j], w[j], m[j]);
     } else {
 #pragma unroll
       for (int j = 0; j < L::kVals; ++j)
@@ -377,7 +384,9 @@ __global__ void __launch_bounds__(kBlock)
                     float* __restrict__ master, bf16_t* __restrict__ lp, float* __restrict__ mom, P p,
                     size_t n_valid, size_t sb, const float* __restrict__ clip) {
   constexpr bool kAdam = std::is_same<P, AdamWParams>::value;
+  constexpr bool kLion = std::is_same<P, LionParams>::value;
   static_assert(!kAdam || HAS_MOM, "AdamW needs both moment planes");
+  static_assert(!kLion || HAS_MOM, "Lion needs its moment plane");
   if constexpr (CLIP) p.grad_scale = p.grad_scale * clip[0];
   // 8 elements per lane here (a read-only wire: the 16-per-lane store layout buys nothing, and the smaller
   // register footprint streams master / lp faster: 33.5 vs 42.5 us on a 16.8 M bucket in the flagship step)
@@ -407,6 +416,9 @@ __global__ void __launch_bounds__(kBlock)
         } else {
           for (int j = 0; j < 8 && e + j < n_valid; ++j) p.var[e + j] = v2[j];
         }
+      } else if constexpr (kLion) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) lion_update(p, g[j], w[j], m[j]);
       } else {
 #pragma unroll
         for (int j = 0; j < 8; ++j) sgd_update(p, g[j], w[j], m[j], HAS_MOM);
@@ -876,6 +888,29 @@ void launch_wire_adamw(int codec, const void* wire, size_t n_s, int n_shards, in
   FAN_HIP_CHECK(hipGetLastError());
 }
 
+void launch_wire_lion(int codec, const void* wire, size_t n_s, int n_shards, int skip_shard, int skip_period,
+                      float* master, bf16_t* lp, float* mom, LionParams p, size_t n_valid, hipStream_t stream,
+                      size_t shard_stride, const float* clip) {
+  FAN_CHECK(master != nullptr && mom != nullptr, "wire_lion: master and the moment plane");
+  if (skip_period < 1) skip_period = 1 << 30;
+  check_ns(n_s);
+  if (n_s == 0 || n_shards == 0) return;
+  const int grid = stream_grid(n_s / 8, kBlock, wire_max_blocks());
+  const uint8_t* w = (const uint8_t*)wire;
+#define FAN_LION(LP, CLIP)                                                                                      \
+  hipLaunchKernelGGL((wire_sgd_kernel<C, LP, true, LionParams, CLIP>), grid, kBlock, 0, stream, w, n_s, n_shards, \
+                     skip_shard, skip_period, master, lp, mom, p, n_valid, sb, clip)
+  FAN_CODEC_SWITCH(codec, {
+    const size_t sb = shard_stride ? shard_stride : wire_shard_bytes(C, n_s);
+    if (lp && clip) FAN_LION(true, true);
+    else if (lp) FAN_LION(true, false);
+    else if (clip) FAN_LION(false, true);
+    else FAN_LION(false, false);
+  });
+#undef FAN_LION
+  FAN_HIP_CHECK(hipGetLastError());
+}
+
 static std::atomic<int>& moment_grid_flag() {
   static std::atomic<int> g{0};
   return g;
@@ -1121,7 +1156,8 @@ template <typename P>
 static void launch_reduce_update(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots,
                                  int self_pos, const void* local, float* master, float* mom, P p, size_t n_valid,
                                  const WirePtrs& dst, int n_dst, size_t n_s, bool peers, hipStream_t stream) {
-  constexpr bool kAdam = std::is_same<P, AdamWParams>::value;  // AdamW: both moment planes, always
+  // AdamW: both moment planes, always; Lion: its one plane, always
+  constexpr bool kMomAlways = std::is_same<P, AdamWParams>::value || std::is_same<P, LionParams>::value;
   check_ns(n_s);
   FAN_CHECK(n_dst <= kMaxPeers && local != nullptr && master != nullptr,
             "reduce_sgd: local operand, master shard and at most 16 destinations");
@@ -1134,11 +1170,11 @@ static void launch_reduce_update(int codec, int local_dtype, const void* slots, 
   FAN_CODEC_SWITCH(codec, with_lanes<C>(n_slots, n_s, pl.cap, [&](auto lanes, int grid) {
     using L = decltype(lanes);
     if (local_dtype == kF32) {
-      if (kAdam || mom) FAN_RSGD(float, true);
-      else if constexpr (!kAdam) FAN_RSGD(float, false);
+      if (kMomAlways || mom) FAN_RSGD(float, true);
+      else if constexpr (!kMomAlways) FAN_RSGD(float, false);
     } else {
-      if (kAdam || mom) FAN_RSGD(bf16_t, true);
-      else if constexpr (!kAdam) FAN_RSGD(bf16_t, false);
+      if (kMomAlways || mom) FAN_RSGD(bf16_t, true);
+      else if constexpr (!kMomAlways) FAN_RSGD(bf16_t, false);
     }
   }));
 #undef FAN_RSGD
@@ -1157,6 +1193,15 @@ void launch_wire_reduce_adamw(int codec, int local_dtype, const void* slots, siz
                               size_t n_valid, const WirePtrs& dst, int n_dst, size_t n_s, bool peers,
                               hipStream_t stream) {
   FAN_CHECK(mom != nullptr && p.var != nullptr, "reduce_adamw: both moment shards");
+  launch_reduce_update(codec, local_dtype, slots, slot_stride, n_slots, self_pos, local, master, mom, p, n_valid, dst,
+                       n_dst, n_s, peers, stream);
+}
+
+void launch_wire_reduce_lion(int codec, int local_dtype, const void* slots, size_t slot_stride, int n_slots,
+                             int self_pos, const void* local, float* master, float* mom, LionParams p,
+                             size_t n_valid, const WirePtrs& dst, int n_dst, size_t n_s, bool peers,
+                             hipStream_t stream) {
+  FAN_CHECK(mom != nullptr, "reduce_lion: the moment shard");
   launch_reduce_update(codec, local_dtype, slots, slot_stride, n_slots, self_pos, local, master, mom, p, n_valid, dst,
                        n_dst, n_s, peers, stream);
 }

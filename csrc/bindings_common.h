@@ -30,6 +30,13 @@ inline fan::AdamWParams fan_adamw_params(const std::vector<double>& s, double gr
   p.var = var.data_ptr<float>();
   return p;
 }
+// LionParams from bfp_oracle.lion_scalars (already rounded to f32, in its order: beta1, omb1, beta2, omb2, lr, decay,
+// wd).
+inline fan::LionParams fan_lion_params(const std::vector<double>& s, double grad_scale) {
+  TORCH_CHECK(s.size() == 7, "lion: 7 scalars (beta1, omb1, beta2, omb2, lr, decay, wd)");
+  return fan::LionParams{(float)grad_scale, (float)s[0], (float)s[1], (float)s[2], (float)s[3], (float)s[4],
+                         (float)s[6], (float)s[5]};
+}
 // One 8-bit moment plane of a padded bucket of n_pad elements (bfp_format.h launch_wire_adamw_q): contiguous uint8,
 // exactly n_pad * 17 / 16 bytes, 16-byte aligned (a sliced tensor may not be), on `ref`'s device.
 inline uint8_t* fan_moment_plane(const at::Tensor& t, int64_t n_pad, const at::Tensor& ref) {

@@ -253,7 +253,7 @@ void register_engine(pybind11::module_& m) {
               c10::optional<std::vector<double>> adamw, c10::optional<std::vector<double>> lamb, int64_t n_adapt,
               c10::optional<at::Tensor> trust_out, c10::optional<at::Tensor> clip,
               c10::optional<at::Tensor> residual, bool sr, uint64_t sr_seed, c10::optional<at::Tensor> mom_q,
-              c10::optional<at::Tensor> var_q, uint64_t moment_seed) {
+              c10::optional<at::Tensor> var_q, uint64_t moment_seed, c10::optional<std::vector<double>> lion) {
              FAN_T_CUDA_CONTIG(grad);
              TORCH_CHECK(grad.scalar_type() == at::kFloat || grad.scalar_type() == at::kBFloat16,
                          "gradients must be f32 or bf16");
@@ -303,9 +303,22 @@ void register_engine(pybind11::module_& m) {
                req.prepacked = prepacked->data_ptr<uint8_t>();
              }
              req.upd.sgd = SgdParams{(float)lr, (float)grad_scale, (float)wd, (float)momentum, nesterov ? 1 : 0};
-             TORCH_CHECK(opt == kOptSgd || opt == kOptAdamW, "opt: 0 (SGD) or 1 (AdamW)");
+             TORCH_CHECK(opt == kOptSgd || opt == kOptAdamW || opt == kOptLion, "opt: 0 (SGD), 1 (AdamW) or 2 (Lion)");
+             TORCH_CHECK(opt != kOptLion || !(mom_q && mom_q->defined()),
+                         "moment_codec bfp8: AdamW only (Lion's one moment plane stays f32)");
              TORCH_CHECK(opt == kOptAdamW || !(mom_q && mom_q->defined()),
                          "moment_codec bfp8: AdamW only (SGD keeps no second moment)");
+             if (opt == kOptLion) {
+               TORCH_CHECK(lion.has_value(), "Lion needs its scalars");
+               TORCH_CHECK(!lamb.has_value(), "trust ratio: a flag of AdamW update requests, not of Lion");
+               TORCH_CHECK(!(var && var->defined()), "Lion keeps one moment plane (mom): no second-moment plane (var)");
+               TORCH_CHECK(!update || req.mom != nullptr, "Lion needs its moment plane (mom)");
+               // the kernels read the planes a whole lane (and, in the owner reduce, a whole shard) at a time
+               TORCH_CHECK(!update || (mom->numel() >= L.n_pad && master.numel() >= L.n_pad),
+                           "Lion: master and mom must be padded to the layout's ", L.n_pad, " elements");
+               req.upd.kind = kOptLion;
+               req.upd.lion = fan_lion_params(*lion, grad_scale);
+             }
              if (opt == kOptAdamW) {
                TORCH_CHECK(adamw.has_value(), "AdamW needs its scalars");
                const bool mq = mom_q && mom_q->defined();
@@ -373,7 +386,7 @@ void register_engine(pybind11::module_& m) {
            py::arg("adamw") = py::none(), py::arg("lamb") = py::none(), py::arg("n_adapt") = -1,
            py::arg("trust_out") = py::none(), py::arg("clip") = py::none(), py::arg("residual") = py::none(),
            py::arg("sr") = false, py::arg("sr_seed") = 0, py::arg("mom_q") = py::none(),
-           py::arg("var_q") = py::none(), py::arg("moment_seed") = 0,
+           py::arg("var_q") = py::none(), py::arg("moment_seed") = 0, py::arg("lion") = py::none(),
            py::call_guard<py::gil_scoped_release>())
       .def("prepack_shape", [](AllReduceEngine& e, int64_t n) {
         const auto s = e.prepack_shape(n);

@@ -581,6 +581,47 @@ void wire_adamw_q(const at::Tensor& wire, int64_t shard_elems, int64_t n_shards,
                       fan_stream(), (size_t)shard_stride, cw);
 }
 
+// Lion (bfp_format.h launch_wire_lion): `mom` is the one moment plane; master and mom hold n_valid rounded up to the
+// kernel's 8-value lane trip.
+void wire_lion(const at::Tensor& wire, int64_t shard_elems, int64_t n_shards, int64_t skip_shard, int64_t skip_period,
+               at::Tensor& master, const c10::optional<at::Tensor>& lp, at::Tensor& mom,
+               const std::vector<double>& scalars, double grad_scale, int64_t n_valid, int64_t codec,
+               int64_t shard_stride, const c10::optional<at::Tensor>& clip) {
+  FAN_T_CUDA_CONTIG(wire);
+  FAN_T_CUDA_CONTIG(master);
+  FAN_T_CUDA_CONTIG(mom);
+  TORCH_CHECK(shard_elems > 0 && shard_elems % 256 == 0 && n_shards > 0, "shard_elems: a positive multiple of 256");
+  TORCH_CHECK(n_valid >= 0 && n_valid <= shard_elems * n_shards, "n_valid beyond the wire region");
+  const int64_t need_elems = (n_valid + 7) / 8 * 8;
+  TORCH_CHECK(master.scalar_type() == at::kFloat && mom.scalar_type() == at::kFloat,
+              "master weights and the moment plane must be float32");
+  TORCH_CHECK(master.numel() >= need_elems && mom.numel() >= need_elems,
+              "master and mom must hold n_valid rounded up to 8 elements");
+  TORCH_CHECK(wire.device() == master.device() && mom.device() == master.device(), "one device");
+  const size_t sb = wire_shard_bytes((int)codec, shard_elems);
+  TORCH_CHECK(shard_stride == 0 || (size_t)shard_stride >= sb, "shard_stride below the packed shard size");
+  TORCH_CHECK(shard_stride % 16 == 0, "shard_stride must keep 16-byte alignment");
+  const size_t need = shard_stride ? (size_t)shard_stride * (n_shards - 1) + sb : sb * n_shards;
+  TORCH_CHECK((size_t)wire.numel() * wire.element_size() >= need, "wire buffer too small");
+  bf16_t* lpp = nullptr;
+  if (lp) {
+    FAN_T_CUDA_CONTIG((*lp));
+    TORCH_CHECK(lp->scalar_type() == at::kBFloat16 && lp->numel() >= n_valid && lp->device() == master.device(),
+                "bad lp weights");
+    lpp = reinterpret_cast<bf16_t*>(lp->data_ptr());
+  }
+  const float* cw = nullptr;
+  if (clip) {
+    FAN_T_CUDA_CONTIG((*clip));
+    TORCH_CHECK(clip->scalar_type() == at::kFloat && clip->numel() >= 4, "clip: f32[4]");
+    cw = clip->data_ptr<float>();
+  }
+  const LionParams p = fan_lion_params(scalars, grad_scale);
+  launch_wire_lion((int)codec, wire.data_ptr(), (size_t)shard_elems, (int)n_shards, (int)skip_shard, (int)skip_period,
+                   master.data_ptr<float>(), lpp, mom.data_ptr<float>(), p, (size_t)n_valid, fan_stream(),
+                   (size_t)shard_stride, cw);
+}
+
 }  // namespace
 
 void register_gemm(pybind11::module_& m) {
@@ -692,6 +733,11 @@ void register_nn(pybind11::module_& m) {
         pybind11::arg("var_q"), pybind11::arg("scalars"), pybind11::arg("grad_scale"), pybind11::arg("weight_decay"),
         pybind11::arg("seed"), pybind11::arg("n_valid"), pybind11::arg("codec"), pybind11::arg("shard_stride") = 0,
         pybind11::arg("clip") = pybind11::none(), pybind11::arg("elem_base") = 0);
+  m.def("wire_lion", &wire_lion, "fused decode + Lion weight update in place (one f32 moment plane)",
+        pybind11::arg("wire"), pybind11::arg("shard_elems"), pybind11::arg("n_shards"), pybind11::arg("skip_shard"),
+        pybind11::arg("skip_period"), pybind11::arg("master"), pybind11::arg("lp"), pybind11::arg("mom"),
+        pybind11::arg("scalars"), pybind11::arg("grad_scale"), pybind11::arg("n_valid"), pybind11::arg("codec"),
+        pybind11::arg("shard_stride") = 0, pybind11::arg("clip") = pybind11::none());
 }
 
 void register_planner(pybind11::module_& m) {

@@ -256,6 +256,9 @@ static void update_at(const EngineRequest& req, int codec, const void* wire, siz
     a.var += off;
     launch_wire_adamw(codec, wire, n_s, n_shards, skip_shard, skip_period, req.master + off, lp, req.mom + off, a, nv,
                       st, shard_stride, req.clip_words);
+  } else if (req.upd.kind == kOptLion) {
+    launch_wire_lion(codec, wire, n_s, n_shards, skip_shard, skip_period, req.master + off, lp, req.mom + off,
+                     req.upd.lion, nv, st, shard_stride, req.clip_words);
   } else {
     launch_wire_sgd(codec, wire, n_s, n_shards, skip_shard, skip_period, req.master + off, lp,
                     req.mom ? req.mom + off : nullptr, req.upd.sgd, nv, st, shard_stride, req.clip_words);
@@ -271,6 +274,9 @@ static void reduce_update_at(const EngineRequest& req, int codec, const void* sl
     a.var += off;
     launch_wire_reduce_adamw(codec, req.grad_dtype, slots, slot_stride, n_slots, self_pos, local, req.master + off,
                              req.mom + off, a, nv, dst, n_dst, n_s, peers, st);
+  } else if (req.upd.kind == kOptLion) {
+    launch_wire_reduce_lion(codec, req.grad_dtype, slots, slot_stride, n_slots, self_pos, local, req.master + off,
+                            req.mom + off, req.upd.lion, nv, dst, n_dst, n_s, peers, st);
   } else {
     launch_wire_reduce_sgd(codec, req.grad_dtype, slots, slot_stride, n_slots, self_pos, local, req.master + off,
                            req.mom ? req.mom + off : nullptr, req.upd.sgd, nv, dst, n_dst, n_s, peers, st);
@@ -1103,6 +1109,15 @@ int AllReduceEngine::submit(const EngineRequest& req, hipStream_t producer) {
   FAN_CHECK(req.upd.kind != kOptAdamW || !req.update || req.moment_q ||
                 (req.mom != nullptr && req.upd.adamw.var != nullptr),
             "AdamW needs both moment planes");
+  FAN_CHECK(req.upd.kind == kOptSgd || req.upd.kind == kOptAdamW || req.upd.kind == kOptLion,
+            "unknown optimizer kind (0 SGD, 1 AdamW, 2 Lion)");
+  if (req.upd.kind == kOptLion) {
+    // One f32 moment plane, where SGD's momentum travels (refused before the request takes a slot).
+    FAN_CHECK(!req.update || req.mom != nullptr, "Lion needs its moment plane (mom)");
+    FAN_CHECK(req.upd.adamw.var == nullptr, "Lion keeps one moment plane: no second-moment plane (var)");
+    FAN_CHECK(!req.upd.trust, "trust ratio: a flag of AdamW update requests, not of Lion");
+    FAN_CHECK(!req.moment_q, "moment_codec bfp8: AdamW update requests only (Lion's one moment plane stays f32)");
+  }
   if (req.moment_q) {
     // The 8-bit state is read and written by update_at's one launch (refused before the request takes a slot).
     FAN_CHECK(req.upd.kind == kOptAdamW && req.update,

@@ -128,16 +128,19 @@ enum VerifySite : uint32_t {
   kSiteMeshWeightGather = 7,  // the sharded update's bf16 weight all-gather (run_mesh)
 };
 
-// The weight update of one request: SGD (the default), or AdamW with its own scalars and second-moment plane
-// (adamw.var; the first moment travels where SGD's momentum does). One value through every schedule, so a site that
+// The weight update of one request: SGD (the default), AdamW with its own scalars and second-moment plane
+// (adamw.var; the first moment travels where SGD's momentum does), or Lion with its own scalars (its one moment plane
+// is `mom`; no second plane, no trust ratio, no 8-bit state: submit() refuses them). One value through every schedule,
+// so a site that
 // offsets the planes offsets adamw.var with them (update_at in engine.cpp).
 // trust (kOptAdamW only): the layer-wise trust ratio (LAMB) — the update is then the two-pass epilogue of
 // bfp_format.h (launch_wire_lamb_*) with `lamb`'s scalars, and adamw.var still names the second-moment plane.
-enum OptKind : int { kOptSgd = 0, kOptAdamW = 1 };
+enum OptKind : int { kOptSgd = 0, kOptAdamW = 1, kOptLion = 2 };
 struct UpdateParams {
   int kind = kOptSgd;
   SgdParams sgd{};
   AdamWParams adamw{};
+  LionParams lion{};
   bool trust = false;
   LambParams lamb{};
 };

@@ -102,8 +102,8 @@ def run(argv=None, out=sys.stdout):
         bias, relu = True, "hidden"
     else:  # reference fuse_type mapping (sw:479-489)
         bias, relu = {1: (True, "none"), 2: (False, "all"), 3: (True, "all")}.get(a.fuse_type, (False, "none"))
-    model = MLP(sizes, dtype=dtype, device=device, pad_fn=pad_fn, seed=cfg.seed, momentum=cfg.momentum > 0,
-                bias=bias, relu=relu, adam=cfg.optimizer == "adamw",
+    model = MLP(sizes, dtype=dtype, device=device, pad_fn=pad_fn, seed=cfg.seed,
+                momentum=cfg.momentum > 0 or cfg.optimizer == "lion", bias=bias, relu=relu, adam=cfg.optimizer == "adamw",
                 moment_codec=cfg.moment_codec if cfg.optimizer == "adamw" else "f32")
     if world > 1:  # reference C3/C4: broadcast weights + bias from rank 0
         for l in model.layers:
@@ -111,14 +111,14 @@ def run(argv=None, out=sys.stdout):
         model.sync_lp()
     start_iter, opt_step, sr_step = 0, 0, 0
     if cfg.resume:
-        info = checkpoint.load(cfg.resume, model)
+        info = checkpoint.load(cfg.resume, model, optimizer=cfg.optimizer)
         start_iter = int(info.get("iteration", 0))
         if info.get("optimizer", "sgd") == cfg.optimizer:  # the update count belongs to the moments it was saved with
             opt_step = int(info.get("opt_step", 0))
         sr_step = int(info.get("sr_step", 0))  # (saved by a --stochastic-rounding run only)
     trainer = DataParallelTrainer(model, engine, lr=cfg.lr, weight_decay=cfg.weight_decay, momentum=cfg.momentum,
                                   loss_scale=cfg.loss_scale, profile=cfg.profile, optimizer=cfg.optimizer,
-                                  betas=(cfg.beta1, cfg.beta2), eps=cfg.eps, trust_ratio=cfg.trust_ratio,
+                                  betas=cfg.betas(), eps=cfg.eps, trust_ratio=cfg.trust_ratio,
                                   max_grad_norm=cfg.clip_grad_norm if cfg.clip_grad_norm > 0 else None,
                                   error_feedback=cfg.error_feedback,
                                   error_feedback_codec=f"bfp_{cfg.rounding}",

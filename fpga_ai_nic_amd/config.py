@@ -39,15 +39,15 @@ class TrainConfig:
     lr: float = 0.1
     momentum: float = 0.0
     weight_decay: float = 0.0
-    optimizer: str = "sgd"         # sgd | adamw
+    optimizer: str = "sgd"         # sgd | adamw | lion
     trust_ratio: bool = False      # adamw: layer-wise trust ratio (LAMB)
     clip_grad_norm: float = 0.0    # > 0: clip the reduced gradient of all layers to this 2-norm (0: off)
     error_feedback: bool = False   # BFP mesh: each encoder keeps what it drops and adds it to the next step's input
     stochastic_rounding: bool = False  # rne BFP mesh: each encoder rounds up with probability = the dropped fraction
     sr_seed: int = 0               # the run's base seed of the stochastic rounding, an int in [0, 2^64)
     moment_codec: str = "f32"      # adamw: f32 | bfp8 (both moments in 8-bit block floating point, 2.125 B / parameter)
-    beta1: float = 0.9
-    beta2: float = 0.999
+    beta1: float | None = None     # None: the optimizer's default (adamw 0.9, lion 0.9)
+    beta2: float | None = None     # None: the optimizer's default (adamw 0.999, lion 0.99)
     eps: float = 1e-8
     loss_scale: float = 1.0
     warmup: int = 2
@@ -61,6 +61,11 @@ class TrainConfig:
 
     def to_dict(self):
         return dataclasses.asdict(self)
+
+    def betas(self):
+        """(beta1, beta2) with the optimizer's defaults filled in: AdamW's (0.9, 0.999), Lion's (0.9, 0.99)."""
+        d1, d2 = (0.9, 0.99) if self.optimizer == "lion" else (0.9, 0.999)
+        return (d1 if self.beta1 is None else self.beta1, d2 if self.beta2 is None else self.beta2)
 
 
 def add_named_flags(ap: argparse.ArgumentParser):
@@ -80,8 +85,10 @@ def add_named_flags(ap: argparse.ArgumentParser):
     ap.add_argument("--lr", type=float, default=d.lr)
     ap.add_argument("--momentum", type=float, default=d.momentum)
     ap.add_argument("--weight-decay", type=float, default=d.weight_decay)
-    ap.add_argument("--optimizer", default=d.optimizer, choices=["sgd", "adamw"],
-                    help="weight update fused into the all-reduce epilogue")
+    ap.add_argument("--optimizer", default=d.optimizer, choices=["sgd", "adamw", "lion"],
+                    help="weight update fused into the all-reduce epilogue; lion: sign of the interpolated momentum "
+                         "with decoupled decay, one f32 moment plane (SGD-momentum's bytes and state); not with "
+                         "--momentum, --trust-ratio or --moment-codec bfp8")
     ap.add_argument("--trust-ratio", action="store_true",
                     help="AdamW: scale each layer's step by ||w|| / ||update|| (LAMB; two-pass epilogue)")
     ap.add_argument("--clip-grad-norm", type=float, default=d.clip_grad_norm,
@@ -103,8 +110,10 @@ def add_named_flags(ap: argparse.ArgumentParser):
                     help="--optimizer adamw: keep both moments in 8-bit block floating point (2.125 B per parameter "
                          "instead of 8; stored with stochastic rounding under --sr-seed, the second as sqrt(v)); not "
                          "with --trust-ratio. Checkpointed with the codec's name: --resume needs the same codec")
-    ap.add_argument("--beta1", type=float, default=d.beta1, help="AdamW first-moment decay")
-    ap.add_argument("--beta2", type=float, default=d.beta2, help="AdamW second-moment decay")
+    ap.add_argument("--beta1", type=float, default=d.beta1,
+                    help="AdamW first-moment decay / Lion's update interpolation (default 0.9)")
+    ap.add_argument("--beta2", type=float, default=d.beta2,
+                    help="AdamW second-moment decay (default 0.999) / Lion's momentum decay (default 0.99)")
     ap.add_argument("--eps", type=float, default=d.eps, help="AdamW denominator term")
     ap.add_argument("--loss-scale", type=float, default=d.loss_scale)
     ap.add_argument("--warmup", type=int, default=d.warmup)

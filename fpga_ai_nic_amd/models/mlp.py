@@ -67,7 +67,8 @@ class MLP:
     def __init__(self, sizes, *, dtype=torch.bfloat16, device="cpu", pad_fn=None, seed: int = 1,
                  momentum: bool = False, init_scale: float | None = None, bias: bool = True,
                  relu: str = "hidden", adam: bool = False, moment_codec: str = "f32"):
-        """``adam``: allocate both AdamW moment planes per layer (``mom`` the first, ``var`` the second);
+        """``momentum``: allocate the f32 momentum plane ``mom`` per layer (SGD's momentum, or Lion's one moment);
+        ``adam``: allocate both AdamW moment planes per layer (``mom`` the first, ``var`` the second);
         ``moment_codec="bfp8"``: as 8-bit planes (uint8, ``n_pad * 17 / 16`` bytes each, ``var`` holding sqrt(v):
         ``ops/bfp_oracle.py`` adamw_q), zeroed — the zero state.
         ``bias`` / ``relu`` select the layer epilogue. ``relu``: 'hidden' (every layer but the classifier,

@@ -454,6 +454,58 @@ def adamw(w: np.ndarray, g: np.ndarray, m: np.ndarray, v: np.ndarray, scalars: A
     return w2, m2, v2
 
 
+class LionScalars(tuple):
+    """Lion's scalars, each already rounded to f32 (``lion_scalars``); ``wd`` rides along because the update tests it
+    against 0, as ``AdamWScalars`` does. No eps and no step: Lion has no bias correction."""
+    FIELDS = ("beta1", "omb1", "beta2", "omb2", "lr", "decay", "wd")
+
+    def __new__(cls, *vals):
+        assert len(vals) == len(cls.FIELDS)
+        return super().__new__(cls, (np.float32(x) for x in vals))
+
+    def __getattr__(self, name):
+        try:
+            return self[self.FIELDS.index(name)]
+        except ValueError:
+            raise AttributeError(name) from None
+
+    def kernel_args(self):
+        """The seven scalars the native launchers take, as Python floats holding the f32 values."""
+        return [float(x) for x in self]
+
+
+def lion_scalars(lr: float, wd: float, beta1: float, beta2: float) -> LionScalars:
+    """Lion's scalars of a request, computed in float64 and rounded once to f32; the kernels, the C++ engine and
+    ``lion`` below all receive these values, so every path sees the same bits."""
+    lr, wd, b1, b2 = float(lr), float(wd), float(beta1), float(beta2)
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+        raise ValueError(f"Lion: betas must lie in [0, 1), got {(beta1, beta2)}")
+    if not (math.isfinite(lr) and math.isfinite(wd)):
+        raise ValueError(f"Lion: lr and weight_decay must be finite, got {(lr, wd)}")
+    return LionScalars(b1, 1.0 - b1, b2, 1.0 - b2, lr, 1.0 - lr * wd, wd)
+
+
+def lion(w: np.ndarray, g: np.ndarray, m: np.ndarray, scalars: LionScalars, grad_scale: float = 1.0):
+    """fp32 Lion with the kernel's operation order (csrc/bfp/bfp_format.h lion_update): each fma emulated in float64
+    and rounded. The float64 sum of an f32 product and an f32 has the exact fma's sign (a product of two f32 values is
+    exact in float64, and a float64 sum is zero only when the exact sum is), so the sign decision compares bit for
+    bit. Returns (w', m')."""
+    s = scalars
+    f64 = np.float64
+    w = np.asarray(w, np.float32)
+    m = np.asarray(m, np.float32)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        g = (np.asarray(g, np.float32) * np.float32(grad_scale)).astype(np.float32)
+        t1 = (s.omb1 * g).astype(np.float32)
+        c = (f64(s.beta1) * m.astype(f64) + t1.astype(f64)).astype(np.float32)
+        sg = np.where(c > 0, np.float32(1), np.where(c < 0, np.float32(-1), c)).astype(np.float32)
+        base = (w * s.decay).astype(np.float32) if s.wd != 0 else w
+        w2 = (f64(-s.lr) * sg.astype(f64) + base.astype(f64)).astype(np.float32)
+        t2 = (s.omb2 * g).astype(np.float32)
+        m2 = (f64(s.beta2) * m.astype(f64) + t2.astype(f64)).astype(np.float32)
+    return w2, m2
+
+
 # --------------------------------------------------------------------------- 8-bit AdamW state (moment_codec="bfp8")
 # Both moments of a bucket of n_pad elements live in one uint8 plane each, exactly ``pack(x, n_pad, "bfp_rne")`` of one
 # shard of n_pad elements: bytes [0, n_pad) the int8 mantissas (element-indexed), bytes [n_pad, n_pad + n_pad/16) the

@@ -290,6 +290,46 @@ def adamw(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Ten
             lp.view(-1)[lo:hi].copy_(master.view(-1)[lo:hi].to(lp.dtype))
 
 
+def lion(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Tensor, *, codec,
+         mom: torch.Tensor, scalars: O.LionScalars, lp: torch.Tensor | None = None, grad_scale: float = 1.0,
+         n_valid: int | None = None, skip_shard: int = -1, skip_period: int = 0, shard_stride: int = 0,
+         clip: torch.Tensor | None = None):
+    """Fused decode + Lion in place (``bfp_oracle.lion``'s arithmetic): ``mom`` is the one moment plane (f32, laid out
+    as master), ``scalars`` the request's ``bfp_oracle.lion_scalars``; lp = bf16(master). On the GPU master and mom hold
+    ``n_valid`` rounded up to 8 elements (the kernel's lane trip). ``shard_stride`` and ``clip``: as :func:`adamw`."""
+    c = codec_id(codec)
+    if mom is None:
+        raise ValueError("Lion needs its moment plane (mom)")
+    if not isinstance(scalars, O.LionScalars):
+        raise TypeError(f"wire.lion takes bfp_oracle.lion_scalars, got {type(scalars).__name__}")
+    n_valid = master.numel() if n_valid is None else int(n_valid)
+    if master.is_cuda:
+        _ext.require().wire_lion(wire, int(shard_elems), int(n_shards), int(skip_shard), int(skip_period), master,
+                                 lp, mom, scalars.kernel_args(), float(grad_scale), n_valid, c, int(shard_stride),
+                                 clip)
+        return
+    if clip is not None:
+        grad_scale = O.clip_scale(grad_scale, _np_f32(clip))
+    sb = O.shard_bytes(c, shard_elems)
+    raw = _np_u8(wire)
+    if shard_stride:
+        raw = np.concatenate([raw[s * shard_stride: s * shard_stride + sb] for s in range(n_shards)])
+    n = shard_elems * n_shards
+    g = O.unpack(raw, n, shard_elems, c)
+    w = master.view(-1).numpy()
+    m = mom.view(-1).numpy()
+    period = skip_period if skip_period >= 1 else (1 << 30)
+    for s in range(n_shards):
+        if skip_shard >= 0 and s % period == skip_shard:
+            continue
+        lo, hi = s * shard_elems, min((s + 1) * shard_elems, n_valid)
+        if hi <= lo:
+            continue
+        w[lo:hi], m[lo:hi] = O.lion(w[lo:hi], g[lo:hi], m[lo:hi], scalars, grad_scale)
+        if lp is not None:
+            lp.view(-1)[lo:hi].copy_(master.view(-1)[lo:hi].to(lp.dtype))
+
+
 def moment_plane(n_pad: int, device) -> torch.Tensor:
     """A zeroed 8-bit moment plane (the zero state) of a padded bucket of ``n_pad`` elements: uint8,
     ``n_pad * 17 / 16`` bytes (``bfp_oracle.moment_plane_bytes``)."""

@@ -66,7 +66,14 @@ def _round_up(a, b):
     return _cdiv(a, b) * b
 
 
-OPTIMIZERS = ("sgd", "adamw")
+OPTIMIZERS = ("sgd", "adamw", "lion")
+DEFAULT_BETAS = {"sgd": (0.9, 0.999), "adamw": (0.9, 0.999), "lion": (0.9, 0.99)}
+
+
+def resolve_betas(opt, betas):
+    """``betas`` left unset: AdamW's (0.9, 0.999) for ``sgd`` (which ignores them) and ``adamw``, Lion's (0.9, 0.99)
+    for ``lion`` (Chen et al. 2023)."""
+    return DEFAULT_BETAS.get(opt, (0.9, 0.999)) if betas is None else betas
 CLIP_GROUP_LIMIT = f"a clip group holds at most {NUM_SLOTS} deferred requests"
 
 
@@ -182,6 +189,8 @@ def moment_request(moment_codec, moment_seed, mom, var, L, master, *, opt, trust
         if moment_seed is not None:
             raise ValueError("moment_seed belongs to moment_codec='bfp8'")
         return None
+    if opt == "lion":
+        raise ValueError("moment_codec='bfp8': AdamW only (opt='lion' keeps its one moment plane in f32)")
     if opt != "adamw":
         raise ValueError("moment_codec='bfp8': AdamW only (opt='sgd' keeps no second moment; its momentum stays f32)")
     if trust_ratio:
@@ -201,14 +210,43 @@ def moment_request(moment_codec, moment_seed, mom, var, L, master, *, opt, trust
     return seed
 
 
+def lion_request(mom, var, *, lr, weight_decay, momentum, nesterov, betas, trust_ratio=False, device=None):
+    """Validate one ``opt="lion"`` request; its ``bfp_oracle.LionScalars``. ``mom`` is Lion's one moment plane (f32,
+    contiguous, laid out as master, on ``device`` where one is given); there is no second plane, no ``step`` (no bias
+    correction; a value given is ignored) and no trust ratio."""
+    if trust_ratio:
+        raise ValueError("trust_ratio is a flag of opt='adamw' (a trust ratio on Lion is not provided)")
+    if momentum or nesterov:
+        raise ValueError("momentum / nesterov belong to SGD: Lion's moment is governed by betas")
+    if var is not None:
+        raise ValueError("Lion keeps one moment plane (mom): var must be None")
+    if mom is None:
+        raise ValueError("Lion needs its moment plane: mom (f32, laid out as master)")
+    if mom.dtype != torch.float32 or not mom.is_contiguous():
+        raise ValueError(f"Lion: mom must be a contiguous float32 tensor, got {mom.dtype}"
+                         f"{'' if mom.is_contiguous() else ', not contiguous'}")
+    if device is not None and (mom.device.type != torch.device(device).type or (
+            mom.device.type == "cuda" and torch.device(device).index not in (None, mom.device.index))):
+        raise ValueError(f"Lion: mom must be on the engine's device {device}, got {mom.device}")
+    betas = resolve_betas("lion", betas)
+    return wire.O.lion_scalars(lr, weight_decay, betas[0], betas[1])
+
+
 def adamw_request(opt, mom, var, *, lr, weight_decay, momentum, nesterov, betas, eps, step, trust_ratio=False,
-                  n_adapt=None, n_valid=None):
+                  n_adapt=None, n_valid=None, device=None):
     """Validate one request's optimizer arguments; the step's ``bfp_oracle.AdamWScalars`` for ``opt="adamw"``
-    (``mom`` the first moment, ``var`` the second, ``step`` the bucket's 1-based update count), None for SGD.
+    (``mom`` the first moment, ``var`` the second, ``step`` the bucket's 1-based update count), the request's
+    ``bfp_oracle.LionScalars`` for ``opt="lion"`` (:func:`lion_request`), None for SGD.
     ``trust_ratio`` (AdamW only): the layer-wise trust ratio (LAMB) over the bucket's first ``n_adapt`` of ``n_valid``
     elements; the scalars are then ``bfp_oracle.LambScalars``."""
     if opt not in OPTIMIZERS:
         raise ValueError(f"unknown optimizer {opt!r} (one of {OPTIMIZERS})")
+    if opt == "lion":
+        if n_adapt is not None:
+            raise ValueError("n_adapt belongs to trust_ratio=True, a flag of opt='adamw'")
+        return lion_request(mom, var, lr=lr, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov,
+                            betas=betas, trust_ratio=trust_ratio, device=device)
+    betas = resolve_betas(opt, betas)
     if trust_ratio and opt != "adamw":
         raise ValueError("trust_ratio is a flag of opt='adamw' (LARS on the SGD path is not provided)")
     if n_adapt is not None and not trust_ratio:
@@ -455,7 +493,7 @@ class CompressedAllReduce:
                       grad_scale: float = 1.0, weight_decay: float = 0.0, momentum: float = 0.0,
                       nesterov: bool = False, update_after=None, defer: bool = False,
                       name: str = "bucket", opt: str = "sgd", var: torch.Tensor | None = None,
-                      betas=(0.9, 0.999), eps: float = 1e-8, step: int | None = None, trust_ratio: bool = False,
+                      betas=None, eps: float = 1e-8, step: int | None = None, trust_ratio: bool = False,
                       n_adapt: int | None = None, trust_out: torch.Tensor | None = None,
                       clip: torch.Tensor | None = None, residual: torch.Tensor | None = None,
                       sr_seed: int | None = None, moment_codec: str = "f32",
@@ -475,7 +513,10 @@ class CompressedAllReduce:
         with probability equal to the dropped fraction (``bfp_oracle.sr_pack`` / ``sr_reduce``), stateless; every rank
         passes the same seed. Mesh schedule, ``bfp_rne`` / ``bfp4_rne`` only. ``moment_codec="bfp8"`` (AdamW): ``mom`` /
         ``var`` are 8-bit moment planes (``wire.moment_plane(layout(n).n_pad, device)``; ``var`` holds sqrt(v)) updated
-        by ``wire.adamw_q`` under the request seed ``moment_seed``, on every schedule; not with ``trust_ratio``."""
+        by ``wire.adamw_q`` under the request seed ``moment_seed``, on every schedule; not with ``trust_ratio``.
+        ``opt="lion"``: Lion (``bfp_oracle.lion``), ``mom`` its one f32 moment plane (required; no ``var``, ``step``
+        ignored), on every schedule and the sharded update; no ``trust_ratio``, no ``moment_codec="bfp8"``. ``betas``
+        left unset: (0.9, 0.999) for AdamW, (0.9, 0.99) for Lion."""
         clip_request(clip, defer, self.device)
         if clip is not None and self.compat_owner_fp32 and self.algo == "ring":
             raise ValueError("clip: not with compat_owner_fp32 (the owner's slices would be updated from another "
@@ -483,8 +524,9 @@ class CompressedAllReduce:
         n_valid = int(n_valid if n_valid is not None else master.numel())
         scalars = adamw_request(opt, mom, var, lr=lr, weight_decay=weight_decay, momentum=momentum,
                                 nesterov=nesterov, betas=betas, eps=eps, step=step, trust_ratio=trust_ratio,
-                                n_adapt=n_adapt, n_valid=n_valid)
+                                n_adapt=n_adapt, n_valid=n_valid, device=self.device)
         lamb = isinstance(scalars, wire.O.LambScalars)
+        lion = isinstance(scalars, wire.O.LionScalars)
         if lamb and self.compat_owner_fp32 and self.algo == "ring":
             raise ValueError("trust_ratio: not with compat_owner_fp32 (the owner's slices would be updated from "
                              "another gradient than the one the norms were taken over)")
@@ -524,6 +566,9 @@ class CompressedAllReduce:
                                                  grad_scale=grad_scale, n_valid=nv, n_adapt=adapt,
                                                  skip_shard=skip[0], skip_period=skip[1], clip=planes["clip"])
                 tr["regions"].append((shard, off, length, nv, adapt, skip))
+            elif lion:
+                wire.lion(G, shard, n_shards, master.view(-1)[off:off + length], codec=codec, scalars=scalars,
+                          grad_scale=grad_scale, n_valid=nv, skip_shard=skip[0], skip_period=skip[1], **planes)
             elif scalars is not None:
                 wire.adamw(G, shard, n_shards, master.view(-1)[off:off + length], codec=codec,
                            var=var.view(-1)[off:off + length], scalars=scalars, grad_scale=grad_scale, n_valid=nv,
@@ -884,6 +929,9 @@ def uncompressed_allreduce_sgd(transport: Transport, grad, master, lp=None, mom=
     if trust_ratio:
         raise ValueError("trust_ratio belongs to the compressed engines' two-pass epilogue; the uncompressed baseline "
                          "has a single update kernel")
+    if opt == "lion":
+        raise ValueError("opt='lion' belongs to the compressed engines' epilogues; the uncompressed baseline offers "
+                         "SGD and AdamW")
     scalars = adamw_request(opt, mom, var, lr=lr, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov,
                             betas=betas, eps=eps, step=step)
     transport.all_reduce_(grad)

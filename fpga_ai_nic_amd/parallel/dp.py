@@ -23,7 +23,8 @@ from ..ops import gemm as G
 from ..ops import gemm_tune, wire
 from ..utils import tracing
 from ..config import wire_codec
-from .allreduce import MAX_PEERS, NUM_SLOTS, OPTIMIZERS, CompressedAllReduce, Handle, _round_up
+from .allreduce import (MAX_PEERS, NUM_SLOTS, OPTIMIZERS, CompressedAllReduce, Handle, _round_up,
+                        resolve_betas)
 from .transport import Transport
 
 
@@ -86,7 +87,7 @@ class DataParallelTrainer:
                  loss_scale: float = 1.0, average: bool = True, profile: bool = False, prepack: bool = True,
                  commit_at_end: bool | None = None, fused_update: bool | None = None,
                  gemm_inflight: str | None = None, wgrad_pair: bool | str | None = None, optimizer: str = "sgd",
-                 betas=(0.9, 0.999), eps: float = 1e-8, trust_ratio: bool = False,
+                 betas=None, eps: float = 1e-8, trust_ratio: bool = False,
                  max_grad_norm: float | None = None, error_feedback: bool = False,
                  error_feedback_codec: str = "bfp_rne", stochastic_rounding: bool = False, sr_seed: int = 0,
                  moment_codec: str = "f32"):
@@ -128,13 +129,17 @@ class DataParallelTrainer:
         8 layers; ``fused_update`` is off (the GEMM epilogue cannot wait for the group); not with a sharded-update
         engine. With any ``optimizer`` and with ``trust_ratio``.
 
-        ``optimizer``: 'sgd' or 'adamw' (``betas``, ``eps``; the model must hold the second-moment planes,
+        ``optimizer``: 'sgd', 'adamw' or 'lion'. AdamW (``betas``, ``eps``; the model holds the second-moment planes,
         ``MLP(..., adam=True)``). AdamW runs in the engine's decode + update epilogue — not in the bwd-weight GEMM's,
         so ``fused_update`` is off with it — with ``opt_step``, the 1-based update count, advanced once per
         ``backward_pass``. ``trust_ratio`` (AdamW): the layer-wise trust ratio (LAMB) — each layer's weight matrix
         steps by lr * ||W|| / ||update||, its bias by lr — through the engines' two-pass epilogue; ``trust_ratios``
         ([L, 3] f32 on the model's device) then holds every layer's {lr * phi, lr, phi} of the last step, written by
-        the requests themselves (no host sync). Not with a sharded-update engine.
+        the requests themselves (no host sync). Not with a sharded-update engine. 'lion': Lion (``bfp_oracle.lion``;
+        ``betas`` default (0.9, 0.99), no ``eps``, no step count) on the model's momentum plane, ``MLP(...,
+        momentum=True)`` — SGD-momentum's planes and bytes, in the engine's epilogue like AdamW, so ``fused_update`` is
+        off with it; with ``max_grad_norm``, ``error_feedback``, ``stochastic_rounding`` and a sharded-update engine,
+        not with ``trust_ratio`` or ``moment_codec='bfp8'``. ``betas`` left unset: (0.9, 0.999) for AdamW.
 
         ``fused_update`` (default env FAN_FUSED_UPDATE, else on): with a single-rank engine (world 1, requests
         inline: the all-reduce of one rank is the identity) and the GEMM-encoded wire, the bwd-weight GEMM's epilogue
@@ -161,6 +166,7 @@ class DataParallelTrainer:
         self.lr, self.wd, self.momentum, self.nesterov = lr, weight_decay, momentum, nesterov
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
+        betas = resolve_betas(optimizer, betas)
         self.optimizer, self.betas, self.eps = optimizer, (float(betas[0]), float(betas[1])), float(eps)
         self.opt_step = 0  # updates applied so far (AdamW's bias correction; checkpointed)
         if optimizer == "adamw":
@@ -169,8 +175,21 @@ class DataParallelTrainer:
             wire.O.adamw_scalars(lr, weight_decay, self.betas[0], self.betas[1], self.eps, 1)  # validates
             if moment_codec != "bfp8" and any(l.mom is None or l.var is None for l in model.layers):
                 raise ValueError("optimizer='adamw' needs a model with both moment planes: MLP(..., adam=True)")
+        if optimizer == "lion":
+            if momentum or nesterov:
+                raise ValueError("momentum / nesterov belong to SGD: Lion's moment is governed by betas")
+            if trust_ratio:
+                raise ValueError("trust_ratio is a flag of optimizer='adamw' (a trust ratio on Lion is not provided)")
+            wire.O.lion_scalars(lr, weight_decay, self.betas[0], self.betas[1])  # validates
+            if any(l.mom is None or l.mom.dtype != torch.float32 for l in model.layers):
+                raise ValueError("optimizer='lion' needs a model with the f32 momentum plane: MLP(..., momentum=True)")
+            if any(l.var is not None for l in model.layers):
+                raise ValueError("optimizer='lion' keeps one moment plane: the model holds a second (adam=True); "
+                                 "allocate it with MLP(..., momentum=True)")
         self.moment_codec = wire.O.moment_codec_check(moment_codec)
         if moment_codec == "bfp8":
+            if optimizer == "lion":
+                raise ValueError("moment_codec='bfp8': optimizer='adamw' only (Lion's one moment plane stays f32)")
             if optimizer != "adamw":
                 raise ValueError("moment_codec='bfp8': optimizer='adamw' only (SGD keeps no second moment; its "
                                  "momentum stays f32)")
@@ -317,6 +336,9 @@ class DataParallelTrainer:
             kw["residual"] = self.residuals[self._index(l)]
         if self.stochastic_rounding:
             kw["sr_seed"] = self._sr_seed_of(l)
+        if self.optimizer == "lion":
+            kw.update(opt="lion", betas=self.betas)
+            return kw
         if self.optimizer != "adamw":
             return kw
         kw.update(opt="adamw", var=l.var, betas=self.betas, eps=self.eps, step=self.opt_step)
@@ -407,6 +429,11 @@ class DataParallelTrainer:
                 return
             wire.adamw(src, l.n_pad, 1, l.master, codec=codec, lp=l.lp, mom=l.mom, var=l.var,
                        scalars=scalars, grad_scale=self.grad_scale, n_valid=l.n, clip=clip)
+            return
+        if self.optimizer == "lion":
+            scalars = wire.O.lion_scalars(self.lr, self.wd, self.betas[0], self.betas[1])
+            wire.lion(src, l.n_pad, 1, l.master, codec=codec, lp=l.lp, mom=l.mom, scalars=scalars,
+                      grad_scale=self.grad_scale, n_valid=l.n, clip=clip)
             return
         wire.sgd(src, l.n_pad, 1, l.master, codec=codec, lp=l.lp, mom=l.mom, lr=self.lr,
                  grad_scale=self.grad_scale, weight_decay=self.wd, momentum=self.momentum, nesterov=self.nesterov,

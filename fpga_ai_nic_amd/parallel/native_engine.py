@@ -24,7 +24,7 @@ import torch
 from .. import _ext
 from ..ops import wire
 from .allreduce import (CLIP_GROUP_LIMIT, NUM_SLOTS, BucketLayout, ChecksumError, CommTimeoutError, adamw_request,
-                        clip_group_check, clip_request, moment_request, residual_request, sr_request)
+                        clip_group_check, clip_request, moment_request, residual_request, resolve_betas, sr_request)
 from .transport import NativeTransport, Transport
 
 _ALGOS = {"mesh": 0, "ring": 1}
@@ -256,7 +256,7 @@ class NativeAllReduce:
                       grad_scale: float = 1.0, weight_decay: float = 0.0, momentum: float = 0.0,
                       nesterov: bool = False, update_after=None, defer: bool = False,
                       name: str = "bucket", prepacked=None, layout=None, on_producer: bool = False,
-                      opt: str = "sgd", var: torch.Tensor | None = None, betas=(0.9, 0.999), eps: float = 1e-8,
+                      opt: str = "sgd", var: torch.Tensor | None = None, betas=None, eps: float = 1e-8,
                       step: int | None = None, trust_ratio: bool = False, n_adapt: int | None = None,
                       trust_out: torch.Tensor | None = None, clip: torch.Tensor | None = None,
                       residual: torch.Tensor | None = None, sr_seed: int | None = None,
@@ -278,19 +278,25 @@ class NativeAllReduce:
         :meth:`CompressedAllReduce.allreduce_sgd`; refused where ``residual`` is, and together with it.
         ``moment_codec="bfp8"`` / ``moment_seed``: AdamW's moments in 8-bit planes (``mom`` / ``var`` are then
         ``wire.moment_plane`` tensors), as :meth:`CompressedAllReduce.allreduce_sgd`; every schedule carries it, the
-        trust ratio and the sharded update refuse it."""
+        trust ratio and the sharded update refuse it. ``opt="lion"``: Lion, ``mom`` its one f32 moment plane (as
+        :meth:`CompressedAllReduce.allreduce_sgd`); every schedule and the sharded update carry it, ``trust_ratio`` and
+        ``moment_codec="bfp8"`` are refused. ``betas`` left unset: (0.9, 0.999) for AdamW, (0.9, 0.99) for Lion."""
         n_valid = int(n_valid if n_valid is not None else master.numel())
+        betas = resolve_betas(opt, betas)
         clip_request(clip, defer, self.device)
         sr_seed = self._sr(sr_seed, n_valid, prepacked, layout, residual)
         residual = self._residual(residual, n_valid, prepacked, layout)
         scalars = adamw_request(opt, mom, var, lr=lr, weight_decay=weight_decay, momentum=momentum,
                                 nesterov=nesterov, betas=betas, eps=eps, step=step, trust_ratio=trust_ratio,
-                                n_adapt=n_adapt, n_valid=n_valid)
+                                n_adapt=n_adapt, n_valid=n_valid, device=self.device)
         pre, pre_n = (None, 0) if prepacked is None else prepacked
         ls, lc = (0, 0) if layout is None else (int(layout[0]), int(layout[1]))
         mq_seed = moment_request(moment_codec, moment_seed, mom, var, self.layout(n_valid, ls, lc), master, opt=opt,
                                  trust_ratio=trust_ratio, sharded=self.shard_update)
-        okw = {} if scalars is None else dict(opt=1, var=var.view(-1), adamw=scalars.kernel_args())
+        if isinstance(scalars, wire.O.LionScalars):
+            okw = dict(opt=2, lion=scalars.kernel_args())
+        else:
+            okw = {} if scalars is None else dict(opt=1, var=var.view(-1), adamw=scalars.kernel_args())
         if mq_seed is not None:  # the 8-bit planes stand in for mom / var
             okw = dict(opt=1, adamw=scalars.kernel_args(), mom_q=mom.view(-1), var_q=var.view(-1), moment_seed=mq_seed)
             mom = None

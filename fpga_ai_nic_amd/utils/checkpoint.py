@@ -5,7 +5,8 @@ The reference never writes weights to disk; its in-memory layo
 defines the on-disk format as exactly that:
 
 * ``<path>.safetensors`` — tensors ``fc{i}.weight`` [C_i, C_{i+1}] and ``fc{i}.bias`` [C_{i+1}] in f32 (or bf16),
-  optional ``fc{i}.momentum`` (flat, f32), or for an AdamW model ``fc{i}.exp_avg`` / ``fc{i}.exp_avg_sq`` (its two
+  optional ``fc{i}.momentum`` (flat, f32: SGD's momentum, or Lion's one moment plane when the index says
+  ``optimizer`` = "lion"), or for an AdamW model ``fc{i}.exp_avg`` / ``fc{i}.exp_avg_sq`` (its two
   moment planes, flat, f32; the index then carries ``optimizer`` and ``opt_step``, the updates applied so far; a
   stochastically rounded run adds ``sr_step``, the update counter its request seeds are derived from; a model with
   8-bit moment planes stores each plane's bytes whole under the same two names, uint8, and the index carries
@@ -72,9 +73,17 @@ def save(path: str, model, *, iteration: int = 0, dtype: str = "f32", meta: dict
     return path
 
 
-def load(path: str, model) -> dict:
+def load(path: str, model, optimizer: str | None = None) -> dict:
+    """``optimizer``: the resuming run's. Lion's ``fc{i}.momentum`` plane is not SGD's momentum and not AdamW's first
+    moment, so a checkpoint whose index names an optimizer loads into a Lion run, and a Lion checkpoint into any run,
+    only under that optimizer."""
     with open(path + ".json") as f:
         info = json.load(f)
+    saved_opt = info.get("optimizer")
+    if optimizer is not None and saved_opt is not None and saved_opt != optimizer and "lion" in (saved_opt, optimizer):
+        raise ValueError(f"checkpoint was written under optimizer={saved_opt!r}; this run is optimizer={optimizer!r} "
+                         f"(Lion's moment plane belongs to Lion alone: resume under the optimizer the checkpoint was "
+                         f"written with)")
     if list(info["sizes"]) != list(model.sizes):
         raise ValueError(f"checkpoint sizes {info['sizes']} != model sizes {model.sizes}")
     sd = load_file(path + ".safetensors")
