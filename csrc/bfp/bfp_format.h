@@ -147,6 +147,36 @@ __device__ __forceinline__ float lamb_direction(const LambParams& p, float w, fl
   return p.weight_decay != 0.0f ? fmaf(p.weight_decay, w, ub) : ub;
 }
 
+// Adafactor (Shazeer & Stern 2018) with a factored second moment, no first moment, an absolute lr and per-tensor
+// update clipping; ops/bfp_oracle.py adafactor_* pin the operation order. The scalars that enter fp64 expressions stay
+// double (bfp_oracle.adafactor_scalars: beta2 = 1 - step^-0.8, omb2 = 1 - beta2, eps1 = 1e-30, lr, d the clipping
+// threshold); decay = 1 - lr * wd and wd are f32 as in LionParams.
+struct AdafactorParams {
+  double beta2, omb2, eps1, lr, d;
+  float grad_scale;
+  float weight_decay;  // only tested against 0: the decay itself is `decay`
+  float decay;
+};
+
+// How the Adafactor kernels tile a bucket: the adapted matrix [0, rows * cols), row-major over the gathered wire, in
+// tiles of kAfPanel consecutive rows by a strip of kAfStrip columns (a lane owns one 16-value group of every row of the
+// tile), then the tail [rows * cols, n_valid) in tail tiles of kAfStrip elements. Tile t = panel * n_strips + strip;
+// tail tiles follow the matrix tiles. The fp64 partials buffer of one request, at offsets fixed by the shape alone:
+//   col[n_panels][cols]  the tiles' column sums of s      row[n_strips][rows]  the tiles' row sums of s
+//   rms[n_tiles + n_tail_tiles]  the tiles' sums of u^2   rsum[n_row_blocks]   adafactor_factors' block sums of R'
+constexpr int kAfPanel = 16;
+constexpr int kAfBatch = 8;         // rows of a panel between two barriers
+constexpr int kAfStrip = 256 * 16;  // one 16-value group per lane of a 256-lane workgroup
+struct AdafactorShape {
+  size_t rows, cols, tail;
+  int n_strips, n_panels, n_tiles, n_tail_tiles, n_row_blocks;
+  __host__ __device__ __forceinline__ size_t col_off() const { return 0; }
+  __host__ __device__ __forceinline__ size_t row_off() const { return (size_t)n_panels * cols; }
+  __host__ __device__ __forceinline__ size_t rms_off() const { return row_off() + (size_t)n_strips * rows; }
+  __host__ __device__ __forceinline__ size_t rsum_off() const { return rms_off() + (size_t)n_tiles + n_tail_tiles; }
+  __host__ __device__ __forceinline__ size_t partials() const { return rsum_off() + n_row_blocks; }
+};
+
 __host__ __device__ inline size_t wire_shard_bytes(int codec, size_t n_s) {
   switch (codec) {
     case kBfpTrunc:
@@ -800,6 +830,24 @@ void launch_lamb_ratio(const double* partials, int n_pairs, float lr, float* wor
 // (of n_s elements) with (s % skip_period) == skip_shard are left untouched, as in pass 1.
 void launch_wire_lamb_apply(float* master, bf16_t* lp, const float* mom, LambParams p, const float* words, size_t n_s,
                             int skip_shard, int skip_period, size_t n_valid, size_t adapt_end, hipStream_t stream);
+// The Adafactor epilogue of one request whose gathered wire is one region of n_shards equal shards (element e of the
+// bucket in shard e / n_s at offset e % n_s; shard_stride as launch_wire_sgd's): six launches on one stream, no atomics,
+// no fences, every sum fp64 in an order the shape alone fixes (so any grid gives the same bits).
+//   1 wire_adafactor_stats   tiles: row and column sums of s = g^2 + eps1 into partials; tail tiles: V' and a_k
+//   2 adafactor_factors      R', C' into fac, b into ab, each row block's sum of R' into partials
+//   3 adafactor_rowscale     meanR from the block sums, a into ab (the one step that needs every R')
+//   4 wire_adafactor_rms     read-only: each tile's sum of u^2
+//   5 adafactor_scale        one block: words = {scale_mat, rms_mat, scale_tail, rms_tail}
+//   6 wire_adafactor_apply   w' = fma(-scale, u, wd != 0 ? w * decay : w), lp = bf16(w')
+// fac = R[rows] | C[cols] | V[tail] (f32, updated in place), ab = a[rows] | b[cols] | a_tail[tail] (f32 scratch),
+// partials: adafactor_shape(...).partials() doubles, words: f32[4]. cols % 16 == 0, rows * cols <= n_valid <=
+// n_s * n_shards. max_blocks > 0 caps the tiled launches' grids below the wire kernels' cap; `phases` is a mask of the
+// launches to run (bit k - 1 for launch k; the probes time them one by one).
+AdafactorShape adafactor_shape(size_t rows, size_t cols, size_t n_valid);
+void launch_wire_adafactor(int codec, const void* wire, size_t n_s, int n_shards, float* master, bf16_t* lp,
+                           float* fac, float* ab, double* partials, float* words, AdafactorParams p, size_t rows,
+                           size_t cols, size_t n_valid, hipStream_t stream, size_t shard_stride = 0,
+                           int max_blocks = 0, int phases = 63);
 // Decode to f32/bf16 from a strided wire (as launch_wire_sgd's shard_stride).
 void launch_wire_unpack_strided(int codec, int out_dtype, const void* in, size_t shard_stride, void* out, size_t n_s,
                                 int n_shards, hipStream_t stream);

@@ -721,6 +721,343 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
+// ---------------------------------------------------------------- Adafactor epilogue (bfp_format.h AdafactorShape)
+// The statistics are 2-D and the gradient exists only as wire, so the three wire kernels walk TILES, not a flat
+// element range: a workgroup takes tiles t = blockIdx.x, + gridDim.x, ...; in a matrix tile lane l owns column group
+// strip * 256 + l (16 columns) and walks down the panel's rows, one 16-value wire group per row — one 16-B mantissa
+// load plus the exponent byte for the BFP codecs. What belongs to the lane's columns (16 column sums, or the 16 b_j)
+// stays in registers for the whole panel; what belongs to a row (its sum, or a_i) is uniform over the workgroup.
+
+// The kernels of this section are built without the packed f32 instructions (v_pk_mul_f32, v_pk_fma_f32, v_pk_add_f32:
+// two f32 operations per lane and instruction), by a target attribute on each kernel: new kernels of this project do
+// not use them, and kernels that wait on memory lose nothing (with the attribute the apply variants move by a few
+// VGPRs and one occupancy step either way, the others not at all: profiles/adafactor_epilogue.txt). The attribute has
+// a price. This file's own __forceinline__ helpers (WireLane16, DenseLane16, f32_to_bf16) are still inlined, but the
+// HIP headers' plain `inline` device functions are compiled for the default features and are then CALLED from these
+// kernels (measured: s_swappc to __syncthreads, __shfl_down(double) and make_double2, 64 B of scratch per lane and
+// 165 VGPRs in the stats kernel). So the three primitives below are spelled with builtins, and block_sum, which calls
+// two of them, is repeated over them; change block_sum and af_block_sum together.
+#define FAN_AF_KERNEL __global__ __attribute__((target("no-packed-fp32-ops"))) void __launch_bounds__(kBlock)
+
+__device__ __forceinline__ void af_sync() {  // (__syncthreads' three statements)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// The value lane + off of the wave holds (the lane's own past the wave's end), as __shfl_down.
+__device__ __forceinline__ double af_shfl_down(double x, int off) {
+  const int lane = (int)(threadIdx.x & 63), src = lane + off < 64 ? lane + off : lane;
+  const long long b = __builtin_bit_cast(long long, x);
+  const int lo = __builtin_amdgcn_ds_bpermute(src << 2, (int)b);
+  const int hi = __builtin_amdgcn_ds_bpermute(src << 2, (int)(b >> 32));
+  return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
+}
+
+// block_sum's order exactly (lanes 32 .. 1, then the waves in wave order by thread 0), results valid in thread 0.
+template <int kN>
+__device__ __forceinline__ void af_block_sum(double (&a)[kN]) {
+  __shared__ double red[kN][kBlock / 64];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+    for (int k = 0; k < kN; ++k) a[k] += af_shfl_down(a[k], off);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < kN; ++k) red[k][threadIdx.x >> 6] = a[k];
+  }
+  af_sync();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < kN; ++k) a[k] = red[k][0];
+#pragma unroll
+    for (int i = 1; i < kBlock / 64; ++i) {
+#pragma unroll
+      for (int k = 0; k < kN; ++k) a[k] += red[k][i];
+    }
+  }
+}
+
+// The 16 values of the wire group at bucket element e (a multiple of 16): shard e / n_s, offset e % n_s.
+template <int C>
+__device__ __forceinline__ void af_load(const uint8_t* __restrict__ wire, size_t n_s, size_t sb, size_t e,
+                                        float scale, float (&g)[16]) {
+  const size_t s = e / n_s;
+  WireLane16<C>::load16(wire + s * sb, n_s, e - s * n_s, g);
+#pragma unroll
+  for (int j = 0; j < 16; ++j) g[j] = g[j] * scale;
+}
+
+// Launch 1. Matrix tile: s = fma(g, g, eps1) in fp64 (g^2 is exact there). A lane adds each s to its column's sum and
+// to the row's; a row's sum over the strip = the lane's 16 values in order, the wave's lanes by shuffles (32 .. 1),
+// the waves in wave order through LDS. Rows go in batches of kAfBatch: kAfBatch row sums per lane cross the wave
+// together and ONE barrier per batch publishes them (two LDS buffers alternate: a buffer is rewritten two barriers
+// after it was read). Lanes past the last column group and rows past the panel's last row add 0.0, which changes no
+// bit. The tile's row sums land at row[strip][r], its column sums at col[panel][c]: every slot has one writer.
+// Tail tile: element-wise, V' = f32(beta2 * V + omb2 * s) and a_k = f32(1 / sqrt(V')) straight into fac and ab.
+template <int C>
+FAN_AF_KERNEL
+    wire_adafactor_stats_kernel(const uint8_t* __restrict__ wire, size_t n_s, size_t sb, AdafactorShape sh,
+                                AdafactorParams p, float* __restrict__ fac, float* __restrict__ ab,
+                                double* __restrict__ partials) {
+  __shared__ double red[2][kAfBatch][kBlock / 64];
+  double* const colp = partials + sh.col_off();
+  double* const rowp = partials + sh.row_off();
+  const size_t n_adapt = sh.rows * sh.cols;
+  int buf = 0;
+  for (int tile = blockIdx.x; tile < sh.n_tiles + sh.n_tail_tiles; tile += gridDim.x) {
+    if (tile >= sh.n_tiles) {
+      const size_t k0 = ((size_t)(tile - sh.n_tiles) * kBlock + threadIdx.x) << 4;
+      if (k0 >= sh.tail) continue;
+      float g[16];
+      af_load<C>(wire, n_s, sb, n_adapt + k0, p.grad_scale, g);
+      float* const V = fac + sh.rows + sh.cols + k0;
+      float* const at = ab + sh.rows + sh.cols + k0;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        if (k0 + j < sh.tail) {
+          const double gd = (double)g[j];
+          const float v = (float)(p.beta2 * (double)V[j] + p.omb2 * fma(gd, gd, p.eps1));
+          V[j] = v;
+          at[j] = (float)(1.0 / sqrt((double)v));
+        }
+      }
+      continue;
+    }
+    const int panel = tile / sh.n_strips, strip = tile - panel * sh.n_strips;
+    const size_t c0 = ((size_t)strip * kBlock + threadIdx.x) << 4;  // the lane's first column
+    const bool act = c0 < sh.cols;
+    const size_t r0 = (size_t)panel * kAfPanel;
+    const size_t r1 = r0 + kAfPanel < sh.rows ? r0 + kAfPanel : sh.rows;
+    double cs[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) cs[j] = 0.0;
+    for (size_t rb = r0; rb < r1; rb += kAfBatch) {
+      double rs[kAfBatch];
+#pragma unroll
+      for (int k = 0; k < kAfBatch; ++k) {
+        rs[k] = 0.0;
+        if (act && rb + k < r1) {
+          float g[16];
+          af_load<C>(wire, n_s, sb, (rb + k) * sh.cols + c0, p.grad_scale, g);
+#pragma unroll
+          for (int j = 0; j < 16; ++j) {
+            const double gd = (double)g[j];
+            const double s = fma(gd, gd, p.eps1);
+            cs[j] += s;
+            rs[k] += s;
+          }
+        }
+      }
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < kAfBatch; ++k) rs[k] += af_shfl_down(rs[k], off);
+      }
+      if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < kAfBatch; ++k) red[buf][k][threadIdx.x >> 6] = rs[k];
+      }
+      af_sync();
+      if (threadIdx.x < kAfBatch && rb + threadIdx.x < r1) {
+        double t = red[buf][threadIdx.x][0];
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) t += red[buf][threadIdx.x][w];
+        rowp[(size_t)strip * sh.rows + rb + threadIdx.x] = t;
+      }
+      buf ^= 1;
+    }
+    if (act) {
+      double2* const dst = reinterpret_cast<double2*>(colp + (size_t)panel * sh.cols + c0);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        double2 d;
+        d.x = cs[2 * j];
+        d.y = cs[2 * j + 1];
+        dst[j] = d;
+      }
+    }
+  }
+}
+
+// Launch 2: one lane per row (blocks [0, n_row_blocks)) or per column (the blocks behind them). A row's sum is its
+// strips' partials in strip order, a column's its panels' in panel order; the mean, then the EMA in fp64, rounded once.
+// Row blocks also leave the fixed-order block sum of their (rounded) R' for launch 3; column lanes write b_j.
+FAN_AF_KERNEL
+    adafactor_factors_kernel(AdafactorShape sh, AdafactorParams p, float* __restrict__ fac, float* __restrict__ ab,
+                             double* __restrict__ partials) {
+  if ((int)blockIdx.x < sh.n_row_blocks) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    double sums[1] = {0.0};
+    if (i < sh.rows) {
+      const double* __restrict__ rowp = partials + sh.row_off();
+      double t = rowp[i];
+      for (int s = 1; s < sh.n_strips; ++s) t += rowp[(size_t)s * sh.rows + i];
+      const float r = (float)(p.beta2 * (double)fac[i] + p.omb2 * (t / (double)sh.cols));
+      fac[i] = r;
+      sums[0] = (double)r;
+    }
+    af_block_sum(sums);
+    if (threadIdx.x == 0) partials[sh.rsum_off() + blockIdx.x] = sums[0];
+  } else {
+    const size_t j = (size_t)(blockIdx.x - sh.n_row_blocks) * kBlock + threadIdx.x;
+    if (j >= sh.cols) return;
+    const double* __restrict__ colp = partials + sh.col_off();
+    double t = colp[j];
+    for (int q = 1; q < sh.n_panels; ++q) t += colp[(size_t)q * sh.cols + j];
+    const float c = (float)(p.beta2 * (double)fac[sh.rows + j] + p.omb2 * (t / (double)sh.rows));
+    fac[sh.rows + j] = c;
+    ab[sh.rows + j] = (float)(1.0 / sqrt((double)c));
+  }
+}
+
+// Launch 3: meanR = (the row blocks' sums, lane t taking blocks t, t + 256, ... in ascending order, then the fixed
+// tree) / rows — every block computes the same bits — and a_i = f32(1 / sqrt(R'_i / meanR)) for the block's rows.
+FAN_AF_KERNEL
+    adafactor_rowscale_kernel(AdafactorShape sh, const float* __restrict__ fac, float* __restrict__ ab,
+                              const double* __restrict__ partials) {
+  __shared__ double mean_r;
+  double sums[1] = {0.0};
+  for (int b = threadIdx.x; b < sh.n_row_blocks; b += kBlock) sums[0] += partials[sh.rsum_off() + b];
+  af_block_sum(sums);
+  if (threadIdx.x == 0) mean_r = sums[0] / (double)sh.rows;
+  af_sync();
+  const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < sh.rows) ab[i] = (float)(1.0 / sqrt((double)fac[i] / mean_r));
+}
+
+// The lane's 16 b_j of a matrix tile, kept in registers down the panel (b starts `rows` floats into ab, any alignment,
+// so the loads are scalar; they happen once per tile).
+__device__ __forceinline__ void af_load_b(const float* __restrict__ b, size_t c0, float (&v)[16]) {
+#pragma unroll
+  for (int j = 0; j < 16; ++j) v[j] = b[c0 + j];
+}
+
+// Launch 4, read-only: u = (g * a_i) * b_j on the matrix, g * a_k on the tail (f32 products in that order), u^2 exact
+// in fp64, summed per lane in its row order, then the block sum; one double per tile at rms[tile].
+template <int C>
+FAN_AF_KERNEL
+    wire_adafactor_rms_kernel(const uint8_t* __restrict__ wire, size_t n_s, size_t sb, AdafactorShape sh,
+                              AdafactorParams p, const float* __restrict__ ab, double* __restrict__ partials) {
+  const size_t n_adapt = sh.rows * sh.cols;
+  for (int tile = blockIdx.x; tile < sh.n_tiles + sh.n_tail_tiles; tile += gridDim.x) {
+    double acc = 0.0;
+    if (tile >= sh.n_tiles) {
+      const size_t k0 = ((size_t)(tile - sh.n_tiles) * kBlock + threadIdx.x) << 4;
+      if (k0 < sh.tail) {
+        float g[16];
+        af_load<C>(wire, n_s, sb, n_adapt + k0, p.grad_scale, g);
+        const float* const at = ab + sh.rows + sh.cols + k0;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          if (k0 + j < sh.tail) {
+            const double u = (double)(g[j] * at[j]);
+            acc = fma(u, u, acc);
+          }
+        }
+      }
+    } else {
+      const int panel = tile / sh.n_strips, strip = tile - panel * sh.n_strips;
+      const size_t c0 = ((size_t)strip * kBlock + threadIdx.x) << 4;
+      const size_t r0 = (size_t)panel * kAfPanel;
+      const size_t r1 = r0 + kAfPanel < sh.rows ? r0 + kAfPanel : sh.rows;
+      if (c0 < sh.cols) {
+        float b[16];
+        af_load_b(ab + sh.rows, c0, b);
+        for (size_t r = r0; r < r1; ++r) {
+          const float a = ab[r];
+          float g[16];
+          af_load<C>(wire, n_s, sb, r * sh.cols + c0, p.grad_scale, g);
+#pragma unroll
+          for (int j = 0; j < 16; ++j) {
+            const double u = (double)((g[j] * a) * b[j]);
+            acc = fma(u, u, acc);
+          }
+        }
+      }
+    }
+    double sums[1] = {acc};
+    af_block_sum(sums);
+    if (threadIdx.x == 0) partials[sh.rms_off() + tile] = sums[0];
+    af_sync();  // (af_block_sum's LDS is read by thread 0 until here)
+  }
+}
+
+// Launch 5, one block: the matrix tiles' and the tail tiles' sums (lane t takes tiles t, t + 256, ..., then the fixed
+// tree), rms = sqrt(sum / count) (0 for an empty tensor), scale = f32(lr / max(1, rms / d)); a NaN rms propagates.
+FAN_AF_KERNEL
+    adafactor_scale_kernel(AdafactorShape sh, AdafactorParams p, const double* __restrict__ partials,
+                           float* __restrict__ words) {
+  const double* __restrict__ rp = partials + sh.rms_off();
+  double sums[2] = {0.0, 0.0};
+  for (int i = threadIdx.x; i < sh.n_tiles; i += kBlock) sums[0] += rp[i];
+  for (int i = threadIdx.x; i < sh.n_tail_tiles; i += kBlock) sums[1] += rp[sh.n_tiles + i];
+  af_block_sum(sums);
+  if (threadIdx.x == 0) {
+    const double cnt[2] = {(double)sh.rows * (double)sh.cols, (double)sh.tail};
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const double rms = cnt[k] > 0.0 ? sqrt(sums[k] / cnt[k]) : 0.0;
+      const double q = rms / p.d;
+      words[2 * k] = (float)(p.lr / ((q > 1.0 || q != q) ? q : 1.0));
+      words[2 * k + 1] = (float)rms;
+    }
+  }
+}
+
+// Launch 6: launch 4's traversal with master read and written a 16-value group per lane (64 B in, 64 B out, 32 B of
+// bf16); u is recomputed, not stored. Tail elements go one by one (the bias segment may end inside a group).
+template <int C, bool HAS_LP>
+FAN_AF_KERNEL
+    wire_adafactor_apply_kernel(const uint8_t* __restrict__ wire, size_t n_s, size_t sb, AdafactorShape sh,
+                                AdafactorParams p, const float* __restrict__ ab, const float* __restrict__ words,
+                                float* __restrict__ master, bf16_t* __restrict__ lp) {
+  const size_t n_adapt = sh.rows * sh.cols;
+  const float ns_mat = -words[0], ns_tail = -words[2];
+  const bool wd = p.weight_decay != 0.0f;
+  for (int tile = blockIdx.x; tile < sh.n_tiles + sh.n_tail_tiles; tile += gridDim.x) {
+    if (tile >= sh.n_tiles) {
+      const size_t k0 = ((size_t)(tile - sh.n_tiles) * kBlock + threadIdx.x) << 4;
+      if (k0 >= sh.tail) continue;
+      float g[16];
+      af_load<C>(wire, n_s, sb, n_adapt + k0, p.grad_scale, g);
+      const float* const at = ab + sh.rows + sh.cols + k0;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        if (k0 + j < sh.tail) {
+          const size_t e = n_adapt + k0 + j;
+          const float w0 = master[e];
+          const float w = fmaf(ns_tail, g[j] * at[j], wd ? w0 * p.decay : w0);
+          master[e] = w;
+          if (HAS_LP) lp[e] = f32_to_bf16(w);
+        }
+      }
+      continue;
+    }
+    const int panel = tile / sh.n_strips, strip = tile - panel * sh.n_strips;
+    const size_t c0 = ((size_t)strip * kBlock + threadIdx.x) << 4;
+    if (c0 >= sh.cols) continue;
+    const size_t r0 = (size_t)panel * kAfPanel;
+    const size_t r1 = r0 + kAfPanel < sh.rows ? r0 + kAfPanel : sh.rows;
+    float b[16];
+    af_load_b(ab + sh.rows, c0, b);
+    for (size_t r = r0; r < r1; ++r) {
+      const float a = ab[r];
+      const size_t e = r * sh.cols + c0;
+      float g[16], w[16];
+      af_load<C>(wire, n_s, sb, e, p.grad_scale, g);
+      DenseLane16<float>::load16(master, e, w);
+#pragma unroll
+      for (int j = 0; j < 16; ++j) w[j] = fmaf(ns_mat, (g[j] * a) * b[j], wd ? w[j] * p.decay : w[j]);
+      DenseLane16<float>::store16(master, e, w);
+      if (HAS_LP) DenseLane16<bf16_t>::store16(lp, e, w);
+    }
+  }
+}
+
+#undef FAN_AF_KERNEL
+
 }  // namespace
 
 #define FAN_CODEC_SWITCH(codec, ...)                         \
@@ -1029,6 +1366,68 @@ void launch_wire_lamb_apply(float* master, bf16_t* lp, const float* mom, LambPar
   else
     hipLaunchKernelGGL((wire_lamb_apply_kernel<false>), grid, kBlock, 0, stream, master, lp, mom, p, words, n_s,
                        skip_shard, skip_period, n_valid, adapt_end);
+  FAN_HIP_CHECK(hipGetLastError());
+}
+
+AdafactorShape adafactor_shape(size_t rows, size_t cols, size_t n_valid) {
+  FAN_CHECK(rows >= 1 && cols >= 16 && cols % 16 == 0,
+            "adafactor: cols must be a positive multiple of 16 (a wire group may not cross rows) and rows >= 1");
+  FAN_CHECK(rows <= n_valid / cols, "adafactor: rows * cols must not exceed n_valid");
+  AdafactorShape sh{};
+  sh.rows = rows;
+  sh.cols = cols;
+  sh.tail = n_valid - rows * cols;
+  const size_t strips = (cols + kAfStrip - 1) / kAfStrip, panels = (rows + kAfPanel - 1) / kAfPanel;
+  const size_t tail_tiles = (sh.tail + kAfStrip - 1) / kAfStrip, row_blocks = (rows + kBlock - 1) / kBlock;
+  FAN_CHECK(strips * panels + tail_tiles < ((size_t)1 << 30) && row_blocks + cols / kBlock < ((size_t)1 << 30),
+            "adafactor: too many tiles");
+  sh.n_strips = (int)strips;
+  sh.n_panels = (int)panels;
+  sh.n_tiles = (int)(strips * panels);
+  sh.n_tail_tiles = (int)tail_tiles;
+  sh.n_row_blocks = (int)row_blocks;
+  return sh;
+}
+
+void launch_wire_adafactor(int codec, const void* wire, size_t n_s, int n_shards, float* master, bf16_t* lp,
+                           float* fac, float* ab, double* partials, float* words, AdafactorParams p, size_t rows,
+                           size_t cols, size_t n_valid, hipStream_t stream, size_t shard_stride, int max_blocks,
+                           int phases) {
+  FAN_CHECK(wire != nullptr && master != nullptr && fac != nullptr && ab != nullptr && partials != nullptr &&
+                words != nullptr,
+            "wire_adafactor: the wire, master, fac, the scale vector, the partials buffer and the four output words");
+  check_ns(n_s);
+  FAN_CHECK(n_s > 0 && n_shards > 0 && n_valid <= n_s * (size_t)n_shards, "wire_adafactor: n_valid beyond the wire");
+  FAN_CHECK((reinterpret_cast<uintptr_t>(master) | reinterpret_cast<uintptr_t>(partials)) % 16 == 0 &&
+                (lp == nullptr || reinterpret_cast<uintptr_t>(lp) % 16 == 0),
+            "wire_adafactor: master, lp and the partials buffer are 16-byte aligned");
+  const AdafactorShape sh = adafactor_shape(rows, cols, n_valid);
+  const int cap = max_blocks > 0 ? std::min(max_blocks, wire_max_blocks()) : wire_max_blocks();
+  const int grid = std::min(sh.n_tiles + sh.n_tail_tiles, cap);
+  const int col_blocks = (int)((cols + kBlock - 1) / kBlock);
+  const uint8_t* w = (const uint8_t*)wire;
+  FAN_CODEC_SWITCH(codec, {
+    const size_t sb = shard_stride ? shard_stride : wire_shard_bytes(C, n_s);
+    if (phases & 1)
+      hipLaunchKernelGGL((wire_adafactor_stats_kernel<C>), grid, kBlock, 0, stream, w, n_s, sb, sh, p, fac, ab,
+                         partials);
+    if (phases & 2)
+      hipLaunchKernelGGL(adafactor_factors_kernel, sh.n_row_blocks + col_blocks, kBlock, 0, stream, sh, p, fac, ab,
+                         partials);
+    if (phases & 4)
+      hipLaunchKernelGGL(adafactor_rowscale_kernel, sh.n_row_blocks, kBlock, 0, stream, sh, fac, ab, partials);
+    if (phases & 8)
+      hipLaunchKernelGGL((wire_adafactor_rms_kernel<C>), grid, kBlock, 0, stream, w, n_s, sb, sh, p, ab, partials);
+    if (phases & 16) hipLaunchKernelGGL(adafactor_scale_kernel, 1, kBlock, 0, stream, sh, p, partials, words);
+    if (phases & 32) {
+      if (lp)
+        hipLaunchKernelGGL((wire_adafactor_apply_kernel<C, true>), grid, kBlock, 0, stream, w, n_s, sb, sh, p, ab,
+                           words, master, lp);
+      else
+        hipLaunchKernelGGL((wire_adafactor_apply_kernel<C, false>), grid, kBlock, 0, stream, w, n_s, sb, sh, p, ab,
+                           words, master, lp);
+    }
+  });
   FAN_HIP_CHECK(hipGetLastError());
 }
 

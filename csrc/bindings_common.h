@@ -37,6 +37,12 @@ inline fan::LionParams fan_lion_params(const std::vector<double>& s, double grad
   return fan::LionParams{(float)grad_scale, (float)s[0], (float)s[1], (float)s[2], (float)s[3], (float)s[4],
                          (float)s[6], (float)s[5]};
 }
+// AdafactorParams from bfp_oracle.adafactor_scalars (in its order: beta2, omb2, eps1, lr, d in float64, then the f32
+// values decay, wd).
+inline fan::AdafactorParams fan_adafactor_params(const std::vector<double>& s, double grad_scale) {
+  TORCH_CHECK(s.size() == 7, "adafactor: 7 scalars (beta2, omb2, eps1, lr, d, decay, wd)");
+  return fan::AdafactorParams{s[0], s[1], s[2], s[3], s[4], (float)grad_scale, (float)s[6], (float)s[5]};
+}
 // One 8-bit moment plane of a padded bucket of n_pad elements (bfp_format.h launch_wire_adamw_q): contiguous uint8,
 // exactly n_pad * 17 / 16 bytes, 16-byte aligned (a sliced tensor may not be), on `ref`'s device.
 inline uint8_t* fan_moment_plane(const at::Tensor& t, int64_t n_pad, const at::Tensor& ref) {

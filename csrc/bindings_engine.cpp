@@ -253,7 +253,9 @@ void register_engine(pybind11::module_& m) {
               c10::optional<std::vector<double>> adamw, c10::optional<std::vector<double>> lamb, int64_t n_adapt,
               c10::optional<at::Tensor> trust_out, c10::optional<at::Tensor> clip,
               c10::optional<at::Tensor> residual, bool sr, uint64_t sr_seed, c10::optional<at::Tensor> mom_q,
-              c10::optional<at::Tensor> var_q, uint64_t moment_seed, c10::optional<std::vector<double>> lion) {
+              c10::optional<at::Tensor> var_q, uint64_t moment_seed, c10::optional<std::vector<double>> lion,
+              c10::optional<std::vector<double>> adafactor, c10::optional<at::Tensor> fac, int64_t rows,
+              int64_t cols, c10::optional<at::Tensor> adafactor_out) {
              FAN_T_CUDA_CONTIG(grad);
              TORCH_CHECK(grad.scalar_type() == at::kFloat || grad.scalar_type() == at::kBFloat16,
                          "gradients must be f32 or bf16");
@@ -303,7 +305,30 @@ void register_engine(pybind11::module_& m) {
                req.prepacked = prepacked->data_ptr<uint8_t>();
              }
              req.upd.sgd = SgdParams{(float)lr, (float)grad_scale, (float)wd, (float)momentum, nesterov ? 1 : 0};
-             TORCH_CHECK(opt == kOptSgd || opt == kOptAdamW || opt == kOptLion, "opt: 0 (SGD), 1 (AdamW) or 2 (Lion)");
+             TORCH_CHECK(opt == kOptSgd || opt == kOptAdamW || opt == kOptLion || opt == kOptAdafactor,
+                         "opt: 0 (SGD), 1 (AdamW), 2 (Lion) or 3 (Adafactor)");
+             if (opt == kOptAdafactor) {  // (the engine's submit() refuses what the request may not carry)
+               TORCH_CHECK(adafactor.has_value(), "opt: 0 (SGD), 1 (AdamW), 2 (Lion), or 3 (Adafactor) together with "
+                                                  "adafactor=: Adafactor needs its scalars");
+               TORCH_CHECK(!lamb.has_value(), "trust ratio: a flag of AdamW update requests, not of Adafactor");
+               TORCH_CHECK(!(var && var->defined()), "Adafactor keeps no moment plane (mom, var): its state is fac");
+               TORCH_CHECK(fac && fac->defined(), "Adafactor needs its state (fac)");
+               FAN_T_CUDA_CONTIG(*fac);
+               TORCH_CHECK(fac->scalar_type() == at::kFloat && fac->device() == grad.device(),
+                           "fac: float32 on the gradient's device");
+               req.upd.kind = kOptAdafactor;
+               req.upd.adafactor = fan_adafactor_params(*adafactor, grad_scale);
+               req.fac = fac->data_ptr<float>();
+               req.fac_elems = fac->numel();
+               req.af_rows = rows;
+               req.af_cols = cols;
+               if (adafactor_out && adafactor_out->defined()) {
+                 FAN_T_CUDA_CONTIG(*adafactor_out);
+                 TORCH_CHECK(adafactor_out->scalar_type() == at::kFloat && adafactor_out->numel() >= 4,
+                             "adafactor_out: f32[4]");
+                 req.af_words = adafactor_out->data_ptr<float>();
+               }
+             }
              TORCH_CHECK(opt != kOptLion || !(mom_q && mom_q->defined()),
                          "moment_codec bfp8: AdamW only (Lion's one moment plane stays f32)");
              TORCH_CHECK(opt == kOptAdamW || !(mom_q && mom_q->defined()),
@@ -387,7 +412,8 @@ void register_engine(pybind11::module_& m) {
            py::arg("trust_out") = py::none(), py::arg("clip") = py::none(), py::arg("residual") = py::none(),
            py::arg("sr") = false, py::arg("sr_seed") = 0, py::arg("mom_q") = py::none(),
            py::arg("var_q") = py::none(), py::arg("moment_seed") = 0, py::arg("lion") = py::none(),
-           py::call_guard<py::gil_scoped_release>())
+           py::arg("adafactor") = py::none(), py::arg("fac") = py::none(), py::arg("rows") = 0, py::arg("cols") = 0,
+           py::arg("adafactor_out") = py::none(), py::call_guard<py::gil_scoped_release>())
       .def("prepack_shape", [](AllReduceEngine& e, int64_t n) {
         const auto s = e.prepack_shape(n);
         return py::make_tuple(s[0], s[1], s[2]);

@@ -622,6 +622,52 @@ void wire_lion(const at::Tensor& wire, int64_t shard_elems, int64_t n_shards, in
                    (size_t)shard_stride, cw);
 }
 
+// Adafactor (bfp_format.h launch_wire_adafactor): fac = R | C | V is the state, ab / partials / words the request's
+// scratch and output; every buffer is exactly as long as the shape says, so nothing behind it is reachable.
+void wire_adafactor(const at::Tensor& wire, int64_t shard_elems, int64_t n_shards, at::Tensor& master,
+                    const c10::optional<at::Tensor>& lp, at::Tensor& fac, at::Tensor& ab, at::Tensor& partials,
+                    at::Tensor& words, const std::vector<double>& scalars, double grad_scale, int64_t rows,
+                    int64_t cols, int64_t n_valid, int64_t codec, int64_t shard_stride, int64_t max_blocks,
+                    int64_t phases) {
+  FAN_T_CUDA_CONTIG(wire);
+  FAN_T_CUDA_CONTIG(master);
+  FAN_T_CUDA_CONTIG(fac);
+  FAN_T_CUDA_CONTIG(ab);
+  FAN_T_CUDA_CONTIG(partials);
+  FAN_T_CUDA_CONTIG(words);
+  TORCH_CHECK(shard_elems > 0 && shard_elems % 256 == 0 && n_shards > 0, "shard_elems: a positive multiple of 256");
+  TORCH_CHECK(n_valid >= 0 && n_valid <= shard_elems * n_shards, "n_valid beyond the wire region");
+  TORCH_CHECK(rows >= 1 && cols >= 16 && cols % 16 == 0, "adafactor: cols must be a positive multiple of 16, rows >= 1");
+  TORCH_CHECK(rows <= n_valid / cols, "adafactor: rows * cols must not exceed n_valid");
+  const AdafactorShape sh = adafactor_shape((size_t)rows, (size_t)cols, (size_t)n_valid);
+  const int64_t state = rows + cols + (int64_t)sh.tail;
+  TORCH_CHECK(master.scalar_type() == at::kFloat && master.numel() >= n_valid, "master: float32, n_valid elements");
+  TORCH_CHECK(fac.scalar_type() == at::kFloat && fac.numel() == state, "fac: float32[rows + cols + tail = ", state, "]");
+  TORCH_CHECK(ab.scalar_type() == at::kFloat && ab.numel() >= state, "ab: float32[rows + cols + tail]");
+  TORCH_CHECK(partials.scalar_type() == at::kDouble && (size_t)partials.numel() >= sh.partials(),
+              "partials: float64[", sh.partials(), "]");
+  TORCH_CHECK(words.scalar_type() == at::kFloat && words.numel() >= 4, "words: f32[4]");
+  for (const at::Tensor* t : {&wire, (const at::Tensor*)&fac, (const at::Tensor*)&ab, (const at::Tensor*)&partials,
+                              (const at::Tensor*)&words})
+    TORCH_CHECK(t->device() == master.device(), "adafactor: one device");
+  const size_t sb = wire_shard_bytes((int)codec, shard_elems);
+  TORCH_CHECK(shard_stride == 0 || (size_t)shard_stride >= sb, "shard_stride below the packed shard size");
+  TORCH_CHECK(shard_stride % 16 == 0, "shard_stride must keep 16-byte alignment");
+  const size_t need = shard_stride ? (size_t)shard_stride * (n_shards - 1) + sb : sb * n_shards;
+  TORCH_CHECK((size_t)wire.numel() * wire.element_size() >= need, "wire buffer too small");
+  bf16_t* lpp = nullptr;
+  if (lp) {
+    FAN_T_CUDA_CONTIG((*lp));
+    TORCH_CHECK(lp->scalar_type() == at::kBFloat16 && lp->numel() >= n_valid && lp->device() == master.device(),
+                "bad lp weights");
+    lpp = reinterpret_cast<bf16_t*>(lp->data_ptr());
+  }
+  launch_wire_adafactor((int)codec, wire.data_ptr(), (size_t)shard_elems, (int)n_shards, master.data_ptr<float>(), lpp,
+                        fac.data_ptr<float>(), ab.data_ptr<float>(), partials.data_ptr<double>(),
+                        words.data_ptr<float>(), fan_adafactor_params(scalars, grad_scale), (size_t)rows, (size_t)cols,
+                        (size_t)n_valid, fan_stream(), (size_t)shard_stride, (int)max_blocks, (int)phases);
+}
+
 }  // namespace
 
 void register_gemm(pybind11::module_& m) {
@@ -738,6 +784,18 @@ void register_nn(pybind11::module_& m) {
         pybind11::arg("skip_period"), pybind11::arg("master"), pybind11::arg("lp"), pybind11::arg("mom"),
         pybind11::arg("scalars"), pybind11::arg("grad_scale"), pybind11::arg("n_valid"), pybind11::arg("codec"),
         pybind11::arg("shard_stride") = 0, pybind11::arg("clip") = pybind11::none());
+  m.def("adafactor_layout", [](int64_t rows, int64_t cols, int64_t n_valid) {
+    const AdafactorShape sh = adafactor_shape((size_t)rows, (size_t)cols, (size_t)n_valid);
+    return std::vector<int64_t>{kAfPanel, kAfStrip, sh.n_panels, sh.n_strips, sh.n_tail_tiles, (int64_t)sh.col_off(),
+                                (int64_t)sh.row_off(), (int64_t)sh.rms_off(), (int64_t)sh.partials()};
+  }, "{panel rows, strip columns, panels, strips, tail tiles, and the partials buffer's col / row / rms offsets and "
+     "length in doubles} of an Adafactor request");
+  m.def("wire_adafactor", &wire_adafactor, "the Adafactor epilogue of one gathered wire region (six launches)",
+        pybind11::arg("wire"), pybind11::arg("shard_elems"), pybind11::arg("n_shards"), pybind11::arg("master"),
+        pybind11::arg("lp"), pybind11::arg("fac"), pybind11::arg("ab"), pybind11::arg("partials"),
+        pybind11::arg("words"), pybind11::arg("scalars"), pybind11::arg("grad_scale"), pybind11::arg("rows"),
+        pybind11::arg("cols"), pybind11::arg("n_valid"), pybind11::arg("codec"), pybind11::arg("shard_stride") = 0,
+        pybind11::arg("max_blocks") = 0, pybind11::arg("phases") = 63);
 }
 
 void register_planner(pybind11::module_& m) {

@@ -246,6 +246,8 @@ static void update_at(const EngineRequest& req, int codec, const void* wire, siz
                       int skip_period, int64_t off, size_t nv, hipStream_t st, size_t shard_stride = 0) {
   bf16_t* lp = req.lp ? req.lp + off : nullptr;
   FAN_CHECK(!req.upd.trust, "a trust-ratio update is the two-pass epilogue (lamb_region), never a single launch");
+  FAN_CHECK(req.upd.kind != kOptAdafactor, "an Adafactor update is the whole-bucket epilogue (adafactor_region), never "
+                                           "a launch over part of the bucket");
   if (req.moment_q) {
     // the 8-bit planes are passed whole: the region's bucket offset addresses them (and keys the random bytes)
     launch_wire_adamw_q(codec, wire, n_s, n_shards, skip_shard, skip_period, req.master + off, lp, req.mom_q, req.var_q,
@@ -269,6 +271,8 @@ static void update_at(const EngineRequest& req, int codec, const void* wire, siz
 static void reduce_update_at(const EngineRequest& req, int codec, const void* slots, size_t slot_stride, int n_slots,
                              int self_pos, const void* local, int64_t off, size_t nv, const WirePtrs& dst, int n_dst,
                              size_t n_s, bool peers, hipStream_t st) {
+  FAN_CHECK(req.upd.kind != kOptAdafactor, "Adafactor: not with the sharded update (its statistics need the whole "
+                                           "bucket)");
   if (req.upd.kind == kOptAdamW) {
     AdamWParams a = req.upd.adamw;
     a.var += off;
@@ -326,10 +330,34 @@ EpiThunk AllReduceEngine::lamb_region(const EngineRequest& req, const uint8_t* w
   };
 }
 
+EpiThunk AllReduceEngine::adafactor_region(const EngineRequest& req, const uint8_t* wire, int64_t shard_elems,
+                                           int n_shards, size_t shard_stride) {
+  const int c = cfg_.codec;
+  const AdafactorShape sh = adafactor_shape((size_t)req.af_rows, (size_t)req.af_cols, (size_t)req.n_valid);
+  float* ab = reinterpret_cast<float*>(epi_scratch("adafactor_ab", (size_t)req.fac_elems * 4));
+  double* partials = reinterpret_cast<double*>(epi_scratch("adafactor_partials", sh.partials() * 8));
+  float* words = req.af_words ? req.af_words : reinterpret_cast<float*>(epi_scratch("adafactor_words", 16));
+  return [=](hipStream_t es) {
+    launch_wire_adafactor(c, wire, (size_t)shard_elems, n_shards, req.master, req.lp, req.fac, ab, partials, words,
+                          req.upd.adafactor, (size_t)req.af_rows, (size_t)req.af_cols, (size_t)req.n_valid, es,
+                          shard_stride);
+  };
+}
+
 EpiThunk AllReduceEngine::make_epilogue(const EngineRequest& req, const uint8_t* wire, int64_t shard_elems,
                                         int n_shards, int64_t off, int64_t len, int skip_shard, int skip_period) {
   const int c = cfg_.codec;
   const int64_t nv = valid_in(req.n_valid, off, len);
+  if (adafactor(req)) {
+    FAN_CHECK(off == 0 && nv == req.n_valid && skip_shard < 0,
+              "Adafactor: the epilogue must see the whole bucket as one region (its statistics are 2-D)");
+    const EpiThunk upd = adafactor_region(req, wire, shard_elems, n_shards);
+    float* out_sum = req.out_sum;
+    return [=](hipStream_t es) {
+      upd(es);
+      if (out_sum) launch_wire_unpack(c, kF32, wire, out_sum, (size_t)shard_elems, n_shards, es);
+    };
+  }
   if (req.clip_words && nv > 0) {
     // the norm pass of this region, now: the gathered wire is complete in the order of cur_.run at every call site
     // (a clipped request is deferred, so the direct mesh has copied it out of the arena), and the launch runs beside
@@ -630,6 +658,7 @@ std::vector<EpiThunk> AllReduceEngine::run_mesh_direct(P2PComm* d, const EngineL
     // path, and the other two on the epilogue stream.
     if (trust(req) && nv > 0)
       lamb_region(req, Gv, s, N, 0, nv, -1, 0, gstride)(st);
+    else if (adafactor(req)) adafactor_region(req, Gv, s, N, gstride)(st);
     else if (req.update && nv > 0) update_at(req, c, Gv, (size_t)s, N, -1, 0, 0, (size_t)nv, st, gstride);
     if (req.out_sum) launch_wire_unpack_strided(c, kF32, Gv, gstride, req.out_sum, (size_t)s, N, st);
   }
@@ -1109,8 +1138,30 @@ int AllReduceEngine::submit(const EngineRequest& req, hipStream_t producer) {
   FAN_CHECK(req.upd.kind != kOptAdamW || !req.update || req.moment_q ||
                 (req.mom != nullptr && req.upd.adamw.var != nullptr),
             "AdamW needs both moment planes");
-  FAN_CHECK(req.upd.kind == kOptSgd || req.upd.kind == kOptAdamW || req.upd.kind == kOptLion,
-            "unknown optimizer kind (0 SGD, 1 AdamW, 2 Lion)");
+  FAN_CHECK(req.upd.kind == kOptSgd || req.upd.kind == kOptAdamW || req.upd.kind == kOptLion ||
+                req.upd.kind == kOptAdafactor,
+            "unknown optimizer kind (0 SGD, 1 AdamW, 2 Lion, 3 Adafactor)");
+  if (req.upd.kind == kOptAdafactor) {
+    // The statistics are sums over the whole matrix, so only a schedule whose epilogue sees the bucket as one region of
+    // equal shards carries the request (refused before the request takes a slot).
+    FAN_CHECK(req.update, "Adafactor: update requests only");
+    FAN_CHECK(req.mom == nullptr && req.upd.adamw.var == nullptr, "Adafactor keeps no moment plane (mom, var): its "
+                                                                  "state is fac");
+    FAN_CHECK(!req.upd.trust, "trust ratio: a flag of AdamW update requests, not of Adafactor");
+    FAN_CHECK(!req.moment_q, "moment_codec bfp8: AdamW update requests only (Adafactor's state is fac)");
+    FAN_CHECK(req.clip_words == nullptr, "clip: not with Adafactor (its direction does not depend on the gradient's "
+                                         "scale, and it clips its own update)");
+    FAN_CHECK(cfg_.algo == 0, "Adafactor: mesh schedule only (the ring's regions split rows)");
+    FAN_CHECK(!shard_upd_, "Adafactor: not with the sharded update (shard_update)");
+    FAN_CHECK(!cfg_.compat_owner_fp32, "Adafactor: not with compat_owner_fp32");
+    FAN_CHECK(req.n_valid > 0 && layout(req.n_valid, req.layout_shard, req.layout_chunks).chunks <= 1,
+              "Adafactor: not with a chunked layout (layout_chunks > 1, or a bucket above chunk_elems)");
+    FAN_CHECK(req.af_rows >= 1 && req.af_cols >= 16 && req.af_cols % 16 == 0,
+              "Adafactor: cols must be a positive multiple of 16 (a wire group may not cross rows) and rows >= 1");
+    FAN_CHECK(req.af_rows <= req.n_valid / req.af_cols, "Adafactor: rows * cols must not exceed n_valid");
+    FAN_CHECK(req.fac != nullptr && req.fac_elems == req.af_rows + req.af_cols + (req.n_valid - req.af_rows * req.af_cols),
+              "Adafactor: fac holds exactly rows + cols + tail f32 elements");
+  }
   if (req.upd.kind == kOptLion) {
     // One f32 moment plane, where SGD's momentum travels (refused before the request takes a slot).
     FAN_CHECK(!req.update || req.mom != nullptr, "Lion needs its moment plane (mom)");

@@ -135,12 +135,16 @@ enum VerifySite : uint32_t {
 // offsets the planes offsets adamw.var with them (update_at in engine.cpp).
 // trust (kOptAdamW only): the layer-wise trust ratio (LAMB) — the update is then the two-pass epilogue of
 // bfp_format.h (launch_wire_lamb_*) with `lamb`'s scalars, and adamw.var still names the second-moment plane.
-enum OptKind : int { kOptSgd = 0, kOptAdamW = 1, kOptLion = 2 };
+// kOptAdafactor: the factored-second-moment epilogue of bfp_format.h launch_wire_adafactor with `adafactor`'s scalars;
+// its state is EngineRequest::fac, it has no moment plane, and only the schedules whose epilogue sees the whole bucket
+// as one region of equal shards carry it (submit() refuses the rest).
+enum OptKind : int { kOptSgd = 0, kOptAdamW = 1, kOptLion = 2, kOptAdafactor = 3 };
 struct UpdateParams {
   int kind = kOptSgd;
   SgdParams sgd{};
   AdamWParams adamw{};
   LionParams lion{};
+  AdafactorParams adafactor{};
   bool trust = false;
   LambParams lamb{};
 };
@@ -168,6 +172,13 @@ struct EngineRequest {
   // writes (nullptr: a per-slot scratch of the engine holds them)
   int64_t n_adapt = -1;
   float* trust_out = nullptr;
+  // Adafactor requests (upd.kind == kOptAdafactor): flat elements [0, af_rows * af_cols) are the adapted row-major
+  // matrix, the rest up to n_valid its tail; fac = R[af_rows] | C[af_cols] | V[tail] is the f32 state, fac_elems its
+  // length (checked by submit()); af_words: four f32 device words {scale_mat, rms_mat, scale_tail, rms_tail} the
+  // request writes (nullptr: a per-slot scratch of the engine holds them).
+  float* fac = nullptr;
+  int64_t fac_elems = 0, af_rows = 0, af_cols = 0;
+  float* af_words = nullptr;
   // global-norm clipping: the four f32 device words {coef, total, max_norm, nonfinite} of the request's clip group
   // (bfp_format.h launch_clip_coef). Non-null: an update request that must be deferred; its communication phase ends
   // with the norm pass over its gathered wire, and commit_group() — never commit() — enqueues its update, which
@@ -380,6 +391,12 @@ class AllReduceEngine {
   // pass-2 thunk in cur_.apply; submit() appends the ratio thunk and those after the schedule's own thunks.
   EpiThunk lamb_region(const EngineRequest& req, const uint8_t* wire, int64_t shard_elems, int n_shards, int64_t off,
                        int64_t nv, int skip_shard, int skip_period, size_t shard_stride = 0);
+  bool adafactor(const EngineRequest& req) const { return req.update && req.upd.kind == kOptAdafactor; }
+  // The Adafactor epilogue of the request being built over its whole gathered wire (n_shards equal shards from bucket
+  // element 0; submit() has refused every schedule that splits the bucket): one thunk of six launches, its scale
+  // vector and fp64 partials in per-slot scratch.
+  EpiThunk adafactor_region(const EngineRequest& req, const uint8_t* wire, int64_t shard_elems, int n_shards,
+                            size_t shard_stride = 0);
   bool sharded(const EngineRequest& req) const {  // the request runs the sharded update (EngineConfig::shard_update)
     return shard_upd_ && req.update && req.out_sum == nullptr && req.lp != nullptr;
   }

@@ -39,7 +39,7 @@ class TrainConfig:
     lr: float = 0.1
     momentum: float = 0.0
     weight_decay: float = 0.0
-    optimizer: str = "sgd"         # sgd | adamw | lion
+    optimizer: str = "sgd"         # sgd | adamw | lion | adafactor
     trust_ratio: bool = False      # adamw: layer-wise trust ratio (LAMB)
     clip_grad_norm: float = 0.0    # > 0: clip the reduced gradient of all layers to this 2-norm (0: off)
     error_feedback: bool = False   # BFP mesh: each encoder keeps what it drops and adds it to the next step's input
@@ -63,7 +63,10 @@ class TrainConfig:
         return dataclasses.asdict(self)
 
     def betas(self):
-        """(beta1, beta2) with the optimizer's defaults filled in: AdamW's (0.9, 0.999), Lion's (0.9, 0.99)."""
+        """(beta1, beta2) with the optimizer's defaults filled in: AdamW's (0.9, 0.999), Lion's (0.9, 0.99); None for
+        Adafactor, which has none (a --beta1 / --beta2 given with it is passed on and refused)."""
+        if self.optimizer == "adafactor" and self.beta1 is None and self.beta2 is None:
+            return None
         d1, d2 = (0.9, 0.99) if self.optimizer == "lion" else (0.9, 0.999)
         return (d1 if self.beta1 is None else self.beta1, d2 if self.beta2 is None else self.beta2)
 
@@ -85,10 +88,12 @@ def add_named_flags(ap: argparse.ArgumentParser):
     ap.add_argument("--lr", type=float, default=d.lr)
     ap.add_argument("--momentum", type=float, default=d.momentum)
     ap.add_argument("--weight-decay", type=float, default=d.weight_decay)
-    ap.add_argument("--optimizer", default=d.optimizer, choices=["sgd", "adamw", "lion"],
+    ap.add_argument("--optimizer", default=d.optimizer, choices=["sgd", "adamw", "lion", "adafactor"],
                     help="weight update fused into the all-reduce epilogue; lion: sign of the interpolated momentum "
                          "with decoupled decay, one f32 moment plane (SGD-momentum's bytes and state); not with "
-                         "--momentum, --trust-ratio or --moment-codec bfp8")
+                         "--momentum, --trust-ratio or --moment-codec bfp8; adafactor: factored second moment "
+                         "(rows + cols floats of state per layer), absolute --lr, update clipping at 1; mesh schedule "
+                         "only, not with --momentum, --trust-ratio, --clip-grad-norm or --moment-codec bfp8")
     ap.add_argument("--trust-ratio", action="store_true",
                     help="AdamW: scale each layer's step by ||w|| / ||update|| (LAMB; two-pass epilogue)")
     ap.add_argument("--clip-grad-norm", type=float, default=d.clip_grad_norm,

@@ -33,6 +33,7 @@ class LayerBucket:
     lp: torch.Tensor | None
     mom: torch.Tensor | None
     var: torch.Tensor | None = None  # AdamW's second moment (mom is then the first)
+    fac: torch.Tensor | None = None  # Adafactor's state R[cin] | C[cout] | V[bias] (allocated by the trainer)
 
     @property
     def w_master(self):

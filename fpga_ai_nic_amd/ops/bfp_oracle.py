@@ -687,3 +687,125 @@ def lamb_apply(w: np.ndarray, m2: np.ndarray, v2: np.ndarray, scalars: LambScala
         r = _lamb_direction(w, np.asarray(m2, np.float32), np.asarray(v2, np.float32), scalars)
         scale = np.where(np.arange(w.size) < n_adapt, np.float32(words[0]), np.float32(words[1])).astype(np.float32)
         return (-scale.astype(np.float64) * r.astype(np.float64) + w.astype(np.float64)).astype(np.float32)
+
+
+# --------------------------------------------------------------------------- Adafactor (factored second moment)
+# A bucket is the adapted matrix [0, rows * cols), row-major, then a tail [rows * cols, n_valid) (the bias segment).
+# State: one f32 vector fac = R[rows] | C[cols] | V[tail]; no first moment, no relative step, no parameter scaling.
+class AdafactorScalars(tuple):
+    """Adafactor's scalars of one update (``adafactor_scalars``). ``beta2``, ``omb2``, ``eps1``, ``lr`` and ``d`` enter
+    float64 expressions and stay float64; ``decay`` and ``wd`` are f32 values (``wd`` rides along because the update
+    tests it against 0, as in Lion)."""
+    FIELDS = ("beta2", "omb2", "eps1", "lr", "d", "decay", "wd")
+
+    def __new__(cls, *vals):
+        assert len(vals) == len(cls.FIELDS)
+        return super().__new__(cls, [float(x) for x in vals[:5]] + [float(np.float32(x)) for x in vals[5:]])
+
+    def __getattr__(self, name):
+        try:
+            return self[self.FIELDS.index(name)]
+        except ValueError:
+            raise AttributeError(name) from None
+
+    def kernel_args(self):
+        """The seven scalars the native launchers take."""
+        return [float(x) for x in self]
+
+
+def adafactor_scalars(lr: float, wd: float, step: int, clip_threshold: float = 1.0) -> AdafactorScalars:
+    """The scalars of update ``step`` (1-based), in float64: beta2 = 1 - step^-0.8 (0 at step 1, so a zero state is
+    the right start), omb2 = 1 - beta2, eps1 = 1e-30, the absolute ``lr``, the update-clipping threshold d, and the
+    f32 values decay = 1 - lr * wd and wd."""
+    lr, wd, d = float(lr), float(wd), float(clip_threshold)
+    if int(step) != step or int(step) < 1:
+        raise ValueError(f"Adafactor: step is the 1-based update count, got {step!r}")
+    if not (math.isfinite(lr) and math.isfinite(wd)):
+        raise ValueError(f"Adafactor: lr and weight_decay must be finite, got {(lr, wd)}")
+    if not (math.isfinite(d) and d > 0.0):
+        raise ValueError(f"Adafactor: clip_threshold must be finite and positive, got {clip_threshold!r}")
+    beta2 = 1.0 - float(int(step)) ** -0.8
+    return AdafactorScalars(beta2, 1.0 - beta2, 1e-30, lr, d, 1.0 - lr * wd, wd)
+
+
+def _sum64(x) -> float:
+    """Exactly rounded float64 sum (math.fsum); a non-finite term gives numpy's non-finite sum instead of an error."""
+    x = np.asarray(x, np.float64)
+    if np.isfinite(x).all():
+        return math.fsum(x)
+    with np.errstate(invalid="ignore", over="ignore"):
+        return float(np.sum(x))
+
+
+def adafactor_stats(g: np.ndarray, rows: int, cols: int, n_valid: int, grad_scale: float = 1.0, eps1: float = 1e-30):
+    """g' = f32(g * grad_scale) and s = (double)g' * g' + eps1 per element; the row and column means of s over the
+    matrix and s of the tail. Returns (g', rowmean[rows], colmean[cols], s_tail), the last three float64."""
+    n_adapt = rows * cols
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        g = (np.asarray(g, np.float32)[:n_valid] * np.float32(grad_scale)).astype(np.float32)
+        s = g.astype(np.float64) ** 2 + np.float64(eps1)
+    S = s[:n_adapt].reshape(rows, cols)
+    rowmean = np.array([_sum64(S[i]) for i in range(rows)], np.float64) / cols
+    colmean = np.array([_sum64(S[:, j]) for j in range(cols)], np.float64) / rows
+    return g, rowmean, colmean, s[n_adapt:]
+
+
+def adafactor_factors(fac: np.ndarray, rowmean, colmean, s_tail, scalars: AdafactorScalars):
+    """The EMA of the three state segments (float64 expression, rounded once) and the scale vectors: fac' = R' | C' | V'
+    and ab = a | b | a_tail with a_i = f32(1 / sqrt(R'_i / meanR)), meanR the float64 mean of the rounded R',
+    b_j = f32(1 / sqrt(C'_j)), a_k = f32(1 / sqrt(V'_k))."""
+    s = scalars
+    rows = len(rowmean)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore", under="ignore"):
+        new = (s.beta2 * np.asarray(fac, np.float32).astype(np.float64)
+               + s.omb2 * np.concatenate([rowmean, colmean, s_tail])).astype(np.float32)
+        mean_r = _sum64(new[:rows]) / rows
+        den = new.astype(np.float64)
+        den[:rows] = den[:rows] / mean_r
+        ab = (1.0 / np.sqrt(den)).astype(np.float32)
+    return new, ab
+
+
+def adafactor_rms(g: np.ndarray, ab: np.ndarray, rows: int, cols: int):
+    """The direction u (matrix: (g * a_i) * b_j, two f32 products in that order; tail: g * a_k) of the scaled gradient
+    ``g`` of ``adafactor_stats``, and the float64 sums of its exact squares. Returns (u, sum_mat, sum_tail)."""
+    n_adapt = rows * cols
+    ab = np.asarray(ab, np.float32)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        um = (g[:n_adapt].reshape(rows, cols) * ab[:rows, None]).astype(np.float32) * ab[None, rows:rows + cols]
+        u = np.concatenate([um.astype(np.float32).reshape(-1), (g[n_adapt:] * ab[rows + cols:]).astype(np.float32)])
+        sq = u.astype(np.float64) ** 2
+    return u, _sum64(sq[:n_adapt]), _sum64(sq[n_adapt:])
+
+
+def adafactor_scale(sum_mat: float, n_mat: int, sum_tail: float, n_tail: int, scalars: AdafactorScalars) -> np.ndarray:
+    """The four f32 words {scale_mat, rms_mat, scale_tail, rms_tail}: rms = sqrt(sum / count) (0 for an empty tensor),
+    scale = f32(lr / max(1, rms / d)), float64 throughout. A NaN rms gives a NaN scale."""
+    out = []
+    for tot, n in ((sum_mat, n_mat), (sum_tail, n_tail)):
+        rms = math.sqrt(tot / n) if n > 0 else 0.0
+        q = rms / scalars.d
+        out += [scalars.lr / (q if q > 1.0 or q != q else 1.0), rms]
+    with np.errstate(over="ignore"):
+        return np.array(out, np.float64).astype(np.float32)
+
+
+def adafactor_apply(w: np.ndarray, u: np.ndarray, words: np.ndarray, n_adapt: int, scalars: AdafactorScalars):
+    """w' = fma(-scale, u, wd != 0 ? w * decay : w), scale = words[0] on the matrix and words[2] on the tail."""
+    w = np.asarray(w, np.float32)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        scale = np.where(np.arange(w.size) < n_adapt, np.float32(words[0]), np.float32(words[2])).astype(np.float64)
+        base = (w * np.float32(scalars.decay)).astype(np.float32) if scalars.wd != 0 else w
+        return (-scale * np.asarray(u, np.float32).astype(np.float64) + base.astype(np.float64)).astype(np.float32)
+
+
+def adafactor(w: np.ndarray, g: np.ndarray, fac: np.ndarray, rows: int, cols: int, scalars: AdafactorScalars,
+              grad_scale: float = 1.0):
+    """One whole Adafactor update of a bucket of ``len(w)`` valid elements from the functions above.
+    Returns (w', fac', words, ab)."""
+    n = len(w)
+    g2, rowmean, colmean, s_tail = adafactor_stats(g, rows, cols, n, grad_scale, scalars.eps1)
+    fac2, ab = adafactor_factors(fac, rowmean, colmean, s_tail, scalars)
+    u, sm, st = adafactor_rms(g2, ab, rows, cols)
+    words = adafactor_scale(sm, rows * cols, st, n - rows * cols, scalars)
+    return adafactor_apply(w, u, words, rows * cols, scalars), fac2, words, ab

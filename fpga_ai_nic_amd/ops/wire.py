@@ -330,6 +330,88 @@ def lion(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Tens
             lp.view(-1)[lo:hi].copy_(master.view(-1)[lo:hi].to(lp.dtype))
 
 
+def adafactor_check(fac, rows, cols, n_valid, ref: torch.Tensor | None = None, device=None) -> int:
+    """Validate an Adafactor request's shape and state: ``cols`` a multiple of 16 (a wire group may not cross rows),
+    ``rows * cols <= n_valid``, ``fac`` a contiguous f32 tensor of exactly ``rows + cols + tail`` elements on the
+    device of ``ref`` / ``device``. Returns the tail length ``n_valid - rows * cols``."""
+    if rows is None or cols is None:
+        raise ValueError("Adafactor needs the adapted matrix's shape: rows and cols")
+    rows, cols = int(rows), int(cols)
+    if rows < 1 or cols < 16 or cols % 16:
+        raise ValueError(f"Adafactor: cols must be a positive multiple of 16 and rows >= 1, got {rows} x {cols}")
+    if rows * cols > n_valid:
+        raise ValueError(f"Adafactor: rows * cols = {rows * cols} exceeds n_valid = {n_valid}")
+    tail = n_valid - rows * cols
+    if fac is None:
+        raise ValueError("Adafactor needs its state: fac (f32, rows + cols + tail elements, zeroed before step 1)")
+    if fac.dtype != torch.float32 or not fac.is_contiguous():
+        raise ValueError(f"Adafactor: fac must be a contiguous float32 tensor, got {fac.dtype}"
+                         f"{'' if fac.is_contiguous() else ', not contiguous'}")
+    if fac.numel() != rows + cols + tail:
+        raise ValueError(f"Adafactor: fac must hold exactly rows + cols + tail = {rows + cols + tail} elements, got "
+                         f"{fac.numel()}")
+    dev = ref.device if ref is not None else (torch.device(device) if device is not None else None)
+    if dev is not None and (fac.device.type != dev.type or (
+            dev.type == "cuda" and dev.index not in (None, fac.device.index))):
+        raise ValueError(f"Adafactor: fac must be on the device {dev}, got {fac.device}")
+    return tail
+
+
+def adafactor_layout(rows: int, cols: int, n_valid: int) -> dict:
+    """The native kernels' tiling of an Adafactor request: ``panel`` rows by ``strip`` columns per tile, the tile
+    counts, and the offsets (``col``, ``row``, ``rms``) and ``length`` in doubles of the fp64 partials buffer
+    (col[panels][cols], row[strips][rows], rms[tiles + tail tiles])."""
+    keys = ("panel", "strip", "panels", "strips", "tail_tiles", "col", "row", "rms", "length")
+    return dict(zip(keys, _ext.require().adafactor_layout(int(rows), int(cols), int(n_valid))))
+
+
+def adafactor(wire: torch.Tensor, shard_elems: int, n_shards: int, master: torch.Tensor, fac: torch.Tensor, *, codec,
+              rows: int, cols: int, scalars: O.AdafactorScalars, lp: torch.Tensor | None = None,
+              grad_scale: float = 1.0, n_valid: int | None = None, words: torch.Tensor | None = None,
+              shard_stride: int = 0, ab: torch.Tensor | None = None, partials: torch.Tensor | None = None,
+              max_blocks: int = 0, phases: int = 63):
+    """Decode + Adafactor in place (``bfp_oracle.adafactor``'s arithmetic) over one gathered wire region: the bucket's
+    first ``rows * cols`` elements are the adapted row-major matrix, the rest up to ``n_valid`` its tail. ``fac`` =
+    R[rows] | C[cols] | V[tail] is the state (f32, zeroed before step 1, updated in place), ``scalars`` the update's
+    ``bfp_oracle.adafactor_scalars``; lp = bf16(master). ``words`` (f32[4], optional) receives {scale_mat, rms_mat,
+    scale_tail, rms_tail} without a host sync. On the GPU six launches (csrc/bfp/bfp_format.h launch_wire_adafactor);
+    ``ab`` (f32[rows + cols + tail], the scale vectors a | b | a_tail) and ``partials`` (float64,
+    :func:`adafactor_layout`) are its scratch, allocated here unless given; ``max_blocks`` caps the tiled launches'
+    grids and ``phases`` masks the launches (probes and tests)."""
+    c = codec_id(codec)
+    if not isinstance(scalars, O.AdafactorScalars):
+        raise TypeError(f"wire.adafactor takes bfp_oracle.adafactor_scalars, got {type(scalars).__name__}")
+    n_valid = master.numel() if n_valid is None else int(n_valid)
+    tail = adafactor_check(fac, rows, cols, n_valid, ref=master)
+    rows, cols = int(rows), int(cols)
+    if master.is_cuda:
+        if ab is None:
+            ab = torch.empty(rows + cols + tail, dtype=torch.float32, device=master.device)
+        if partials is None:
+            partials = torch.empty(adafactor_layout(rows, cols, n_valid)["length"], dtype=torch.float64,
+                                   device=master.device)
+        if words is None:
+            words = torch.empty(4, dtype=torch.float32, device=master.device)
+        _ext.require().wire_adafactor(wire, int(shard_elems), int(n_shards), master, lp, fac, ab, partials, words,
+                                      scalars.kernel_args(), float(grad_scale), rows, cols, n_valid, c,
+                                      int(shard_stride), int(max_blocks), int(phases))
+        return
+    sb = O.shard_bytes(c, shard_elems)
+    raw = _np_u8(wire)
+    if shard_stride:
+        raw = np.concatenate([raw[s * shard_stride: s * shard_stride + sb] for s in range(n_shards)])
+    g = O.unpack(raw, shard_elems * n_shards, shard_elems, c)[:n_valid]
+    w = master.view(-1).numpy()
+    w[:n_valid], fac.view(-1).numpy()[:], words_np, ab_np = O.adafactor(w[:n_valid], g, fac.view(-1).numpy(), rows,
+                                                                        cols, scalars, grad_scale)
+    if words is not None:
+        words.view(-1)[:4] = torch.from_numpy(words_np)
+    if ab is not None:
+        ab.view(-1)[:ab_np.size] = torch.from_numpy(ab_np)
+    if lp is not None:
+        lp.view(-1)[:n_valid].copy_(master.view(-1)[:n_valid].to(lp.dtype))
+
+
 def moment_plane(n_pad: int, device) -> torch.Tensor:
     """A zeroed 8-bit moment plane (the zero state) of a padded bucket of ``n_pad`` elements: uint8,
     ``n_pad * 17 / 16`` bytes (``bfp_oracle.moment_plane_bytes``)."""

@@ -66,7 +66,7 @@ def _round_up(a, b):
     return _cdiv(a, b) * b
 
 
-OPTIMIZERS = ("sgd", "adamw", "lion")
+OPTIMIZERS = ("sgd", "adamw", "lion", "adafactor")
 DEFAULT_BETAS = {"sgd": (0.9, 0.999), "adamw": (0.9, 0.999), "lion": (0.9, 0.99)}
 
 
@@ -232,6 +232,40 @@ def lion_request(mom, var, *, lr, weight_decay, momentum, nesterov, betas, trust
     return wire.O.lion_scalars(lr, weight_decay, betas[0], betas[1])
 
 
+def adafactor_request(fac, rows, cols, n_valid, *, lr, weight_decay, step, clip_threshold=1.0, mom=None, var=None,
+                      momentum=0.0, nesterov=False, betas=None, trust_ratio=False, moment_codec="f32", clip=None,
+                      algo="mesh", chunks=1, sharded=False, compat_owner_fp32=False, device=None):
+    """Validate one ``opt="adafactor"`` request; its ``bfp_oracle.AdafactorScalars``. ``fac`` = R | C | V is the one
+    state tensor (``wire.adafactor_check``), ``step`` the bucket's 1-based update count. There is no moment plane, no
+    betas (beta2 follows the step), no trust ratio and no clip group; the statistics are sums over the whole matrix, so
+    only a schedule whose epilogue sees the bucket as one region of equal shards carries the request."""
+    if mom is not None or var is not None:
+        raise ValueError("Adafactor keeps no moment plane: mom and var must be None (its state is fac)")
+    if momentum or nesterov:
+        raise ValueError("momentum / nesterov belong to SGD: Adafactor has no first moment")
+    if betas is not None:
+        raise ValueError("betas belong to AdamW and Lion: Adafactor's beta2 = 1 - step^-0.8 follows the step")
+    if trust_ratio:
+        raise ValueError("trust_ratio is a flag of opt='adamw' (a trust ratio on Adafactor is not provided)")
+    if moment_codec != "f32":
+        raise ValueError("moment_codec='bfp8': AdamW only (Adafactor's state is rows + cols + tail floats already)")
+    if clip is not None:
+        raise ValueError("clip / max_grad_norm: not with Adafactor (its direction is invariant to the gradient's scale "
+                         "up to eps1, and it clips its own update: a clip group buys nothing)")
+    if algo != "mesh":
+        raise ValueError("Adafactor: mesh schedule only (the ring's regions split rows)")
+    if chunks > 1:
+        raise ValueError("Adafactor: not with a chunked layout (a bucket above chunk_elems)")
+    if sharded:
+        raise ValueError("Adafactor: not with the sharded update (shard_update)")
+    if compat_owner_fp32:
+        raise ValueError("Adafactor: not with compat_owner_fp32")
+    if step is None:
+        raise ValueError("Adafactor needs step, the bucket's 1-based update count")
+    wire.adafactor_check(fac, rows, cols, n_valid, device=device)
+    return wire.O.adafactor_scalars(lr, weight_decay, step, clip_threshold)
+
+
 def adamw_request(opt, mom, var, *, lr, weight_decay, momentum, nesterov, betas, eps, step, trust_ratio=False,
                   n_adapt=None, n_valid=None, device=None):
     """Validate one request's optimizer arguments; the step's ``bfp_oracle.AdamWScalars`` for ``opt="adamw"``
@@ -241,6 +275,8 @@ def adamw_request(opt, mom, var, *, lr, weight_decay, momentum, nesterov, betas,
     elements; the scalars are then ``bfp_oracle.LambScalars``."""
     if opt not in OPTIMIZERS:
         raise ValueError(f"unknown optimizer {opt!r} (one of {OPTIMIZERS})")
+    if opt == "adafactor":  # no moment planes, no betas: :func:`adafactor_request` validates it and gives its scalars
+        return None
     if opt == "lion":
         if n_adapt is not None:
             raise ValueError("n_adapt belongs to trust_ratio=True, a flag of opt='adamw'")
@@ -497,7 +533,9 @@ class CompressedAllReduce:
                       n_adapt: int | None = None, trust_out: torch.Tensor | None = None,
                       clip: torch.Tensor | None = None, residual: torch.Tensor | None = None,
                       sr_seed: int | None = None, moment_codec: str = "f32",
-                      moment_seed: int | None = None) -> Handle:
+                      moment_seed: int | None = None, fac: torch.Tensor | None = None, rows: int | None = None,
+                      cols: int | None = None, clip_threshold: float = 1.0,
+                      adafactor_out: torch.Tensor | None = None) -> Handle:
         """All-reduce ``grad`` (flat, padded to ``layout(n).n_pad``) and apply SGD to ``master`` (+bf16 ``lp``).
         ``opt="adamw"``: AdamW instead, ``mom`` / ``var`` the first / second moment planes (both required), ``step``
         the bucket's 1-based update count. ``trust_ratio`` (AdamW): scale the step of the bucket's first ``n_adapt``
@@ -516,8 +554,24 @@ class CompressedAllReduce:
         by ``wire.adamw_q`` under the request seed ``moment_seed``, on every schedule; not with ``trust_ratio``.
         ``opt="lion"``: Lion (``bfp_oracle.lion``), ``mom`` its one f32 moment plane (required; no ``var``, ``step``
         ignored), on every schedule and the sharded update; no ``trust_ratio``, no ``moment_codec="bfp8"``. ``betas``
-        left unset: (0.9, 0.999) for AdamW, (0.9, 0.99) for Lion."""
+        left unset: (0.9, 0.999) for AdamW, (0.9, 0.99) for Lion. ``opt="adafactor"``: Adafactor with a factored second
+        moment (``bfp_oracle.adafactor``): the bucket's first ``rows * cols`` elements are the adapted row-major matrix,
+        the rest its tail; ``fac`` (f32, ``rows + cols + tail``, zeroed before step 1) is the state, ``step`` the
+        1-based update count, ``clip_threshold`` the update-clipping threshold d, ``adafactor_out`` (4 f32, optional)
+        receives {scale_mat, rms_mat, scale_tail, rms_tail}. Mesh schedule, one chunk; no moment plane, ``betas``,
+        ``trust_ratio``, ``clip`` or sharded update (:func:`adafactor_request`)."""
         clip_request(clip, defer, self.device)
+        af = None
+        if opt == "adafactor":
+            n_valid = int(n_valid if n_valid is not None else master.numel())
+            af = adafactor_request(fac, rows, cols, n_valid, lr=lr, weight_decay=weight_decay, step=step,
+                                   clip_threshold=clip_threshold, mom=mom, var=var, momentum=momentum,
+                                   nesterov=nesterov, betas=betas, trust_ratio=trust_ratio, moment_codec=moment_codec,
+                                   clip=clip, algo=self.algo, chunks=self.layout(n_valid).chunks,
+                                   sharded=bool(getattr(self, "shard_update", False)),
+                                   compat_owner_fp32=self.compat_owner_fp32, device=self.device)
+        elif fac is not None or rows is not None or cols is not None or adafactor_out is not None:
+            raise ValueError("fac / rows / cols / adafactor_out belong to opt='adafactor'")
         if clip is not None and self.compat_owner_fp32 and self.algo == "ring":
             raise ValueError("clip: not with compat_owner_fp32 (the owner's slices would be updated from another "
                              "gradient than the one the norm was taken over)")
@@ -543,6 +597,12 @@ class CompressedAllReduce:
         cl = None if clip is None else dict(words=clip.view(-1), partials=None, count=0, norm=True)
 
         def update(G, shard, n_shards, off, length, nv, codec, skip=(-1, 0)):
+            if af is not None:  # the whole bucket as one region (adafactor_request refused the rest)
+                assert off == 0 and nv == n_valid and skip[0] < 0
+                wire.adafactor(G, shard, n_shards, master.view(-1), fac, codec=codec, rows=rows, cols=cols, scalars=af,
+                               lp=None if lp is None else lp.view(-1), grad_scale=grad_scale, n_valid=n_valid,
+                               words=adafactor_out)
+                return
             if cl is not None and cl["norm"]:  # the norm pass over this region (at the tail of the comm phase)
                 cl["count"] += wire.sumsq(G, shard, n_shards, codec=codec, partials=cl["partials"],
                                           partials_base=cl["count"], n_valid=nv, skip_shard=skip[0],
@@ -929,8 +989,8 @@ def uncompressed_allreduce_sgd(transport: Transport, grad, master, lp=None, mom=
     if trust_ratio:
         raise ValueError("trust_ratio belongs to the compressed engines' two-pass epilogue; the uncompressed baseline "
                          "has a single update kernel")
-    if opt == "lion":
-        raise ValueError("opt='lion' belongs to the compressed engines' epilogues; the uncompressed baseline offers "
+    if opt in ("lion", "adafactor"):
+        raise ValueError(f"opt={opt!r} belongs to the compressed engines' epilogues; the uncompressed baseline offers "
                          "SGD and AdamW")
     scalars = adamw_request(opt, mom, var, lr=lr, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov,
                             betas=betas, eps=eps, step=step)

@@ -129,7 +129,8 @@ class DataParallelTrainer:
         8 layers; ``fused_update`` is off (the GEMM epilogue cannot wait for the group); not with a sharded-update
         engine. With any ``optimizer`` and with ``trust_ratio``.
 
-        ``optimizer``: 'sgd', 'adamw' or 'lion'. AdamW (``betas``, ``eps``; the model holds the second-moment planes,
+        ``optimizer``: 'sgd', 'adamw', 'lion' or 'adafactor'. AdamW (``betas``, ``eps``; the model holds the
+        second-moment planes,
         ``MLP(..., adam=True)``). AdamW runs in the engine's decode + update epilogue — not in the bwd-weight GEMM's,
         so ``fused_update`` is off with it — with ``opt_step``, the 1-based update count, advanced once per
         ``backward_pass``. ``trust_ratio`` (AdamW): the layer-wise trust ratio (LAMB) — each layer's weight matrix
@@ -140,6 +141,12 @@ class DataParallelTrainer:
         momentum=True)`` — SGD-momentum's planes and bytes, in the engine's epilogue like AdamW, so ``fused_update`` is
         off with it; with ``max_grad_norm``, ``error_feedback``, ``stochastic_rounding`` and a sharded-update engine,
         not with ``trust_ratio`` or ``moment_codec='bfp8'``. ``betas`` left unset: (0.9, 0.999) for AdamW.
+        'adafactor': Adafactor with a factored second moment (``bfp_oracle.adafactor``: absolute ``lr``, no first
+        moment, update clipping at 1), in the engine's epilogue, so ``fused_update`` is off with it; one state tensor
+        ``fac`` = R[cin] | C[cout] | V[bias] per layer (allocated here, zeroed), ``opt_step`` its update count,
+        ``adafactor_words`` ([L, 4] f32 on the model's device) every layer's {scale_mat, rms_mat, scale_tail, rms_tail}
+        of the last step; mesh schedule only, not with ``betas``, ``max_grad_norm``, ``trust_ratio``, ``momentum`` or a
+        sharded-update engine.
 
         ``fused_update`` (default env FAN_FUSED_UPDATE, else on): with a single-rank engine (world 1, requests
         inline: the all-reduce of one rank is the identity) and the GEMM-encoded wire, the bwd-weight GEMM's epilogue
@@ -166,6 +173,8 @@ class DataParallelTrainer:
         self.lr, self.wd, self.momentum, self.nesterov = lr, weight_decay, momentum, nesterov
         if optimizer not in OPTIMIZERS:
             raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
+        if optimizer == "adafactor" and betas is not None:
+            raise ValueError("betas belong to AdamW and Lion: Adafactor's beta2 = 1 - step^-0.8 follows the step")
         betas = resolve_betas(optimizer, betas)
         self.optimizer, self.betas, self.eps = optimizer, (float(betas[0]), float(betas[1])), float(eps)
         self.opt_step = 0  # updates applied so far (AdamW's bias correction; checkpointed)
@@ -186,6 +195,28 @@ class DataParallelTrainer:
             if any(l.var is not None for l in model.layers):
                 raise ValueError("optimizer='lion' keeps one moment plane: the model holds a second (adam=True); "
                                  "allocate it with MLP(..., momentum=True)")
+        if optimizer == "adafactor":
+            # Adafactor (bfp_oracle.adafactor): one fac = R[cin] | C[cout] | V[bias] per layer, no moment plane
+            if momentum or nesterov:
+                raise ValueError("momentum / nesterov belong to SGD: Adafactor has no first moment")
+            if trust_ratio:
+                raise ValueError("trust_ratio is a flag of optimizer='adamw' (not provided on Adafactor)")
+            if max_grad_norm is not None:
+                raise ValueError("max_grad_norm: not with optimizer='adafactor' (its direction is invariant to the "
+                                 "gradient's scale up to eps1, and it clips its own update)")
+            if moment_codec != "f32":
+                raise ValueError("moment_codec='bfp8': optimizer='adamw' only")
+            if bool(getattr(engine, "shard_update", False)) or getattr(engine, "algo", "mesh") == "ring":
+                raise ValueError("optimizer='adafactor': mesh schedule without the sharded update only")
+            wire.O.adafactor_scalars(lr, weight_decay, 1)  # validates
+            for l in model.layers:
+                if l.cout % 16:
+                    raise ValueError(f"optimizer='adafactor': layer widths must be multiples of 16, got {l.cout}")
+                if l.fac is None or l.fac.numel() != l.cin + l.cout + l.n - l.cin * l.cout:
+                    l.fac = torch.zeros(l.cin + l.cout + l.n - l.cin * l.cout, dtype=torch.float32,
+                                        device=model.device)
+        self.adafactor_words = (torch.zeros(model.L, 4, dtype=torch.float32, device=model.device)
+                                if optimizer == "adafactor" else None)
         self.moment_codec = wire.O.moment_codec_check(moment_codec)
         if moment_codec == "bfp8":
             if optimizer == "lion":
@@ -339,6 +370,10 @@ class DataParallelTrainer:
         if self.optimizer == "lion":
             kw.update(opt="lion", betas=self.betas)
             return kw
+        if self.optimizer == "adafactor":
+            kw.update(opt="adafactor", fac=l.fac, rows=l.cin, cols=l.cout, step=self.opt_step,
+                      adafactor_out=self.adafactor_words[self._index(l)])
+            return kw
         if self.optimizer != "adamw":
             return kw
         kw.update(opt="adamw", var=l.var, betas=self.betas, eps=self.eps, step=self.opt_step)
@@ -430,6 +465,11 @@ class DataParallelTrainer:
             wire.adamw(src, l.n_pad, 1, l.master, codec=codec, lp=l.lp, mom=l.mom, var=l.var,
                        scalars=scalars, grad_scale=self.grad_scale, n_valid=l.n, clip=clip)
             return
+        if self.optimizer == "adafactor":
+            wire.adafactor(src, l.n_pad, 1, l.master, l.fac, codec=codec, rows=l.cin, cols=l.cout,
+                           scalars=wire.O.adafactor_scalars(self.lr, self.wd, self.opt_step), lp=l.lp,
+                           grad_scale=self.grad_scale, n_valid=l.n, words=self.adafactor_words[self._index(l)])
+            return
         if self.optimizer == "lion":
             scalars = wire.O.lion_scalars(self.lr, self.wd, self.betas[0], self.betas[1])
             wire.lion(src, l.n_pad, 1, l.master, codec=codec, lp=l.lp, mom=l.mom, scalars=scalars,
@@ -499,6 +539,8 @@ class DataParallelTrainer:
         if self.optimizer == "adamw" and self.cuda and torch.cuda.is_current_stream_capturing():
             # the step's scalars are by-value kernel arguments: a captured graph would replay step 1's for ever
             raise RuntimeError("an AdamW step cannot be captured into a graph (its per-step scalars would be frozen)")
+        if self.optimizer == "adafactor" and self.cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("an Adafactor step cannot be captured into a graph (beta2 follows the step count)")
         if self.stochastic_rounding and self.cuda and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("a stochastically rounded step cannot be captured into a graph (its seed would be frozen)")
         self.opt_step += 1

@@ -23,7 +23,8 @@ import torch
 
 from .. import _ext
 from ..ops import wire
-from .allreduce import (CLIP_GROUP_LIMIT, NUM_SLOTS, BucketLayout, ChecksumError, CommTimeoutError, adamw_request,
+from .allreduce import (CLIP_GROUP_LIMIT, NUM_SLOTS, BucketLayout, ChecksumError, CommTimeoutError, adafactor_request,
+                        adamw_request,
                         clip_group_check, clip_request, moment_request, residual_request, resolve_betas, sr_request)
 from .transport import NativeTransport, Transport
 
@@ -260,7 +261,9 @@ class NativeAllReduce:
                       step: int | None = None, trust_ratio: bool = False, n_adapt: int | None = None,
                       trust_out: torch.Tensor | None = None, clip: torch.Tensor | None = None,
                       residual: torch.Tensor | None = None, sr_seed: int | None = None,
-                      moment_codec: str = "f32", moment_seed: int | None = None) -> NativeHandle:
+                      moment_codec: str = "f32", moment_seed: int | None = None, fac: torch.Tensor | None = None,
+                      rows: int | None = None, cols: int | None = None, clip_threshold: float = 1.0,
+                      adafactor_out: torch.Tensor | None = None) -> NativeHandle:
         """``opt="adamw"``: AdamW instead of SGD, ``mom`` / ``var`` the first / second moment planes (both required),
         ``step`` the bucket's 1-based update count (as :meth:`CompressedAllReduce.allreduce_sgd`). ``trust_ratio`` /
         ``n_adapt`` / ``trust_out``: the layer-wise trust ratio (LAMB), as there; refused with the sharded update, a
@@ -280,8 +283,23 @@ class NativeAllReduce:
         ``wire.moment_plane`` tensors), as :meth:`CompressedAllReduce.allreduce_sgd`; every schedule carries it, the
         trust ratio and the sharded update refuse it. ``opt="lion"``: Lion, ``mom`` its one f32 moment plane (as
         :meth:`CompressedAllReduce.allreduce_sgd`); every schedule and the sharded update carry it, ``trust_ratio`` and
-        ``moment_codec="bfp8"`` are refused. ``betas`` left unset: (0.9, 0.999) for AdamW, (0.9, 0.99) for Lion."""
+        ``moment_codec="bfp8"`` are refused. ``betas`` left unset: (0.9, 0.999) for AdamW, (0.9, 0.99) for Lion.
+        ``opt="adafactor"`` with ``fac`` / ``rows`` / ``cols`` / ``step`` / ``clip_threshold`` / ``adafactor_out``:
+        Adafactor, as :meth:`CompressedAllReduce.allreduce_sgd`; the mesh schedule on every transport carries it (inline
+        world 1, the forced 1-rank path, the copying and the direct-P2P mesh), ``residual``, ``sr_seed``, ``prepacked``
+        and ``on_producer`` compose with it; the ring, chunked layouts, the sharded update and ``clip`` refuse it."""
         n_valid = int(n_valid if n_valid is not None else master.numel())
+        af = None
+        if opt == "adafactor":
+            ls_, lc_ = (0, 0) if layout is None else (int(layout[0]), int(layout[1]))
+            af = adafactor_request(fac, rows, cols, n_valid, lr=lr, weight_decay=weight_decay, step=step,
+                                   clip_threshold=clip_threshold, mom=mom, var=var, momentum=momentum,
+                                   nesterov=nesterov, betas=betas, trust_ratio=trust_ratio, moment_codec=moment_codec,
+                                   clip=clip, algo=self.algo, chunks=self.C.layout(n_valid, ls_, lc_)["chunks"],
+                                   sharded=self.shard_update, compat_owner_fp32=self.compat_owner_fp32,
+                                   device=self.device)
+        elif fac is not None or rows is not None or cols is not None or adafactor_out is not None:
+            raise ValueError("fac / rows / cols / adafactor_out belong to opt='adafactor'")
         betas = resolve_betas(opt, betas)
         clip_request(clip, defer, self.device)
         sr_seed = self._sr(sr_seed, n_valid, prepacked, layout, residual)
@@ -297,6 +315,9 @@ class NativeAllReduce:
             okw = dict(opt=2, lion=scalars.kernel_args())
         else:
             okw = {} if scalars is None else dict(opt=1, var=var.view(-1), adamw=scalars.kernel_args())
+        if af is not None:
+            okw = dict(opt=3, adafactor=af.kernel_args(), fac=fac.view(-1), rows=int(rows), cols=int(cols),
+                       adafactor_out=None if adafactor_out is None else adafactor_out.view(-1))
         if mq_seed is not None:  # the 8-bit planes stand in for mom / var
             okw = dict(opt=1, adamw=scalars.kernel_args(), mom_q=mom.view(-1), var_q=var.view(-1), moment_seed=mq_seed)
             mom = None

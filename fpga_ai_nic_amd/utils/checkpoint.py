@@ -5,6 +5,8 @@ The reference never writes weights to disk; its in-memory layo
 defines the on-disk format as exactly that:
 
 * ``<path>.safetensors`` — tensors ``fc{i}.weight`` [C_i, C_{i+1}] and ``fc{i}.bias`` [C_{i+1}] in f32 (or bf16),
+  ``fc{i}.fac`` (Adafactor's R | C | V, f32, ``cin + cout + bias`` long, when the index says ``optimizer`` =
+  "adafactor"; ``opt_step`` is then its update count),
   optional ``fc{i}.momentum`` (flat, f32: SGD's momentum, or Lion's one moment plane when the index says
   ``optimizer`` = "lion"), or for an AdamW model ``fc{i}.exp_avg`` / ``fc{i}.exp_avg_sq`` (its two
   moment planes, flat, f32; the index then carries ``optimizer`` and ``opt_step``, the updates applied so far; a
@@ -46,6 +48,8 @@ def save(path: str, model, *, iteration: int = 0, dtype: str = "f32", meta: dict
             tensors[f"fc{i}.exp_avg_sq"] = l.var[: l.n].detach().to("cpu").contiguous()
         elif l.mom is not None:
             tensors[f"fc{i}.momentum"] = l.mom[: l.n].detach().to("cpu").contiguous()
+        if getattr(l, "fac", None) is not None:  # Adafactor's R | C | V (the index says optimizer = "adafactor")
+            tensors[f"fc{i}.fac"] = l.fac.detach().to("cpu").contiguous()
         for name, t in ((f"fc{i}.weight", w), (f"fc{i}.bias", b)):
             raw = t.view(torch.uint8).numpy().tobytes() if tdt == torch.bfloat16 else t.numpy().tobytes()
             index.append({"name": name, "shape": list(t.shape), "dtype": dtype, "offset": off, "nbytes": len(raw)})
@@ -76,14 +80,15 @@ def save(path: str, model, *, iteration: int = 0, dtype: str = "f32", meta: dict
 def load(path: str, model, optimizer: str | None = None) -> dict:
     """``optimizer``: the resuming run's. Lion's ``fc{i}.momentum`` plane is not SGD's momentum and not AdamW's first
     moment, so a checkpoint whose index names an optimizer loads into a Lion run, and a Lion checkpoint into any run,
-    only under that optimizer."""
+    only under that optimizer; Adafactor's ``fc{i}.fac`` likewise."""
     with open(path + ".json") as f:
         info = json.load(f)
     saved_opt = info.get("optimizer")
-    if optimizer is not None and saved_opt is not None and saved_opt != optimizer and "lion" in (saved_opt, optimizer):
+    own = {"lion", "adafactor"} & {saved_opt, optimizer}  # optimizers whose state belongs to them alone
+    if optimizer is not None and saved_opt is not None and saved_opt != optimizer and own:
         raise ValueError(f"checkpoint was written under optimizer={saved_opt!r}; this run is optimizer={optimizer!r} "
-                         f"(Lion's moment plane belongs to Lion alone: resume under the optimizer the checkpoint was "
-                         f"written with)")
+                         f"(the state of {' / '.join(sorted(own))} belongs to that optimizer alone: resume under the "
+                         f"optimizer the checkpoint was written with)")
     if list(info["sizes"]) != list(model.sizes):
         raise ValueError(f"checkpoint sizes {info['sizes']} != model sizes {model.sizes}")
     sd = load_file(path + ".safetensors")
@@ -110,6 +115,8 @@ def load(path: str, model, optimizer: str | None = None) -> dict:
             l.var[: l.n].copy_(sd[f"fc{i}.exp_avg_sq"].to(l.var.device))
         elif l.mom is not None and f"fc{i}.momentum" in sd:
             l.mom[: l.n].copy_(sd[f"fc{i}.momentum"].to(l.mom.device))
+        if f"fc{i}.fac" in sd:  # (allocated here when the trainer has not yet: it keeps a state it finds)
+            l.fac = sd[f"fc{i}.fac"].to(l.master.device, torch.float32).contiguous()
     model.sync_lp()
     return info
 
