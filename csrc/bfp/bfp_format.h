@@ -19,6 +19,11 @@
 // framework's rne form at 4 bits: [u8 nib[n_s/2]][u8 exp[n_s/16]], 9 bytes per 16 values, byte i of a group's 8
 // holding value 2i in bits [3:0] and value 2i+1 in bits [7:4] (two's complement). Exponent plane and shard starts
 // stay 16-B aligned (n_s % 256 == 0). The reference ships no 4-bit configuration, so there is no truncating form.
+//
+// kSign1 is the narrowest contractive form, for use with error feedback (EF-signSGD): one sign bit per value and one
+// power-of-two scale per group, [u8 sign[n_s/8]][u8 exp[n_s/16]], 3 bytes per 16 values. Bit i & 7 of byte i >> 3 is the
+// f32 sign bit of value i; the exponent byte is the exponent field of the group's mean magnitude (sign1_group_exponent),
+// so every value decodes to +-2^(E-127), the mean of |x| rounded down to a power of two. No counterpart in the reference.
 #pragma once
 #include "common/hip_common.h"
 
@@ -30,11 +35,15 @@ enum Codec : int {
   kRawF32 = 2,    // uncompressed fp32 on the wire
   kRawBf16 = 3,   // uncompressed bf16 on the wire
   kBfp4Rne = 4,   // 4-bit mantissas (two per byte), round-to-nearest-even, exact decode q * 2^(E-129)
+  kSign1 = 5,     // one sign bit per value, the group's mean magnitude rounded down to a power of two as the scale
 };
 
-// Codecs whose groups of 16 values share an exponent byte (every BFP width), and the 8-bit ones among them: the only
-// ones the GEMM wire epilogues encode (prepack, the fused update) and the 4-values-per-lane layout (Lanes4) handles.
-__host__ __device__ constexpr bool codec_shared_exp(int c) { return c == kBfpTrunc || c == kBfpRne || c == kBfp4Rne; }
+// Codecs whose groups of 16 values share an exponent byte (every BFP width and kSign1), and the 8-bit ones among them:
+// the only ones the GEMM wire epilogues encode (prepack, the fused update) and the 4-values-per-lane layout (Lanes4)
+// handles.
+__host__ __device__ constexpr bool codec_shared_exp(int c) {
+  return c == kBfpTrunc || c == kBfpRne || c == kBfp4Rne || c == kSign1;
+}
 __host__ __device__ constexpr bool codec_bfp8(int c) { return c == kBfpTrunc || c == kBfpRne; }
 
 enum DType : int { kF32 = 0, kBF16 = 1 };
@@ -182,6 +191,7 @@ __host__ __device__ inline size_t wire_shard_bytes(int codec, size_t n_s) {
     case kBfpTrunc:
     case kBfpRne: return n_s + n_s / 16;
     case kBfp4Rne: return n_s / 2 + n_s / 16;
+    case kSign1: return n_s / 8 + n_s / 16;
     case kRawF32: return n_s * 4;
     default: return n_s * 2;
   }
@@ -236,17 +246,80 @@ __device__ __forceinline__ int32_t bfp4_nibble(uint32_t w, int j) { return (int3
 // Encode / decode of one value by codec (the 8-bit forms take and return the byte's value, the 4-bit form the nibble's).
 template <int C>
 __device__ __forceinline__ int32_t bfp_encode(float x, uint32_t E) {
-  static_assert(codec_shared_exp(C), "BFP codecs");
+  static_assert(codec_shared_exp(C) && C != kSign1, "mantissa codecs");
   if constexpr (C == kBfpTrunc) return bfp_encode_trunc(__float_as_uint(x), E);
   else if constexpr (C == kBfpRne) return bfp_encode_rne(x, E);
   else return bfp4_encode_rne(x, E);
 }
 template <int C>
 __device__ __forceinline__ float bfp_decode(int32_t q, uint32_t E) {
-  static_assert(codec_shared_exp(C), "BFP codecs");
+  static_assert(codec_shared_exp(C) && C != kSign1, "mantissa codecs");
   if constexpr (C == kBfpTrunc) return bfp_decode_trunc(q, E);
   else if constexpr (C == kBfpRne) return bfp_decode_rne(q, E);
   else return bfp4_decode_rne(q, E);
+}
+
+// ---------------------------------------------------------------- kSign1 primitives (ops/bfp_oracle.py sign1_*)
+// The scale of a group is the f32 sum S = h0 + h1 of its two half sums, h = ((((((a_0 + a_1) + a_2) + a_3) + a_4) +
+// a_5) + a_6) + a_7 over a_j = |x_j| * 0.0625f: the mean of |x|, prescaled so that S <= max|x| never overflows. The
+// two-halves order is part of the format: a lane that holds 8 values (its partner's half sum arrives by one shuffle)
+// and a lane that holds the whole group add the same numbers in the same order. Every product and every sum is
+// rounded to f32 on its own, as the oracle's: contraction is off in this function (hipcc's default would fuse each
+// step into fma(|x_j|, 0.0625, h), which differs where a_j is denormal, |x_j| < 2^-122). The build keeps f32
+// denormals (no flush-to-zero flag), as the oracle's NumPy does; the non-finite test goes through the integer bits.
+__device__ __forceinline__ float sign1_half_sum(const float* v) {
+#pragma clang fp contract(off)
+  float h = fabsf(v[0]) * 0.0625f + fabsf(v[1]) * 0.0625f;
+#pragma unroll
+  for (int j = 2; j < 8; ++j) h = h + fabsf(v[j]) * 0.0625f;
+  return h;
+}
+
+// The largest magnitude's bits of kN values: 0x7F800000 or above when one of them is Inf or NaN.
+template <int kN>
+__device__ __forceinline__ uint32_t sign1_max_bits(const float* v) {
+  uint32_t mx = 0;
+#pragma unroll
+  for (int j = 0; j < kN; ++j) mx = max(mx, __float_as_uint(v[j]) & 0x7FFFFFFFu);
+  return mx;
+}
+
+// E from the group's sum and its largest magnitude's bits: 255 for a non-finite group, else S's exponent field
+// (0..254; 0: a zero or denormal mean).
+__device__ __forceinline__ uint32_t sign1_exponent(float S, uint32_t mx) {
+  return mx >= 0x7F800000u ? 255u : (__float_as_uint(S) >> 23) & 0xFFu;
+}
+
+// The exponent byte of a 16-value group one lane holds whole.
+__device__ __forceinline__ uint32_t sign1_group_exponent(const float* v) {
+  return sign1_exponent(sign1_half_sum(v) + sign1_half_sum(v + 8), sign1_max_bits<16>(v));
+}
+
+// The sign bits of kN values, value j in bit j.
+template <int kN>
+__device__ __forceinline__ uint32_t sign1_bits(const float* v) {
+  uint32_t b = 0;
+#pragma unroll
+  for (int j = 0; j < kN; ++j) b |= (__float_as_uint(v[j]) >> 31) << j;
+  return b;
+}
+
+// Decode kN values from their sign bits: E == 255 -> NaN, E == 0 -> +0.0 (both whatever the bits), else +-2^(E-127).
+template <int kN>
+__device__ __forceinline__ void sign1_decode(uint32_t b, uint32_t E, float* v) {
+  const uint32_t s = E == 255u ? 0x7FC00000u : E << 23;
+  const uint32_t m = E - 1u < 254u ? 0x80000000u : 0u;  // the sign applies to a finite non-zero scale only
+#pragma unroll
+  for (int j = 0; j < kN; ++j) v[j] = __uint_as_float(s | ((b << (31 - j)) & m));
+}
+
+// The sign words of 8 consecutive lanes (16 bits each) as the 16 B lane 8k stores: 2 lanes -> one dword, 4 dwords ->
+// one uint4 (valid in lane 8k; all 8 lanes must be active).
+__device__ __forceinline__ uint4 sign1_gather_signs(uint32_t b) {
+  const uint32_t d = b | ((uint32_t)__shfl_down((int)b, 1) << 16);
+  const uint32_t d1 = (uint32_t)__shfl_down((int)d, 2), d2 = (uint32_t)__shfl_down((int)d, 4),
+                 d3 = (uint32_t)__shfl_down((int)d, 6);
+  return make_uint4(d, d1, d2, d3);
 }
 
 // ---------------------------------------------------------------- 8-value lane codecs
@@ -311,6 +384,26 @@ struct WireLane<kBfp4Rne> {
     for (int j = 0; j < 8; ++j) w |= ((uint32_t)bfp4_encode_rne(v[j], E) & 0xFu) << (4 * j);
     *reinterpret_cast<uint32_t*>(shard + (le >> 1)) = w;
     if ((le & 15) == 0) shard[(n_s >> 1) + (le >> 4)] = (uint8_t)E;
+  }
+};
+
+// One sign bit per value, shard layout [u8 sign[n_s/8]][u8 exp[n_s/16]]: a lane's 8 values are ONE byte of signs; the
+// partner's half sum and largest magnitude come through one xor shuffle each, the exponent byte leaves by the even lane.
+template <>
+struct WireLane<kSign1> {
+  __device__ static __forceinline__ void load8(const uint8_t* shard, size_t n_s, size_t le, float v[8]) {
+    const uint32_t b = shard[le >> 3];
+    const uint32_t E = shard[(n_s >> 3) + (le >> 4)];
+    sign1_decode<8>(b, E, v);
+  }
+  // Both lanes of the pair (lane, lane^1) must be active: they hold the two halves of a group.
+  __device__ static __forceinline__ void store8(uint8_t* shard, size_t n_s, size_t le, const float v[8]) {
+    const float h = sign1_half_sum(v);
+    const uint32_t mx = sign1_max_bits<8>(v);
+    const float S = h + __shfl_xor(h, 1);  // (h0 + h1 in the even lane, h1 + h0 in the odd one: the same bits)
+    const uint32_t E = sign1_exponent(S, max(mx, (uint32_t)__shfl_xor((int)mx, 1)));
+    shard[le >> 3] = (uint8_t)sign1_bits<8>(v);
+    if ((le & 15) == 0) shard[(n_s >> 3) + (le >> 4)] = (uint8_t)E;
   }
 };
 
@@ -440,6 +533,25 @@ struct WireLane16<kBfp4Rne> {
   }
 };
 
+// The sign group per lane: ONE 2-B load of signs per lane; on the way out the sign words of 8 adjacent lanes are
+// gathered into one 16-B store by lane 8k (a 16-lane segment starts at a multiple of 16 groups, so lane 8k's byte
+// offset is a multiple of 16) and the exponent plane goes as above. No lane issues a 2-B store.
+template <>
+struct WireLane16<kSign1> {
+  __device__ static __forceinline__ void load16(const uint8_t* shard, size_t n_s, size_t le, float v[16]) {
+    const uint32_t b = *reinterpret_cast<const uint16_t*>(shard + (le >> 3));
+    const uint32_t E = shard[(n_s >> 3) + (le >> 4)];
+    sign1_decode<16>(b, E, v);
+  }
+  __device__ static __forceinline__ void store16(uint8_t* shard, size_t n_s, size_t le, const float v[16]) {
+    const uint32_t E = sign1_group_exponent(v);
+    const uint4 s16 = sign1_gather_signs(sign1_bits<16>(v));
+    if ((threadIdx.x & 7) == 0) *reinterpret_cast<uint4*>(shard + (le >> 3)) = s16;
+    const uint4 e16 = bfp_gather_exponents(E);
+    if ((threadIdx.x & 15) == 0) *reinterpret_cast<uint4*>(shard + (n_s >> 3) + (le >> 4)) = e16;
+  }
+};
+
 // Dense (local) operand loads: f32 or bf16 arrays.
 template <typename T>
 struct DenseLane;
@@ -482,6 +594,7 @@ struct DenseLane16 {
 // The value every rank decodes after `x` is encoded in a group of shared exponent E.
 template <int C>
 __device__ __forceinline__ float bfp_roundtrip(float x, uint32_t E) {
+  static_assert(C != kSign1, "mantissa codecs (kSign1: sign1_decode of sign1_bits)");
   const int32_t q = bfp_encode<C>(x, E);
   // the stored byte (nibble), as the decoder reads it
   const int32_t qs = C == kBfp4Rne ? bfp4_nibble((uint32_t)q & 0xFu, 0) : (int32_t)(int8_t)(uint8_t)((uint32_t)q & 0xFFu);
@@ -508,7 +621,10 @@ struct Lanes16 {
     DenseLane16<bf16_t>::store16(p, e, v);
   }
   __device__ static __forceinline__ void roundtrip(float v[16]) {
-    if constexpr (codec_shared_exp(C)) {
+    if constexpr (C == kSign1) {
+      const uint32_t E = sign1_group_exponent(v);
+      sign1_decode<16>(sign1_bits<16>(v), E, v);
+    } else if constexpr (codec_shared_exp(C)) {
       const uint32_t E = bfp_group_exponent(v);
 #pragma unroll
       for (int j = 0; j < 16; ++j) v[j] = bfp_roundtrip<C>(v[j], E);

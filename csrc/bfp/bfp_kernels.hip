@@ -1067,6 +1067,7 @@ FAN_AF_KERNEL
     case kRawF32: { constexpr int C = kRawF32; __VA_ARGS__; break; }     \
     case kRawBf16: { constexpr int C = kRawBf16; __VA_ARGS__; break; }   \
     case kBfp4Rne: { constexpr int C = kBfp4Rne; __VA_ARGS__; break; }   \
+    case kSign1: { constexpr int C = kSign1; __VA_ARGS__; break; }       \
     default: FAN_CHECK(false, "unknown codec");              \
   }
 
@@ -1124,8 +1125,8 @@ void launch_wire_unpack(int codec, int out_dtype, const void* in, void* out, siz
 }
 
 // The lane layout and the grid of a reduce kernel: launch(L{}, grid) with L = Lanes4<C> (4 values per lane) for an
-// 8-bit BFP codec when wire_reduce4_for(n_slots), else Lanes16<C> (a group per lane; kBfp4Rne always: 4 of its values
-// are two bytes, too narrow a store to be worth a layout of their own).
+// 8-bit BFP codec when wire_reduce4_for(n_slots), else Lanes16<C> (a group per lane; kBfp4Rne and kSign1 always: 4 of
+// their values are two bytes or half a byte, too narrow a store to be worth a layout of their own).
 template <int C, typename F>
 static void with_lanes(int n_slots, size_t n_s, int cap, F&& launch) {
   if constexpr (codec_bfp8(C)) {

@@ -3,7 +3,7 @@
 Reference knobs and where they went:
   iters / MB / fuse_type / type / bn bk bc / C1..CN  -> positional CLI, kept (sw/mlp_mpi_example_f32.cpp:270-320)
   NUM_NODES=3 (sw:38)                               -> world size from the launcher (any N >= 1)
-  `BFP_EN (hw/all_reduce.sv:13)                     -> compress = bfp | bfp4 | raw | rccl | local
+  `BFP_EN (hw/all_reduce.sv:13)                     -> compress = bfp | bfp4 | sign | raw | rccl | local
   NUM_FP=16, MANT_SIZE=8 (hw/bfp_adapter.sv:34-36)   -> group of 16; 8-bit mantissas (bfp; rounding = rne | trunc, the
                                                         bit-exact ref) or 4-bit (bfp4, rne only)
   BUF_SIZE=512 CL slice (hw/all_reduce.sv:102)      -> slice_elems (ring)
@@ -28,7 +28,7 @@ class TrainConfig:
     bc: int = 64
     sizes: list = field(default_factory=lambda: [1024, 4096, 4096, 1024])
     dtype: str = "bf16"            # bf16 | f32
-    compress: str = "bfp"          # bfp | bfp4 | raw | raw_bf16 | rccl | local
+    compress: str = "bfp"          # bfp | bfp4 | sign | raw | raw_bf16 | rccl | local
     rounding: str = "rne"          # rne | trunc
     algo: str = "mesh"             # mesh | ring
     rings: int = 1
@@ -74,9 +74,12 @@ class TrainConfig:
 def add_named_flags(ap: argparse.ArgumentParser):
     d = TrainConfig()
     ap.add_argument("--dtype", default=d.dtype, choices=["bf16", "f32"])
-    ap.add_argument("--compress", default=d.compress, choices=["bfp", "bfp4", "raw", "raw_bf16", "rccl", "local"],
+    ap.add_argument("--compress", default=d.compress,
+                    choices=["bfp", "bfp4", "sign", "raw", "raw_bf16", "rccl", "local"],
                     help="wire format of the all-reduce: bfp = 8-bit mantissas (17 B per 16 values), bfp4 = 4-bit "
-                         "mantissas (9 B per 16 values, --rounding rne only; meant for use with --error-feedback)")
+                         "mantissas (9 B per 16 values, --rounding rne only; meant for use with --error-feedback), "
+                         "sign = one sign bit per value and a power-of-two scale per group (codec sign1, 3 B per 16 "
+                         "values; needs --error-feedback, --rounding rne only)")
     ap.add_argument("--rounding", default=d.rounding, choices=["rne", "trunc"])
     ap.add_argument("--algo", default=d.algo, choices=["mesh", "ring"])
     ap.add_argument("--rings", type=int, default=d.rings)
@@ -139,6 +142,11 @@ def wire_codec(compress: str, rounding: str = "rne") -> str:
             raise ValueError(f"--compress bfp4 has no {rounding!r} rounding: the 4-bit codec is bfp4_rne only (the "
                              f"reference ships no 4-bit configuration to be bit-exact to)")
         return "bfp4_rne"
+    if compress == "sign":
+        if rounding != "rne":
+            raise ValueError(f"--compress sign has no {rounding!r} rounding: the sign1 codec keeps no mantissa to "
+                             f"truncate")
+        return "sign1"
     return {"bfp": f"bfp_{rounding}", "raw": "raw_f32", "raw_bf16": "raw_bf16"}[compress]
 
 
@@ -150,6 +158,9 @@ def config_from_args(a, positional_sizes=None) -> TrainConfig:
             setattr(c, key, getattr(a, key))
     if positional_sizes:
         c.sizes = list(positional_sizes)
-    if c.compress == "bfp4":
+    if c.compress in ("bfp4", "sign"):
         wire_codec(c.compress, c.rounding)  # (--rounding trunc: a ValueError)
+    if c.compress == "sign" and not c.error_feedback:
+        raise ValueError("--compress sign: sign1 needs error feedback (--error-feedback): one bit per value converges "
+                         "only with the residual carried over")
     return c

@@ -15,9 +15,13 @@ Two numerics are modelled:
 ``bfp4_rne`` is the ``rne`` form at a 4-bit mantissa (the reference's MANT_SIZE knob; it ships no such configuration,
 so there is no truncating form): q = clamp(rint(x * 2^(129-E)), -7, 7), decode q * 2^(E-129), E = 255 -> NaN.
 
+``sign1`` keeps one sign bit per value and one power-of-two scale per group (:func:`sign1_encode_groups`): the
+narrowest contractive compressor, meant for use with error feedback.
+
 Packed layout of a shard of n_s elements (n_s % 256 == 0): ``[int8 mant[n_s]][uint8 exp[n_s/16]]``;
 ``bfp4_rne``: ``[uint8 nib[n_s/2]][uint8 exp[n_s/16]]``, byte i of a group's 8 holding value 2i in bits [3:0] and
-value 2i+1 in bits [7:4] (two's complement nibbles). Multi-shard buffers are shards back to back.
+value 2i+1 in bits [7:4] (two's complement nibbles); ``sign1``: ``[uint8 sign[n_s/8]][uint8 exp[n_s/16]]``, bit i & 7
+of byte i >> 3 the sign of value i. Multi-shard buffers are shards back to back.
 """
 from __future__ import annotations
 
@@ -26,8 +30,8 @@ import math
 import numpy as np
 
 GROUP = 16
-CODECS = {"bfp_trunc": 0, "bfp_rne": 1, "raw_f32": 2, "raw_bf16": 3, "bfp4_rne": 4}
-BFP_CODECS = (0, 1, 4)  # a shared exponent per group of 16; (0, 1) are the 8-bit ones the GEMM epilogues encode
+CODECS = {"bfp_trunc": 0, "bfp_rne": 1, "raw_f32": 2, "raw_bf16": 3, "bfp4_rne": 4, "sign1": 5}
+BFP_CODECS = (0, 1, 4, 5)  # a shared exponent per group of 16; (0, 1) are the 8-bit ones the GEMM epilogues encode
 CODEC_NAMES = {v: k for k, v in CODECS.items()}
 
 
@@ -43,6 +47,8 @@ def shard_bytes(codec, n_s: int) -> int:
         return n_s + n_s // 16
     if c == 4:
         return n_s // 2 + n_s // 16
+    if c == 5:
+        return n_s // 8 + n_s // 16
     return n_s * (4 if c == 2 else 2)
 
 
@@ -128,6 +134,39 @@ def unpack_nibbles(b: np.ndarray) -> np.ndarray:
     return np.where(u >= 8, u - 16, u).astype(np.int8)
 
 
+# --------------------------------------------------------------------------- sign1
+def sign1_encode_groups(x: np.ndarray):
+    """x: float32 (size % 16 == 0) -> (sign bytes uint8 [n/8], E uint8 [n/16]). Per group, all f32: a_j = |x_j| *
+    0.0625, h0 = ((((((a_0 + a_1) + a_2) + a_3) + a_4) + a_5) + a_6) + a_7, h1 likewise over a_8..a_15, S = h0 + h1 (the
+    mean of |x|; S <= max|x|, so it never overflows); E = 255 if any x_j is NaN or +-Inf, else S's exponent field
+    (0..254: the mean rounded down to a power of two; 0 for a zero or denormal mean). Bit i & 7 of byte i >> 3 is the
+    f32 sign bit of x_i, whatever E."""
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, GROUP)
+    bits = x.view(np.uint32)
+    with np.errstate(over="ignore", invalid="ignore", under="ignore"):
+        a = np.abs(x) * np.float32(0.0625)
+        h = []
+        for lo in (0, 8):
+            t = a[:, lo] + a[:, lo + 1]
+            for j in range(lo + 2, lo + 8):
+                t = t + a[:, j]
+            h.append(t)
+        S = (h[0] + h[1]).astype(np.float32)
+    E = (S.view(np.uint32) >> 23) & 0xFF
+    E = np.where(((bits & 0x7FFFFFFF) >= 0x7F800000).any(axis=1), 255, E)
+    sign = np.packbits((bits >> 31).astype(np.uint8).reshape(-1), bitorder="little")
+    return sign, E.astype(np.uint8)
+
+
+def sign1_decode_groups(sign: np.ndarray, E: np.ndarray) -> np.ndarray:
+    """The inverse: E == 255 -> NaN and E == 0 -> +0.0 for all 16, else +-2^(E - 127) by the value's bit."""
+    b = np.unpackbits(np.asarray(sign, dtype=np.uint8).reshape(-1), bitorder="little").reshape(-1, GROUP)
+    Eu = np.asarray(E, dtype=np.uint8).reshape(-1, 1).astype(np.uint32)
+    v = ((Eu << 23) | (b.astype(np.uint32) << 31)).astype(np.uint32).view(np.float32)
+    v = np.where(Eu == 255, np.float32(np.nan), np.where(Eu == 0, np.float32(0.0), v))
+    return v.reshape(-1).astype(np.float32)
+
+
 # --------------------------------------------------------------------------- packed buffers
 def pack(x: np.ndarray, shard_elems: int, codec="bfp_rne") -> np.ndarray:
     """Dense f32 (or bf16 given as float32 values) -> packed uint8 buffer (per-shard layout)."""
@@ -140,6 +179,9 @@ def pack(x: np.ndarray, shard_elems: int, codec="bfp_rne") -> np.ndarray:
         return f32_to_bf16_bits(x).view(np.uint8).copy()
     out = []
     for s in range(x.size // shard_elems):
+        if c == 5:
+            out.extend(sign1_encode_groups(x[s * shard_elems:(s + 1) * shard_elems]))
+            continue
         q, E = encode_groups(x[s * shard_elems:(s + 1) * shard_elems], _rounding_of(c))
         out.append(pack_nibbles(q) if c == 4 else q.view(np.uint8))
         out.append(E)
@@ -157,6 +199,9 @@ def unpack(buf: np.ndarray, n: int, shard_elems: int, codec="bfp_rne") -> np.nda
     out = []
     for s in range(n // shard_elems):
         sh = buf[s * sb:(s + 1) * sb]
+        if c == 5:
+            out.append(sign1_decode_groups(sh[:shard_elems // 8], sh[shard_elems // 8:]))
+            continue
         nm = shard_elems // 2 if c == 4 else shard_elems
         q = unpack_nibbles(sh[:nm]) if c == 4 else sh[:nm].view(np.int8)
         out.append(decode_groups(q, sh[nm:], _rounding_of(c)))
@@ -171,6 +216,8 @@ def quantize(x: np.ndarray, codec="bfp_rne") -> np.ndarray:
         return x.copy()
     if c == 3:
         return bf16_bits_to_f32(f32_to_bf16_bits(x))
+    if c == 5:
+        return sign1_decode_groups(*sign1_encode_groups(x))
     q, E = encode_groups(x, _rounding_of(c))
     return decode_groups(q, E, _rounding_of(c))
 

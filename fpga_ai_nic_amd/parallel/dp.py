@@ -61,6 +61,8 @@ def make_engine(transport: Transport | None, kind: str = "bfp", *, rounding: str
     """``device`` (Python engines): where the engine keeps its buffers; None: the current GPU when there is one. A
     CPU run on a machine that has a GPU must name it, or the engine's scratch lands on the GPU beside CPU gradients.
     kind: 'bfp' (compressed engine), 'bfp4' (the same with 4-bit mantissas, codec bfp4_rne: ``rounding`` must be 'rne'),
+    'sign' (the same with one sign bit per value and a scale per group, codec sign1: 'rne' too, and a trainer on it
+    needs ``error_feedback``),
     'raw' (engine, uncompressed fp32 wire), 'rccl' (baseline),
     'local' (no communication: world 1). impl: 'python' (request path issued from Python over any
     transport) or 'native' (C++ engine over its own RCCL communicator, or over ``comm``, e.g. the direct P2P
@@ -263,6 +265,9 @@ class DataParallelTrainer:
         self.residuals = None
         self._ef_wire = None  # the engine-less trainer's one-slot wire, per layer
         self.ef_codec = getattr(engine, "codec", "bfp_rne") if engine is not None else error_feedback_codec
+        if self.ef_codec == "sign1" and not self.error_feedback:
+            raise ValueError("sign1 needs error feedback (error_feedback=True): one bit per value converges only with "
+                             "the residual carried over")
         if self.error_feedback:
             if wire.is_raw(self.ef_codec):
                 raise ValueError(f"error_feedback: nothing to feed back with a raw codec ({self.ef_codec}); BFP codecs "
