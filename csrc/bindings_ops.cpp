@@ -5,6 +5,7 @@
 #include "gemm/gemm.h"
 #include "gemm/gemm_chain.h"
 #include "gemm/gemm_group.h"
+#include "lowrank/lowrank.h"
 #include "nn/nn.h"
 
 namespace fan {
@@ -668,6 +669,66 @@ void wire_adafactor(const at::Tensor& wire, int64_t shard_elems, int64_t n_shard
                         (size_t)n_valid, fan_stream(), (size_t)shard_stride, (int)max_blocks, (int)phases);
 }
 
+// ---- PowerSGD low-rank compression (lowrank/lowrank.h). Every plane: contiguous f32 on one GPU, of exactly the
+// length the shape says (so nothing behind it is reachable), except g, which may be the head of a longer bucket.
+const float* lr_plane(const at::Tensor& t, int64_t n, bool exact, const at::Tensor& ref, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == at::kFloat && t.device() == ref.device() &&
+                  (exact ? t.numel() == n : t.numel() >= n),
+              "lowrank: ", what, " must be a contiguous float32 tensor of ", n, " elements on the gradient's GPU");
+  return t.data_ptr<float>();
+}
+
+void lr_shape(const at::Tensor& g, const at::Tensor& e, int64_t rows, int64_t cols) {
+  TORCH_CHECK(rows > 0 && cols > 0 && rows % 16 == 0 && cols % 16 == 0,
+              "lowrank: rows and cols must be positive multiples of 16, got ", rows, " x ", cols);
+  lr_plane(g, rows * cols, false, g, "g");
+  lr_plane(e, rows * cols, true, g, "e");
+}
+
+void lowrank_project(const at::Tensor& g, const at::Tensor& e, const at::Tensor& q, at::Tensor& part, int64_t rows,
+                     int64_t cols) {
+  lr_shape(g, e, rows, cols);
+  const LowrankLayout L = lowrank_layout(rows, cols);
+  launch_lowrank_project(g.data_ptr<float>(), e.data_ptr<float>(), lr_plane(q, cols * kLrRank, true, g, "q"),
+                         const_cast<float*>(lr_plane(part, L.proj_strips * rows * kLrRank, false, g, "part")), rows,
+                         cols, fan_stream());
+}
+
+void lowrank_backproject(const at::Tensor& g, const at::Tensor& e, const at::Tensor& ph, at::Tensor& part,
+                         int64_t rows, int64_t cols) {
+  lr_shape(g, e, rows, cols);
+  const LowrankLayout L = lowrank_layout(rows, cols);
+  launch_lowrank_backproject(g.data_ptr<float>(), e.data_ptr<float>(), lr_plane(ph, rows * kLrRank, true, g, "ph"),
+                             const_cast<float*>(lr_plane(part, L.back_strips * cols * kLrRank, false, g, "part")),
+                             rows, cols, fan_stream());
+}
+
+void lowrank_combine(const at::Tensor& part, int64_t slabs, at::Tensor& out) {
+  TORCH_CHECK(slabs >= 1, "lowrank combine: slabs >= 1");
+  const int64_t n = out.numel();
+  TORCH_CHECK(n > 0 && n % kLrRank == 0, "lowrank combine: out holds whole rows of 16");
+  TORCH_CHECK(part.data_ptr() != out.data_ptr(), "lowrank combine: out must not be the partial buffer");
+  launch_lowrank_combine(lr_plane(part, slabs * n, false, out, "part"),
+                         slabs, const_cast<float*>(lr_plane(out, n, true, out, "out")), n, fan_stream());
+}
+
+void lowrank_orth(at::Tensor& p, int64_t rank) {
+  TORCH_CHECK(rank >= 1 && rank <= kLrRank, "lowrank: the rank must lie in 1..16, got ", rank);
+  TORCH_CHECK(p.dim() == 2 && p.size(1) == kLrRank && p.size(0) % 16 == 0 && rank <= p.size(0),
+              "lowrank orth: p is [rows][16] with rows a multiple of 16 and rank <= rows");
+  launch_lowrank_orth(const_cast<float*>(lr_plane(p, p.numel(), true, p, "p")), p.size(0), (int)rank, fan_stream());
+}
+
+void lowrank_reconstruct(at::Tensor& g, at::Tensor& e, const at::Tensor& ph, const at::Tensor& qn, at::Tensor& q_out,
+                         double inv, int64_t rows, int64_t cols) {
+  lr_shape(g, e, rows, cols);
+  TORCH_CHECK(qn.data_ptr() != q_out.data_ptr(), "lowrank reconstruct: q_out must not be qn");
+  launch_lowrank_reconstruct(g.data_ptr<float>(), e.data_ptr<float>(), lr_plane(ph, rows * kLrRank, true, g, "ph"),
+                             lr_plane(qn, cols * kLrRank, true, g, "qn"),
+                             const_cast<float*>(lr_plane(q_out, cols * kLrRank, true, g, "q_out")), (float)inv, rows,
+                             cols, fan_stream());
+}
+
 }  // namespace
 
 void register_gemm(pybind11::module_& m) {
@@ -796,6 +857,24 @@ void register_nn(pybind11::module_& m) {
         pybind11::arg("words"), pybind11::arg("scalars"), pybind11::arg("grad_scale"), pybind11::arg("rows"),
         pybind11::arg("cols"), pybind11::arg("n_valid"), pybind11::arg("codec"), pybind11::arg("shard_stride") = 0,
         pybind11::arg("max_blocks") = 0, pybind11::arg("phases") = 63);
+  pybind11::module_ lr = m.def_submodule("lowrank", "PowerSGD low-rank gradient compression kernels");
+  lr.def("layout", [](int64_t rows, int64_t cols) {
+    const LowrankLayout L = lowrank_layout(rows, cols);
+    return std::vector<int64_t>{L.proj_strips, L.back_strips, L.part_elems};
+  }, "{project strips, backproject strips, f32 elements of a partial buffer serving both products}",
+         pybind11::arg("rows"), pybind11::arg("cols"));
+  lr.def("project", &lowrank_project, "part[strip][rows][16] = (g + e)[:, strip] q[strip]", pybind11::arg("g"),
+         pybind11::arg("e"), pybind11::arg("q"), pybind11::arg("part"), pybind11::arg("rows"), pybind11::arg("cols"));
+  lr.def("backproject", &lowrank_backproject, "part[strip][cols][16] = (g + e)[strip, :]^T ph[strip]",
+         pybind11::arg("g"), pybind11::arg("e"), pybind11::arg("ph"), pybind11::arg("part"), pybind11::arg("rows"),
+         pybind11::arg("cols"));
+  lr.def("combine", &lowrank_combine, "out = the first `slabs` slabs of part, added in slab order",
+         pybind11::arg("part"), pybind11::arg("slabs"), pybind11::arg("out"));
+  lr.def("orth", &lowrank_orth, "p[rows][16] -> orthonormal columns 0..rank-1 in place (modified Gram-Schmidt)",
+         pybind11::arg("p"), pybind11::arg("rank"));
+  lr.def("reconstruct", &lowrank_reconstruct, "q_out = qn * inv; g <- ph q_out^T; e <- (g + e) - that",
+         pybind11::arg("g"), pybind11::arg("e"), pybind11::arg("ph"), pybind11::arg("qn"), pybind11::arg("q_out"),
+         pybind11::arg("inv"), pybind11::arg("rows"), pybind11::arg("cols"));
 }
 
 void register_planner(pybind11::module_& m) {

@@ -91,7 +91,12 @@ def run(argv=None, out=sys.stdout):
             from ..parallel.transport import ThreadFabric
 
             transport = ThreadFabric(1).transport(0)
-    kind = cfg.compress if transport is not None else "local"
+    reducer = None
+    if cfg.compress == "powersgd":  # the engine-less trainer; the reducer holds the transport
+        from ..parallel.lowrank import LowRankReducer
+
+        reducer = LowRankReducer(transport if world > 1 else None, cfg.rank, seed=cfg.lowrank_seed)
+    kind = cfg.compress if transport is not None and reducer is None else "local"
     impl = cfg.engine if device.type == "cuda" else "python"
     engine = make_engine(transport, kind, rounding=cfg.rounding, algo=cfg.algo, rings=cfg.rings,
                          max_slice_elems=cfg.slice_elems, compat_owner_fp32=cfg.compat_owner_fp32,
@@ -123,7 +128,7 @@ def run(argv=None, out=sys.stdout):
                                   error_feedback=cfg.error_feedback,
                                   error_feedback_codec=f"bfp_{cfg.rounding}",
                                   stochastic_rounding=cfg.stochastic_rounding, sr_seed=cfg.sr_seed,
-                                  moment_codec=cfg.moment_codec)
+                                  moment_codec=cfg.moment_codec, lowrank=reducer)
     trainer.opt_step = opt_step
     trainer.sr_step = sr_step
     x, y = make_data(mb, sizes[0], sizes[-1], rank, cfg.seed, device, dtype)
@@ -170,6 +175,9 @@ def run(argv=None, out=sys.stdout):
                 c = engine.counters()
                 print(f"ALLREDUCE host wait = {c['host_wait_s'] / max(1, cfg.iters):.6g} s/iter "
                       f"({c['host_waits']} blocking waits, {c['requests']} requests)", file=out)
+        if reducer is not None:
+            print(f"ALLREDUCE: powersgd rank={reducer.rank} "
+                  f"wire_bytes/step={sum(reducer.wire_bytes(l) for l in model.layers):.4g}", file=out)
     if a.dump_norms and rank == world - 1:  # the reference prints from the last rank
         for i, l in enumerate(model.layers):
             print(f"L1 of layer's {i} dweights after training : {float(l.gw.double().abs().sum()):.25g}", file=out)

@@ -3,7 +3,7 @@
 Reference knobs and where they went:
   iters / MB / fuse_type / type / bn bk bc / C1..CN  -> positional CLI, kept (sw/mlp_mpi_example_f32.cpp:270-320)
   NUM_NODES=3 (sw:38)                               -> world size from the launcher (any N >= 1)
-  `BFP_EN (hw/all_reduce.sv:13)                     -> compress = bfp | bfp4 | sign | raw | rccl | local
+  `BFP_EN (hw/all_reduce.sv:13)                     -> compress = bfp | bfp4 | sign | raw | rccl | local | powersgd
   NUM_FP=16, MANT_SIZE=8 (hw/bfp_adapter.sv:34-36)   -> group of 16; 8-bit mantissas (bfp; rounding = rne | trunc, the
                                                         bit-exact ref) or 4-bit (bfp4, rne only)
   BUF_SIZE=512 CL slice (hw/all_reduce.sv:102)      -> slice_elems (ring)
@@ -28,7 +28,9 @@ class TrainConfig:
     bc: int = 64
     sizes: list = field(default_factory=lambda: [1024, 4096, 4096, 1024])
     dtype: str = "bf16"            # bf16 | f32
-    compress: str = "bfp"          # bfp | bfp4 | sign | raw | raw_bf16 | rccl | local
+    compress: str = "bfp"          # bfp | bfp4 | sign | raw | raw_bf16 | rccl | local | powersgd
+    rank: int = 4                  # powersgd: the rank of the approximation, 1..16
+    lowrank_seed: int = 0          # powersgd: seed of the initial Q factors (the same on every rank)
     rounding: str = "rne"          # rne | trunc
     algo: str = "mesh"             # mesh | ring
     rings: int = 1
@@ -75,11 +77,18 @@ def add_named_flags(ap: argparse.ArgumentParser):
     d = TrainConfig()
     ap.add_argument("--dtype", default=d.dtype, choices=["bf16", "f32"])
     ap.add_argument("--compress", default=d.compress,
-                    choices=["bfp", "bfp4", "sign", "raw", "raw_bf16", "rccl", "local"],
+                    choices=["bfp", "bfp4", "sign", "raw", "raw_bf16", "rccl", "local", "powersgd"],
                     help="wire format of the all-reduce: bfp = 8-bit mantissas (17 B per 16 values), bfp4 = 4-bit "
                          "mantissas (9 B per 16 values, --rounding rne only; meant for use with --error-feedback), "
                          "sign = one sign bit per value and a power-of-two scale per group (codec sign1, 3 B per 16 "
-                         "values; needs --error-feedback, --rounding rne only)")
+                         "values; needs --error-feedback, --rounding rne only), powersgd = PowerSGD low-rank compression "
+                         "(each layer crosses the transport as (rows + cols) x --rank f32 numbers; engine-less trainer "
+                         "over the chosen transport, own residual: not with --error-feedback or "
+                         "--stochastic-rounding; layer widths multiples of 16; its residual and factors are not "
+                         "checkpointed: --resume restarts them at zero and from --lowrank-seed)")
+    ap.add_argument("--rank", type=int, default=d.rank, help="--compress powersgd: rank of the approximation, 1..16")
+    ap.add_argument("--lowrank-seed", type=int, default=d.lowrank_seed,
+                    help="--compress powersgd: seed of the initial Q factors")
     ap.add_argument("--rounding", default=d.rounding, choices=["rne", "trunc"])
     ap.add_argument("--algo", default=d.algo, choices=["mesh", "ring"])
     ap.add_argument("--rings", type=int, default=d.rings)
@@ -163,4 +172,10 @@ def config_from_args(a, positional_sizes=None) -> TrainConfig:
     if c.compress == "sign" and not c.error_feedback:
         raise ValueError("--compress sign: sign1 needs error feedback (--error-feedback): one bit per value converges "
                          "only with the residual carried over")
+    if c.compress == "powersgd":
+        if not 1 <= c.rank <= 16:
+            raise ValueError(f"--rank must lie in 1..16, got {c.rank}")
+        if c.error_feedback or c.stochastic_rounding:
+            raise ValueError("--compress powersgd keeps its own residual: not with --error-feedback or "
+                             "--stochastic-rounding")
     return c

@@ -92,8 +92,17 @@ class DataParallelTrainer:
                  betas=None, eps: float = 1e-8, trust_ratio: bool = False,
                  max_grad_norm: float | None = None, error_feedback: bool = False,
                  error_feedback_codec: str = "bfp_rne", stochastic_rounding: bool = False, sr_seed: int = 0,
-                 moment_codec: str = "f32"):
-        """``moment_codec``: 'f32' (the model's f32 moment planes) or 'bfp8' (AdamW only): both moments of every layer
+                 moment_codec: str = "f32", lowrank=None):
+        """``lowrank``: a :class:`~fpga_ai_nic_amd.parallel.lowrank.LowRankReducer` — PowerSGD low-rank compression on
+        the engine-less trainer (``engine`` must be None; the reducer holds the transport). After each layer's
+        bwd-weight GEMM the reducer replaces the layer's f32 gradient by the rank-averaged rank-r approximation (two
+        small synchronous all-reduces) and the local update reads it as ``raw_f32``, so every ``optimizer``,
+        ``trust_ratio``, ``moment_codec`` and ``max_grad_norm`` run unchanged; the gradient is already the mean, so
+        ``grad_scale`` stays 1. Not with ``error_feedback`` or ``stochastic_rounding`` (the reducer owns its own
+        residual: ``lowrank_residuals``, and the warm-started factors ``lowrank_q``; neither is checkpointed). Layer
+        widths must be multiples of 16 and at least the rank.
+
+        ``moment_codec``: 'f32' (the model's f32 moment planes) or 'bfp8' (AdamW only): both moments of every layer
         live in 8-bit block-floating-point planes (``wire.moment_plane``: 2.125 B per parameter instead of 8, the
         second holding sqrt(v)), which the trainer allocates zeroed in place of the model's ``mom`` / ``var`` unless
         the model already holds them (``MLP(..., adam=True, moment_codec="bfp8")``, a resumed run). Every layer's
@@ -261,6 +270,16 @@ class DataParallelTrainer:
                 raise ValueError("max_grad_norm: not with a sharded-update engine (each owner updates its shard before "
                                  "the bucket is reduced)")
             self.grad_norm = torch.zeros(4, dtype=torch.float32, device=model.device)
+        self.lowrank = lowrank
+        if lowrank is not None:
+            if engine is not None:
+                raise ValueError("lowrank: on the engine-less trainer only (engine=None; the reducer holds the "
+                                 "transport)")
+            if error_feedback or stochastic_rounding:
+                raise ValueError("lowrank: not with error_feedback or stochastic_rounding (the reducer owns its own "
+                                 "residual)")
+            for l in model.layers:
+                lowrank.state_for(l)  # (refuses a layer shape the kernels do not take)
         self.error_feedback = bool(error_feedback)
         self.residuals = None
         self._ef_wire = None  # the engine-less trainer's one-slot wire, per layer
@@ -363,6 +382,16 @@ class DataParallelTrainer:
             # an on-producer request's epilogue runs on the compute stream; with the others' on the comm stream the
             # group's one coefficient launch could not precede them all
             self.last_on_producer = False
+
+    @property
+    def lowrank_residuals(self):
+        """Every layer's PowerSGD residual plane (cin * cout f32), or None without ``lowrank``."""
+        return None if self.lowrank is None else [self.lowrank.state_for(l).e for l in self.m.layers]
+
+    @property
+    def lowrank_q(self):
+        """Every layer's warm-started Q ([cout][16] f32), or None without ``lowrank``."""
+        return None if self.lowrank is None else [self.lowrank.state_for(l).q for l in self.m.layers]
 
     def _opt_kw(self, l):
         """The optimizer, clip-group, error-feedback and stochastic-rounding arguments of layer l's request in the step
@@ -609,6 +638,8 @@ class DataParallelTrainer:
                             self._ef_local(l)
                         elif self.stochastic_rounding:
                             self._sr_local(l)
+                        elif self.lowrank is not None:
+                            self.lowrank.reduce(l)
                         m.backward_data(i)
                         if h is not None:
                             clipped = self.grad_norm is not None  # (commits with its group, below)
