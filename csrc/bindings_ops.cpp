@@ -7,6 +7,7 @@
 #include "gemm/gemm_group.h"
 #include "lowrank/lowrank.h"
 #include "nn/nn.h"
+#include "topk/topk.h"
 
 namespace fan {
 
@@ -729,6 +730,47 @@ void lowrank_reconstruct(at::Tensor& g, at::Tensor& e, const at::Tensor& ph, con
                              cols, fan_stream());
 }
 
+// ---- top-k sparsification (topk/topk.h). g and e: contiguous f32 planes of n_pad elements on one GPU; the wire and
+// the scratch of exactly the length topk_layout gives, so nothing behind them is reachable.
+void tk_plane(const at::Tensor& t, at::ScalarType ty, int64_t n, const at::Tensor& ref, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == ty && t.device() == ref.device() &&
+                  t.numel() == n,
+              "topk: ", what, " must be a contiguous ", ty, " tensor of ", n, " elements on the gradient's GPU");
+}
+
+void tk_shape(int64_t n_pad, int64_t n, int64_t k, int64_t max_blocks) {
+  TORCH_CHECK(n_pad > 0 && n_pad % 4 == 0 && n_pad < ((int64_t)1 << 31),
+              "topk: n_pad must be a positive multiple of 4 below 2^31, got ", n_pad);
+  TORCH_CHECK(n >= 1 && n <= n_pad && k >= 1 && k <= n, "topk: 1 <= k <= n <= n_pad, got k = ", k, ", n = ", n);
+  TORCH_CHECK(max_blocks >= 0 && max_blocks <= INT32_MAX, "topk: max_blocks >= 0");
+}
+
+void topk_select(const at::Tensor& g, at::Tensor& e, at::Tensor& wire, at::Tensor& scratch, int64_t n, int64_t k,
+                 int64_t max_blocks, int64_t stages) {
+  const int64_t n_pad = g.numel();
+  tk_shape(n_pad, n, k, max_blocks);
+  const TopkLayout L = topk_layout(n_pad, k);
+  tk_plane(g, at::kFloat, n_pad, g, "g");
+  tk_plane(e, at::kFloat, n_pad, g, "e");
+  tk_plane(wire, at::kByte, L.wire_bytes, g, "wire");
+  tk_plane(scratch, at::kInt, L.scratch_words, g, "scratch");
+  TORCH_CHECK(g.data_ptr() != e.data_ptr(), "topk: e must not be g");
+  launch_topk_select(g.data_ptr<float>(), e.data_ptr<float>(), wire.data_ptr(),
+                     reinterpret_cast<uint32_t*>(scratch.data_ptr<int32_t>()), n_pad, n, k, (int)max_blocks,
+                     fan_stream(), (int)(stages & kTopkAllStages));
+}
+
+void topk_accumulate(const at::Tensor& wires, int64_t world, at::Tensor& g, int64_t n, int64_t k, double inv,
+                     int64_t max_blocks) {
+  const int64_t n_pad = g.numel();
+  tk_shape(n_pad, n, k, max_blocks);
+  TORCH_CHECK(world >= 1 && world <= kTopkMaxWorld, "topk: 1..16 ranks, got ", world);
+  tk_plane(g, at::kFloat, n_pad, g, "g");
+  tk_plane(wires, at::kByte, world * topk_layout(n_pad, k).wire_bytes, g, "wires");
+  launch_topk_accumulate(wires.data_ptr(), (int)world, g.data_ptr<float>(), n_pad, n, k, (float)inv, (int)max_blocks,
+                         fan_stream());
+}
+
 }  // namespace
 
 void register_gemm(pybind11::module_& m) {
@@ -875,6 +917,19 @@ void register_nn(pybind11::module_& m) {
   lr.def("reconstruct", &lowrank_reconstruct, "q_out = qn * inv; g <- ph q_out^T; e <- (g + e) - that",
          pybind11::arg("g"), pybind11::arg("e"), pybind11::arg("ph"), pybind11::arg("qn"), pybind11::arg("q_out"),
          pybind11::arg("inv"), pybind11::arg("rows"), pybind11::arg("cols"));
+  pybind11::module_ tk = m.def_submodule("topk", "top-k gradient sparsification kernels");
+  tk.def("layout", [](int64_t n_pad, int64_t k) {
+    const TopkLayout L = topk_layout(n_pad, k);
+    return std::vector<int64_t>{L.tiles, L.scratch_words, L.wire_bytes};
+  }, "{tiles, int32 words of the select scratch, bytes of one wire}", pybind11::arg("n_pad"), pybind11::arg("k"));
+  tk.def("select", &topk_select,
+         "e = g + e (i < n); wire = the k largest |e| ascending by index; e = +0 where sent. The scratch is zeroed "
+         "once by the caller. stages: bit i enables launch i (hist, pick per digit; count; scan; compact)",
+         pybind11::arg("g"), pybind11::arg("e"), pybind11::arg("wire"), pybind11::arg("scratch"), pybind11::arg("n"),
+         pybind11::arg("k"), pybind11::arg("max_blocks") = 0, pybind11::arg("stages") = (int64_t)kTopkAllStages);
+  tk.def("accumulate", &topk_accumulate, "g[i] = (the ranks' values at i, added in rank order from +0) * inv, i < n",
+         pybind11::arg("wires"), pybind11::arg("world"), pybind11::arg("g"), pybind11::arg("n"), pybind11::arg("k"),
+         pybind11::arg("inv"), pybind11::arg("max_blocks") = 0);
 }
 
 void register_planner(pybind11::module_& m) {

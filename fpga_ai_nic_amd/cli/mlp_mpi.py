@@ -96,7 +96,12 @@ def run(argv=None, out=sys.stdout):
         from ..parallel.lowrank import LowRankReducer
 
         reducer = LowRankReducer(transport if world > 1 else None, cfg.rank, seed=cfg.lowrank_seed)
-    kind = cfg.compress if transport is not None and reducer is None else "local"
+    sparse = None
+    if cfg.compress == "topk":  # the engine-less trainer as well
+        from ..parallel.sparse import TopKReducer
+
+        sparse = TopKReducer(transport if world > 1 else None, cfg.density)
+    kind = cfg.compress if transport is not None and reducer is None and sparse is None else "local"
     impl = cfg.engine if device.type == "cuda" else "python"
     engine = make_engine(transport, kind, rounding=cfg.rounding, algo=cfg.algo, rings=cfg.rings,
                          max_slice_elems=cfg.slice_elems, compat_owner_fp32=cfg.compat_owner_fp32,
@@ -128,7 +133,7 @@ def run(argv=None, out=sys.stdout):
                                   error_feedback=cfg.error_feedback,
                                   error_feedback_codec=f"bfp_{cfg.rounding}",
                                   stochastic_rounding=cfg.stochastic_rounding, sr_seed=cfg.sr_seed,
-                                  moment_codec=cfg.moment_codec, lowrank=reducer)
+                                  moment_codec=cfg.moment_codec, lowrank=reducer, topk=sparse)
     trainer.opt_step = opt_step
     trainer.sr_step = sr_step
     x, y = make_data(mb, sizes[0], sizes[-1], rank, cfg.seed, device, dtype)
@@ -178,6 +183,9 @@ def run(argv=None, out=sys.stdout):
         if reducer is not None:
             print(f"ALLREDUCE: powersgd rank={reducer.rank} "
                   f"wire_bytes/step={sum(reducer.wire_bytes(l) for l in model.layers):.4g}", file=out)
+        if sparse is not None:
+            print(f"ALLREDUCE: topk density={sparse.density:g} "
+                  f"wire_bytes/step={sum(sparse.wire_bytes(l) for l in model.layers):.4g}", file=out)
     if a.dump_norms and rank == world - 1:  # the reference prints from the last rank
         for i, l in enumerate(model.layers):
             print(f"L1 of layer's {i} dweights after training : {float(l.gw.double().abs().sum()):.25g}", file=out)

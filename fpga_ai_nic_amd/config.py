@@ -3,7 +3,8 @@
 Reference knobs and where they went:
   iters / MB / fuse_type / type / bn bk bc / C1..CN  -> positional CLI, kept (sw/mlp_mpi_example_f32.cpp:270-320)
   NUM_NODES=3 (sw:38)                               -> world size from the launcher (any N >= 1)
-  `BFP_EN (hw/all_reduce.sv:13)                     -> compress = bfp | bfp4 | sign | raw | rccl | local | powersgd
+  `BFP_EN (hw/all_reduce.sv:13)                     -> compress = bfp | bfp4 | sign | raw | rccl | local | powersgd |
+                                                        topk
   NUM_FP=16, MANT_SIZE=8 (hw/bfp_adapter.sv:34-36)   -> group of 16; 8-bit mantissas (bfp; rounding = rne | trunc, the
                                                         bit-exact ref) or 4-bit (bfp4, rne only)
   BUF_SIZE=512 CL slice (hw/all_reduce.sv:102)      -> slice_elems (ring)
@@ -28,9 +29,10 @@ class TrainConfig:
     bc: int = 64
     sizes: list = field(default_factory=lambda: [1024, 4096, 4096, 1024])
     dtype: str = "bf16"            # bf16 | f32
-    compress: str = "bfp"          # bfp | bfp4 | sign | raw | raw_bf16 | rccl | local | powersgd
+    compress: str = "bfp"          # bfp | bfp4 | sign | raw | raw_bf16 | rccl | local | powersgd | topk
     rank: int = 4                  # powersgd: the rank of the approximation, 1..16
     lowrank_seed: int = 0          # powersgd: seed of the initial Q factors (the same on every rank)
+    density: float = 0.01          # topk: the fraction of a bucket each rank sends, in (0, 1]
     rounding: str = "rne"          # rne | trunc
     algo: str = "mesh"             # mesh | ring
     rings: int = 1
@@ -77,7 +79,7 @@ def add_named_flags(ap: argparse.ArgumentParser):
     d = TrainConfig()
     ap.add_argument("--dtype", default=d.dtype, choices=["bf16", "f32"])
     ap.add_argument("--compress", default=d.compress,
-                    choices=["bfp", "bfp4", "sign", "raw", "raw_bf16", "rccl", "local", "powersgd"],
+                    choices=["bfp", "bfp4", "sign", "raw", "raw_bf16", "rccl", "local", "powersgd", "topk"],
                     help="wire format of the all-reduce: bfp = 8-bit mantissas (17 B per 16 values), bfp4 = 4-bit "
                          "mantissas (9 B per 16 values, --rounding rne only; meant for use with --error-feedback), "
                          "sign = one sign bit per value and a power-of-two scale per group (codec sign1, 3 B per 16 "
@@ -85,10 +87,16 @@ def add_named_flags(ap: argparse.ArgumentParser):
                          "(each layer crosses the transport as (rows + cols) x --rank f32 numbers; engine-less trainer "
                          "over the chosen transport, own residual: not with --error-feedback or "
                          "--stochastic-rounding; layer widths multiples of 16; its residual and factors are not "
-                         "checkpointed: --resume restarts them at zero and from --lowrank-seed)")
+                         "checkpointed: --resume restarts them at zero and from --lowrank-seed), topk = top-k "
+                         "sparsification with memory (each rank sends the --density largest-magnitude fraction of "
+                         "every bucket as 8 B index/value pairs, one all-gather per bucket; engine-less trainer, own "
+                         "residual, not checkpointed: not with --error-feedback or --stochastic-rounding; at most 16 "
+                         "ranks)")
     ap.add_argument("--rank", type=int, default=d.rank, help="--compress powersgd: rank of the approximation, 1..16")
     ap.add_argument("--lowrank-seed", type=int, default=d.lowrank_seed,
                     help="--compress powersgd: seed of the initial Q factors")
+    ap.add_argument("--density", type=float, default=d.density,
+                    help="--compress topk: fraction of every bucket each rank sends, in (0, 1]")
     ap.add_argument("--rounding", default=d.rounding, choices=["rne", "trunc"])
     ap.add_argument("--algo", default=d.algo, choices=["mesh", "ring"])
     ap.add_argument("--rings", type=int, default=d.rings)
@@ -177,5 +185,11 @@ def config_from_args(a, positional_sizes=None) -> TrainConfig:
             raise ValueError(f"--rank must lie in 1..16, got {c.rank}")
         if c.error_feedback or c.stochastic_rounding:
             raise ValueError("--compress powersgd keeps its own residual: not with --error-feedback or "
+                             "--stochastic-rounding")
+    if c.compress == "topk":
+        if not 0.0 < c.density <= 1.0:
+            raise ValueError(f"--density must lie in (0, 1], got {c.density}")
+        if c.error_feedback or c.stochastic_rounding:
+            raise ValueError("--compress topk keeps its own residual: not with --error-feedback or "
                              "--stochastic-rounding")
     return c
