@@ -78,9 +78,12 @@ void gemm(const at::Tensor& A, bool a_t, const at::Tensor& B, bool b_t, at::Tens
           int64_t wire_shard, int64_t wire_own, int64_t wire_codec, int64_t wire_period, int64_t wire_off,
           const c10::optional<at::Tensor>& upd_master, const c10::optional<at::Tensor>& upd_lp,
           const c10::optional<at::Tensor>& upd_mom, double upd_lr, double upd_grad_scale, double upd_weight_decay,
-          double upd_momentum, bool upd_nesterov, bool defer_colsum, bool defer_reduce) {
+          double upd_momentum, bool upd_nesterov, bool defer_colsum, bool defer_reduce, int64_t precision) {
   TORCH_CHECK(A.is_cuda() && B.is_cuda() && C.is_cuda(), "gemm operands must be GPU tensors");
   TORCH_CHECK(A.scalar_type() == B.scalar_type(), "A and B dtype mismatch");
+  TORCH_CHECK(precision == 0 || precision == 1, "gemm: precision 0 (the operand dtype's kernel) or 1 (bf16x3)");
+  TORCH_CHECK(precision == 0 || (A.scalar_type() == at::kFloat && C.scalar_type() == at::kFloat),
+              "gemm: precision 1 (bf16x3) takes f32 operands and an f32 output");
   GemmArgs g{};
   g.A = A.data_ptr();
   g.B = B.data_ptr();
@@ -151,6 +154,13 @@ void gemm(const at::Tensor& A, bool a_t, const at::Tensor& B, bool b_t, at::Tens
       TORCH_CHECK(workspace && workspace->scalar_type() == at::kFloat && workspace->is_contiguous() &&
                       workspace->numel() >= need,
                   "gemm_f32: split-K ", sk, " needs an f32 workspace of ", need, " elements");
+    }
+    if (precision == 1) {
+      TORCH_CHECK(!bias || bias->scalar_type() == at::kFloat, "gemm_f32x3: bias must be f32");
+      TORCH_CHECK(gemm_f32x3_supported(g), "gemm_f32x3: unsupported shape M=", g.M, " N=", g.N, " K=", g.K,
+                  " epilogue=", g.epilogue, " (f32 output; no colsum, wire epilogue or deferred reduce)");
+      launch_gemm_f32x3(g, fan_stream());
+      return;
     }
     TORCH_CHECK(gemm_f32_supported(g), "gemm_f32: unsupported shape M=", g.M, " N=", g.N, " K=", g.K);
     launch_gemm_f32(g, fan_stream());
@@ -785,7 +795,7 @@ void register_gemm(pybind11::module_& m) {
         pybind11::arg("upd_mom") = pybind11::none(), pybind11::arg("upd_lr") = 0.0,
         pybind11::arg("upd_grad_scale") = 1.0, pybind11::arg("upd_weight_decay") = 0.0,
         pybind11::arg("upd_momentum") = 0.0, pybind11::arg("upd_nesterov") = false,
-        pybind11::arg("defer_colsum") = false, pybind11::arg("defer_reduce") = false);
+        pybind11::arg("defer_colsum") = false, pybind11::arg("defer_reduce") = false, pybind11::arg("precision") = 0);
   m.def("gemm_supported", &gemm_supported);
   m.def("gemm_flush_colsum", []() { return gemm_flush_colsum(fan_stream()); },
         "launch the bias-gradient reduces queued on the current stream by defer_colsum GEMMs; returns how many");

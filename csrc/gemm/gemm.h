@@ -114,4 +114,11 @@ int gemm_f32_split(int M, int N, int K, int split_k);
 bool gemm_f32_supported(const GemmArgs& a);
 void launch_gemm_f32(const GemmArgs& a, hipStream_t stream);
 
+// bf16x3 split-precision GEMM (gemm_f32x3.hip): launch_gemm_f32's contract (f32 A, B, C, bias, aux; all layouts; the
+// four plain epilogues; accumulate; split-K by gemm_f32_split with f32 slabs in workspace) with every product computed
+// as three bf16 MFMAs on the (hi, lo) bf16 pieces of the f32 operands. False for c_bf16, colsum, defer_reduce and the
+// wire epilogues.
+bool gemm_f32x3_supported(const GemmArgs& a);
+void launch_gemm_f32x3(const GemmArgs& a, hipStream_t stream);
+
 }  // namespace fan

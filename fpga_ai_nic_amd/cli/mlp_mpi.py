@@ -114,7 +114,7 @@ def run(argv=None, out=sys.stdout):
         bias, relu = {1: (True, "none"), 2: (False, "all"), 3: (True, "all")}.get(a.fuse_type, (False, "none"))
     model = MLP(sizes, dtype=dtype, device=device, pad_fn=pad_fn, seed=cfg.seed,
                 momentum=cfg.momentum > 0 or cfg.optimizer == "lion", bias=bias, relu=relu, adam=cfg.optimizer == "adamw",
-                moment_codec=cfg.moment_codec if cfg.optimizer == "adamw" else "f32")
+                moment_codec=cfg.moment_codec if cfg.optimizer == "adamw" else "f32", f32_gemm=cfg.f32_gemm)
     if world > 1:  # reference C3/C4: broadcast weights + bias from rank 0
         for l in model.layers:
             transport.broadcast_(l.master, 0)

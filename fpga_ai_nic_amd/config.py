@@ -29,6 +29,7 @@ class TrainConfig:
     bc: int = 64
     sizes: list = field(default_factory=lambda: [1024, 4096, 4096, 1024])
     dtype: str = "bf16"            # bf16 | f32
+    f32_gemm: str = "mfma"         # --dtype f32: mfma (exact f32 MFMA GEMM) | bf16x3 (split precision, 3 bf16 MFMAs)
     compress: str = "bfp"          # bfp | bfp4 | sign | raw | raw_bf16 | rccl | local | powersgd | topk
     rank: int = 4                  # powersgd: the rank of the approximation, 1..16
     lowrank_seed: int = 0          # powersgd: seed of the initial Q factors (the same on every rank)
@@ -78,6 +79,10 @@ class TrainConfig:
 def add_named_flags(ap: argparse.ArgumentParser):
     d = TrainConfig()
     ap.add_argument("--dtype", default=d.dtype, choices=["bf16", "f32"])
+    ap.add_argument("--f32-gemm", default=d.f32_gemm, choices=["mfma", "bf16x3"],
+                    help="--dtype f32: the GEMM of every layer product; mfma = the exact f32 MFMA kernel, bf16x3 = "
+                         "f32 operands split in registers into two bf16 pieces each, three bf16 MFMAs per product "
+                         "(about 2^-14.4 relative per product)")
     ap.add_argument("--compress", default=d.compress,
                     choices=["bfp", "bfp4", "sign", "raw", "raw_bf16", "rccl", "local", "powersgd", "topk"],
                     help="wire format of the all-reduce: bfp = 8-bit mantissas (17 B per 16 values), bfp4 = 4-bit "
@@ -175,6 +180,8 @@ def config_from_args(a, positional_sizes=None) -> TrainConfig:
             setattr(c, key, getattr(a, key))
     if positional_sizes:
         c.sizes = list(positional_sizes)
+    if c.f32_gemm != "mfma" and c.dtype != "f32":
+        raise ValueError(f"--f32-gemm {c.f32_gemm} selects the GEMM of the f32 path: it needs --dtype f32")
     if c.compress in ("bfp4", "sign"):
         wire_codec(c.compress, c.rounding)  # (--rounding trunc: a ValueError)
     if c.compress == "sign" and not c.error_feedback:

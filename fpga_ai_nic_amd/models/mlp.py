@@ -67,16 +67,24 @@ class MLP:
 
     def __init__(self, sizes, *, dtype=torch.bfloat16, device="cpu", pad_fn=None, seed: int = 1,
                  momentum: bool = False, init_scale: float | None = None, bias: bool = True,
-                 relu: str = "hidden", adam: bool = False, moment_codec: str = "f32"):
+                 relu: str = "hidden", adam: bool = False, moment_codec: str = "f32", f32_gemm: str = "mfma"):
         """``momentum``: allocate the f32 momentum plane ``mom`` per layer (SGD's momentum, or Lion's one moment);
         ``adam``: allocate both AdamW moment planes per layer (``mom`` the first, ``var`` the second);
         ``moment_codec="bfp8"``: as 8-bit planes (uint8, ``n_pad * 17 / 16`` bytes each, ``var`` holding sqrt(v):
         ``ops/bfp_oracle.py`` adamw_q), zeroed — the zero state.
         ``bias`` / ``relu`` select the layer epilogue. ``relu``: 'hidden' (every layer but the classifier,
         the default model), 'all' or 'none'. The reference's fuse_type (sw:479-489) maps to
-        0 -> (bias=False, relu='none'), 1 -> (True, 'none'), 2 -> (False, 'all'), 3 -> (True, 'all')."""
+        0 -> (bias=False, relu='none'), 1 -> (True, 'none'), 2 -> (False, 'all'), 3 -> (True, 'all').
+        ``f32_gemm`` (``dtype=torch.float32`` only): 'mfma' (the exact f32 MFMA GEMM) or 'bf16x3' (every forward,
+        bwd-data and bwd-weight GEMM on the split-precision kernel, ops/gemm.py ``precision="bf16x3"``)."""
         if len(sizes) < 2:
             raise ValueError("need at least one layer")
+        if f32_gemm not in ("mfma", "bf16x3"):
+            raise ValueError(f"f32_gemm must be mfma|bf16x3, got {f32_gemm!r}")
+        if f32_gemm != "mfma" and dtype != torch.float32:
+            raise ValueError(f"f32_gemm={f32_gemm!r} selects the GEMM of the f32 path: dtype=torch.float32")
+        self.f32_gemm = f32_gemm
+        self._prec = "bf16x3" if f32_gemm == "bf16x3" else None  # gemm(precision=): None is the default dispatch
         if relu not in ("hidden", "all", "none"):
             raise ValueError(f"relu must be hidden|all|none, got {relu!r}")
         if moment_codec not in ("f32", "bfp8"):
@@ -197,7 +205,8 @@ class MLP:
         self._slabs = None
         if fold_logits and i + 1 == self.L and out.is_cuda and self.dtype == torch.bfloat16 and not self._relu_at(i):
             self._slabs = {}
-        G.linear_fwd(self.act[i], l.w, self._bias_of(l), out, relu=self._relu_at(i), defer_reduce=self._slabs)
+        G.linear_fwd(self.act[i], l.w, self._bias_of(l), out, relu=self._relu_at(i), defer_reduce=self._slabs,
+                     precision=self._prec)
 
     def forward_chain(self) -> bool:
         """Every layer's forward GEMM as ONE layer-chain launch (GPU bf16; ops/gemm.py linear_chain); False when the
@@ -243,11 +252,11 @@ class MLP:
             G.linear_bwd_weight(self.act[i], self.dz[i + 1], l.gw, bias_grad=l.gb if self.bias else None, wire=wire,
                                 update=update, defer_colsum=defer_colsum, split_k=split_k, tile=tile)
         elif not self.bias:
-            G.linear_bwd_weight(self.act[i], self.dz[i + 1], l.gw)
+            G.linear_bwd_weight(self.act[i], self.dz[i + 1], l.gw, precision=self._prec)
         elif l.gw.is_cuda and self.dtype == torch.bfloat16:  # bias gradient fused into the bwd-weight GEMM
             G.linear_bwd_weight(self.act[i], self.dz[i + 1], l.gw, bias_grad=l.gb)
         else:
-            G.linear_bwd_weight(self.act[i], self.dz[i + 1], l.gw)
+            G.linear_bwd_weight(self.act[i], self.dz[i + 1], l.gw, precision=self._prec)
             NN.col_sum(self.dz[i + 1], l.gb)
 
     def wgrad_problem(self, i: int):
@@ -267,7 +276,8 @@ class MLP:
         if i == 0:
             return
         l = self.layers[i]
-        G.linear_bwd_data(self.dz[i + 1], l.w, self.dz[i], relu_input=self.act[i] if self._relu_at(i - 1) else None)
+        G.linear_bwd_data(self.dz[i + 1], l.w, self.dz[i], relu_input=self.act[i] if self._relu_at(i - 1) else None,
+                          precision=self._prec)
 
     def forward(self, x):
         """Inference forward (returns f32 logits)."""

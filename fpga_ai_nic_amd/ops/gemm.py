@@ -55,8 +55,11 @@ def choose_split_k(M: int, N: int, K: int, target_wg: int = 256) -> int:
 
 def gemm(A, a_t: bool, B, b_t: bool, C, epilogue: int = EPI_NONE, bias=None, aux=None, accumulate=False,
          split_k: int | None = None, tile: tuple | None = None, colsum=None, wire=None, update=None,
-         defer_colsum: bool = False, defer_reduce: dict | None = None):
+         defer_colsum: bool = False, defer_reduce: dict | None = None, precision: str | None = None):
     """C = op(A)·op(B) with a fused epilogue. a_t: A given as [K][M]; b_t: B given as [N][K].
+    ``precision``: None / ``"f32"`` run the operand dtype's kernel; ``"bf16x3"`` (f32 operands and output only) the
+    split-precision kernel (csrc/gemm/gemm_f32x3.hip): each operand element x is split into h = bf16(x) and
+    l = bf16(x - h), and h_a·h_b + h_a·l_b + l_a·h_b accumulates in f32 (about 2^-14.4 relative per product).
     ``tile=(BM, BN)`` / ``split_k`` override the kernel planner (bf16 only).
     ``colsum`` (f32 [N]): also write sum_k B(k, n) — the fused bias gradient of bwd-weight (bf16, B [K][N]).
     ``wire=(buf_u8, shard_elems, own_shard, codec_id[, period[, off]])``: BFP-encode the f32 result straight into
@@ -74,6 +77,9 @@ def gemm(A, a_t: bool, B, b_t: bool, C, epilogue: int = EPI_NONE, bias=None, aux
     width and leading dimension (``ops.nn.softmax_xent_slabs_supported``), the slab reduce is not
     launched and C is NOT written — the dict receives ``ws`` (the slabs, [sk][M][N] f32) and ``sk`` for a consumer
     that folds them (:func:`fpga_ai_nic_amd.ops.nn.softmax_xent_slabs`); it stays empty when C was written."""
+    if precision not in (None, "f32"):
+        return _bf16x3(A, a_t, B, b_t, C, epilogue, bias, aux, accumulate, split_k, precision,
+                       dict(colsum=colsum, wire=wire, update=update, defer_reduce=defer_reduce))
     if wire is not None:
         if not C.is_cuda or A.dtype != torch.bfloat16 or not a_t or b_t:
             raise ValueError("wire epilogue: bf16 GPU bwd-weight layout only")
@@ -127,6 +133,49 @@ def gemm(A, a_t: bool, B, b_t: bool, C, epilogue: int = EPI_NONE, bias=None, aux
     C.copy_(r.to(C.dtype))
     if colsum is not None:
         colsum.copy_(b.sum(0).to(colsum.dtype))
+    return C
+
+
+def split_bf16(x):
+    """The bf16x3 pieces of an f32 tensor: h = bf16_rne(x), l = bf16_rne(x - h) (both as bf16 tensors)."""
+    h = x.to(torch.bfloat16)
+    return h, (x - h.float()).to(torch.bfloat16)
+
+
+def _bf16x3(A, a_t, B, b_t, C, epilogue, bias, aux, accumulate, split_k, precision, refused):
+    """``gemm(..., precision="bf16x3")``: the split-precision kernel on the GPU, its definition in torch on the CPU."""
+    if precision != "bf16x3":
+        raise ValueError(f"gemm: precision must be None, 'f32' or 'bf16x3', got {precision!r}")
+    if A.dtype != torch.float32 or B.dtype != torch.float32 or C.dtype != torch.float32:
+        raise ValueError(f"gemm: precision='bf16x3' splits f32 operands into bf16 pieces (f32 A, B and C), got "
+                         f"{A.dtype} / {B.dtype} / {C.dtype}")
+    for name, v in refused.items():
+        if v is not None:
+            raise ValueError(f"gemm: precision='bf16x3' does not take {name}= (plain epilogues only)")
+    if epilogue not in (EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_RELU_MASK):
+        raise ValueError(f"gemm: precision='bf16x3' has no epilogue {epilogue}")
+    if C.is_cuda:
+        Cx = _ext.require()
+        M = A.shape[1] if a_t else A.shape[0]
+        K = A.shape[0] if a_t else A.shape[1]
+        N = B.shape[0] if b_t else B.shape[1]
+        sk = Cx.gemm_f32_split(M, N, K, 0 if split_k is None else int(split_k))
+        ws = _workspace(C.device, sk * M * N) if sk > 1 else None
+        Cx.gemm(A, a_t, B, b_t, C, epilogue, bias, aux, accumulate, sk, ws, precision=1)
+        return C
+    # CPU: the same three products in float64 (each exact), one rounding to f32, then the epilogue
+    (ah, al), (bh, bl) = ((h.double(), l.double()) for h, l in (split_bf16(A.t() if a_t else A),
+                                                                split_bf16(B.t() if b_t else B)))
+    r = (ah @ bl + al @ bh + ah @ bh).float()
+    if epilogue in (EPI_BIAS, EPI_BIAS_RELU):
+        r = r + bias
+    if epilogue == EPI_BIAS_RELU:
+        r = torch.relu(r)
+    if epilogue == EPI_RELU_MASK:
+        r = r * (aux > 0)
+    if accumulate:
+        r = r + C
+    C.copy_(r)
     return C
 
 
@@ -429,21 +478,21 @@ def linear_chain(kind: int, a0, ws, outs, biases=None, auxes=None, epis=None, ke
                                           dry_run))
 
 
-def linear_fwd(x, w, b, out, relu: bool, defer_reduce: dict | None = None):
-    """Y = X · W + b (ReLU); ``defer_reduce`` (no ReLU): see :func:`gemm`."""
+def linear_fwd(x, w, b, out, relu: bool, defer_reduce: dict | None = None, precision=None):
+    """Y = X · W + b (ReLU); ``defer_reduce`` (no ReLU) and ``precision``: see :func:`gemm`."""
     return gemm(x, False, w, False, out, EPI_BIAS_RELU if relu else EPI_BIAS, bias=b,
-                defer_reduce=None if relu else defer_reduce)
+                defer_reduce=None if relu else defer_reduce, precision=precision)
 
 
-def linear_bwd_data(dz, w, out, relu_input=None):
+def linear_bwd_data(dz, w, out, relu_input=None, precision=None):
     """dX = dZ · Wᵀ, optionally masked by (relu_input > 0) (ReLU backward fused)."""
     if relu_input is not None:
-        return gemm(dz, False, w, True, out, EPI_RELU_MASK, aux=relu_input)
-    return gemm(dz, False, w, True, out, EPI_NONE)
+        return gemm(dz, False, w, True, out, EPI_RELU_MASK, aux=relu_input, precision=precision)
+    return gemm(dz, False, w, True, out, EPI_NONE, precision=precision)
 
 
 def linear_bwd_weight(x, dz, out, accumulate=False, bias_grad=None, wire=None, update=None, defer_colsum=False,
-                      split_k=None, tile=None):
+                      split_k=None, tile=None, precision=None):
     """dW = Xᵀ · dZ (f32 out); with ``bias_grad`` also db = colsum(dZ), fused into the same kernel; with
     ``wire`` dW is written BFP-encoded into the all-reduce wire buffer instead (see :func:`gemm`); with ``update``
     (single-rank engine) the encoded dW updates the weights in place instead (``defer_colsum``: the bias part
@@ -452,4 +501,4 @@ def linear_bwd_weight(x, dz, out, accumulate=False, bias_grad=None, wire=None, u
         return gemm(x, True, dz, False, out, EPI_WIRE, colsum=bias_grad, wire=wire, update=update,
                     defer_colsum=defer_colsum, split_k=split_k, tile=tile)
     return gemm(x, True, dz, False, out, EPI_NONE, accumulate=accumulate, colsum=bias_grad, split_k=split_k,
-                tile=tile)
+                tile=tile, precision=precision)
