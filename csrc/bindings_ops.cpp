@@ -730,6 +730,16 @@ void lowrank_orth(at::Tensor& p, int64_t rank) {
   launch_lowrank_orth(const_cast<float*>(lr_plane(p, p.numel(), true, p, "p")), p.size(0), (int)rank, fan_stream());
 }
 
+void lowrank_orth_cholqr2(at::Tensor& p, int64_t rank, at::Tensor& part) {
+  TORCH_CHECK(rank >= 1 && rank <= kLrRank, "lowrank: the rank must lie in 1..16, got ", rank);
+  TORCH_CHECK(p.dim() == 2 && p.size(1) == kLrRank && p.size(0) % 16 == 0 && rank <= p.size(0),
+              "lowrank orth: p is [rows][16] with rows a multiple of 16 and rank <= rows");
+  TORCH_CHECK(part.data_ptr() != p.data_ptr(), "lowrank orth: part must not be p");
+  float* pp = const_cast<float*>(lr_plane(p, p.numel(), true, p, "p"));
+  float* scratch = const_cast<float*>(lr_plane(part, lowrank_cholqr_part_elems(p.size(0)), false, p, "part"));
+  launch_lowrank_orth_cholqr2(pp, p.size(0), (int)rank, reinterpret_cast<double*>(scratch), fan_stream());
+}
+
 void lowrank_reconstruct(at::Tensor& g, at::Tensor& e, const at::Tensor& ph, const at::Tensor& qn, at::Tensor& q_out,
                          double inv, int64_t rows, int64_t cols) {
   lr_shape(g, e, rows, cols);
@@ -924,6 +934,10 @@ void register_nn(pybind11::module_& m) {
          pybind11::arg("part"), pybind11::arg("slabs"), pybind11::arg("out"));
   lr.def("orth", &lowrank_orth, "p[rows][16] -> orthonormal columns 0..rank-1 in place (modified Gram-Schmidt)",
          pybind11::arg("p"), pybind11::arg("rank"));
+  lr.def("orth_cholqr2", &lowrank_orth_cholqr2,
+         "p[rows][16] -> orthonormal columns 0..rank-1 in place by CholeskyQR2; part: at least 4 * ceil(rows / 256) "
+         "* 256 f32 elements of scratch",
+         pybind11::arg("p"), pybind11::arg("rank"), pybind11::arg("part"));
   lr.def("reconstruct", &lowrank_reconstruct, "q_out = qn * inv; g <- ph q_out^T; e <- (g + e) - that",
          pybind11::arg("g"), pybind11::arg("e"), pybind11::arg("ph"), pybind11::arg("qn"), pybind11::arg("q_out"),
          pybind11::arg("inv"), pybind11::arg("rows"), pybind11::arg("cols"));

@@ -5,7 +5,9 @@
 // and memory-bound: they run on v_mfma_f32_16x16x4_f32 with X straight from global memory in the instruction's A
 // layout (no LDS for X) and the small dense operand staged in LDS once per workgroup. No atomics, no last-block
 // fences: split-K partials land in slabs and lowrank_combine_kernel adds them in slab order, so every result is
-// independent of the grid and of the order in which workgroups run.
+// independent of the grid and of the order in which workgroups run. The orthogonalisation between the two products is
+// either modified Gram-Schmidt in one workgroup (lowrank_orth_kernel) or CholeskyQR2 over 256-row strips in three
+// launches (lowrank_gram_kernel, lowrank_cholqr_apply_kernel), whose 16 x 16 Gram matrices follow the same slab rule.
 //
 // v_mfma_f32_16x16x4_f32, D[16][16] += A[16][4] B[4][16]: lane l supplies A[l % 16][l / 16] and B[l / 16][l % 16] and
 // holds D[4 * (l / 16) + v][l % 16] in accumulator register v.
@@ -258,6 +260,176 @@ __global__ void __launch_bounds__(kOrthBlock) lowrank_orth_kernel(float* p, int 
   }
 }
 
+// ---------------------------------------------------------------- P^ = orth_cholqr2(P): three launches, in place
+// CholeskyQR2 (the oracle's orth_cholqr2): per pass W = A^T A in fp64, Rinv from the Jacobi-scaled Cholesky factor of
+// W, A <- A Rinv. The only dependency across rows is W, so every launch spreads over 256-row strips: the strips' Gram
+// matrices land in part[strip][16][16] and every workgroup of the next launch adds them in strip order and redoes the
+// few thousand flops of the factor for itself — the same bits everywhere, nobody waits for another workgroup.
+//
+// v_mfma_f64_16x16x4_f64, D[16][16] += A[16][4] B[4][16]: lane l supplies A[l % 16][l / 16] and B[l / 16][l % 16], one
+// double each, and holds D[4 * v + l / 16][l % 16] in accumulator register v. For W = X^T X over 4 rows of X the two
+// operands are the same number, X[l / 16][l % 16]: no LDS, no transposition.
+typedef double v4d __attribute__((ext_vector_type(4)));
+
+#define FAN_MFMA_F64_16x16x4(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
+
+constexpr double kCholPivotMin = 0x1p-40;
+
+// Lane `src`'s value of x, in every lane (src is the same in all of them: a scalar read, no LDS).
+__device__ __forceinline__ double lane_get(double x, int src) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), src),
+                          __builtin_amdgcn_readlane(__double2loint(x), src));
+}
+
+// The four waves' Gram accumulators, added in wave order, to out[16][16] (row-major); ws: 4 x 256 doubles of LDS.
+__device__ __forceinline__ void gram_store(v4d acc, double* ws, double* __restrict__ out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int v = 0; v < 4; ++v) ws[wave * 256 + (4 * v + (lane >> 4)) * kLrRank + (lane & 15)] = acc[v];
+  __syncthreads();
+  const int t = threadIdx.x;
+  out[t] = ((ws[t] + ws[256 + t]) + ws[512 + t]) + ws[768 + t];
+}
+
+// part[strip][16][16] = A[strip]^T A[strip]. Workgroup = strip of 256 rows, a wave 64 of them in 16 k-steps of 4 rows:
+// lane l loads the single float A[k0 + l / 16][l % 16] (the wave: 256 contiguous bytes), all 16 loads ahead of the
+// 16 dependent MFMAs. Rows past the end are not loaded (rows % 16 == 0 keeps k-steps whole).
+__global__ void __launch_bounds__(kBlock)
+    lowrank_gram_kernel(const float* __restrict__ a, double* __restrict__ part, int rows) {
+  __shared__ double ws[4 * 256];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int row0 = blockIdx.x * kLrOrthStrip + wave * 64 + (lane >> 4);
+  float x[16];
+#pragma unroll
+  for (int s = 0; s < 16; ++s) {
+    const int r = row0 + 4 * s;
+    x[s] = r < rows ? a[(size_t)r * kLrRank + (lane & 15)] : 0.0f;
+  }
+  v4d acc = 0.0;
+#pragma unroll
+  for (int s = 0; s < 16; ++s) {
+    const double d = (double)x[s];
+    acc = FAN_MFMA_F64_16x16x4(d, d, acc);
+  }
+  gram_store(acc, ws, part + (size_t)blockIdx.x * 256);
+}
+
+// The factor step, by the whole workgroup: W = the strips' partials in strip order (thread t element t), then wave 0
+// alone: lane i (and its copies i + 16, ...) holds row i of C = S W S in registers and overwrites it with row i of L,
+// column by column — L_jk crosses the wave by scalar lane reads, 120 of them; then lane j builds column j of T =
+// (L^T)^-1 by back substitution, k = 15 .. 0, and stores column j of Rinv = S T as f32 in the apply's B layout,
+// rs[l] = {Rinv[4 * (l / 16) + m][l % 16], m = 0..3}. *live = the mask of the live columns. Every statement in the
+// oracle's order with no contraction; the caller's __syncthreads publishes rs and live.
+__device__ __forceinline__ void cholqr_factor(const double* __restrict__ part, int strips, int rank, double* ws,
+                                              v4f* rs, unsigned* live) {
+#pragma clang fp contract(off)
+  const int t = threadIdx.x;
+  double w = part[t];
+#pragma unroll 8
+  for (int s = 1; s < strips; ++s) w += part[(size_t)s * 256 + t];
+  ws[t] = w;
+  __syncthreads();
+  if (t >= 64) return;
+  const int i = t & 15;
+  double c[kLrRank];
+#pragma unroll
+  for (int k = 0; k < kLrRank; ++k) c[k] = ws[i * kLrRank + k];
+  const double d = ws[i * (kLrRank + 1)];
+  int alive = i < rank && d != 0.0 && __builtin_isfinite(d);
+  const double s = alive ? 1.0 / sqrt(d) : 0.0;
+#pragma unroll
+  for (int k = 0; k < kLrRank; ++k) {
+    const double sk = lane_get(s, k);
+    c[k] = alive && __builtin_amdgcn_readlane(alive, k) ? (c[k] * s) * sk : 0.0;
+  }
+#pragma unroll
+  for (int j = 0; j < kLrRank; ++j) {
+    double acc = c[j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) acc = acc - c[k] * lane_get(c[k], j);
+    const double piv = lane_get(acc, j);
+    if (__builtin_amdgcn_readlane(alive, j) && piv > kCholPivotMin) {
+      const double ljj = sqrt(piv);
+      c[j] = i > j ? acc / ljj : (i == j ? ljj : 0.0);
+    } else {  // column j is dead: its row and column of L are zero
+      c[j] = 0.0;
+      if (i == j) {
+        alive = 0;
+#pragma unroll
+        for (int k = 0; k < j; ++k) c[k] = 0.0;
+      }
+    }
+  }
+  double tc[kLrRank];  // tc[k] = T[k][i]
+#pragma unroll
+  for (int k = kLrRank - 1; k >= 0; --k) {
+    double acc = 0.0;
+#pragma unroll
+    for (int m = k + 1; m < kLrRank; ++m) acc = acc + lane_get(c[k], m) * tc[m];
+    const double lkk = lane_get(c[k], k);
+    tc[k] = lkk != 0.0 && alive ? (i > k ? -acc / lkk : (i == k ? 1.0 / lkk : 0.0)) : 0.0;
+  }
+  v4f r[4];
+#pragma unroll
+  for (int k = 0; k < kLrRank; ++k) r[k >> 2][k & 3] = (float)(lane_get(s, k) * tc[k]);
+  if (t < 16) {
+#pragma unroll
+    for (int kq = 0; kq < 4; ++kq) rs[kq * 16 + i] = r[kq];
+  }
+  const unsigned mask = (unsigned)__ballot(alive) & 0xffffu;
+  if (t == 0) *live = mask;
+}
+
+// A <- A Rinv in place, Rinv from the partials `win`. Workgroup = strip of 256 rows, a wave 4 tiles of 16 rows. A
+// tile is loaded in the project kernel's A layout (lane l: the float4 at row l % 16, columns 4 * (l / 16) .. + 3; MFMA
+// m takes element m, so its K slot kk is column 4 * kk + m and its B is rs[l][m]) ahead of the factor, whose latency
+// hides the loads; dead columns are masked so that a non-finite entry there cannot reach a live one. The f32 tile
+// leaves the four MFMAs as out[4 * (l / 16) + v][l % 16] in register v — for the fp64 matrix instruction that is
+// k-step v with K slot l / 16 = row 4 * (l / 16) + v, a permutation of the tile's rows, which a Gram sum does not see.
+// So the first apply (SECOND = false) also accumulates the Gram matrix of what it stores, from registers, and leaves
+// it in wout[strip]: the second pass needs no Gram launch.
+template <bool SECOND>
+__global__ void __launch_bounds__(kBlock)
+    lowrank_cholqr_apply_kernel(float* p, const double* __restrict__ win, double* __restrict__ wout, int rows,
+                                int strips, int rank) {
+  __shared__ double ws[4 * 256];
+  __shared__ v4f rs[64];
+  __shared__ unsigned live_s;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n = lane & 15, kk = lane >> 4;
+  const int row0 = blockIdx.x * kLrOrthStrip + wave * 64;
+  v4f a[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int r = row0 + 16 * t;  // (rows % 16 == 0: a tile is all there or all missing)
+    a[t] = r < rows ? *reinterpret_cast<const v4f*>(p + (size_t)(r + n) * kLrRank + 4 * kk) : (v4f)0.0f;
+  }
+  cholqr_factor(win, strips, rank, ws, rs, &live_s);
+  __syncthreads();
+  const v4f b = rs[lane];
+  const unsigned live = live_s >> (4 * kk);
+  v4d g = 0.0;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int r = row0 + 16 * t;
+    if (r >= rows) break;
+    v4f acc = 0.0f;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) acc = FAN_MFMA_16x16x4((live >> m) & 1 ? a[t][m] : 0.0f, b[m], acc);
+    float* out = p + (size_t)(r + 4 * kk) * kLrRank + n;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) out[v * kLrRank] = acc[v];
+    if (!SECOND) {
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const double d = (double)acc[v];
+        g = FAN_MFMA_F64_16x16x4(d, d, g);
+      }
+    }
+  }
+  if (!SECOND) gram_store(g, ws, wout + (size_t)blockIdx.x * 256);  // (ws is free: wave 0 read it before the barrier)
+}
+
 // ---------------------------------------------------------------- G <- P^ Qm^T, E <- X - G, Q <- Qm = Qn * inv
 // K is only 16: plain VALU. Workgroup (column tile, row panel): lane t owns columns c .. c + 3 of 1024 and keeps their
 // Qm values (4 x 16, scaled by inv as they are loaded) in registers down a panel of 64 rows, whose P^ rows every lane
@@ -359,6 +531,20 @@ void launch_lowrank_orth(float* p, int64_t rows, int rank, hipStream_t s) {
   FAN_CHECK(rows > 0 && rows % 16 == 0 && rows <= INT32_MAX, "lowrank: rows must be a positive multiple of 16");
   check_aligned({p});
   lowrank_orth_kernel<<<1, kOrthBlock, 0, s>>>(p, (int)rows, rank);
+  FAN_HIP_CHECK(hipGetLastError());
+}
+
+void launch_lowrank_orth_cholqr2(float* p, int64_t rows, int rank, double* part, hipStream_t s) {
+  FAN_CHECK(rank >= 1 && rank <= kLrRank, "lowrank: the rank must lie in 1..16");
+  FAN_CHECK(rows > 0 && rows % 16 == 0 && rows <= INT32_MAX, "lowrank: rows must be a positive multiple of 16");
+  check_aligned({p, part});
+  const int strips = (int)lowrank_orth_strips(rows);
+  double* part2 = part + (size_t)strips * 256;
+  lowrank_gram_kernel<<<strips, kBlock, 0, s>>>(p, part, (int)rows);
+  FAN_HIP_CHECK(hipGetLastError());
+  lowrank_cholqr_apply_kernel<false><<<strips, kBlock, 0, s>>>(p, part, part2, (int)rows, strips, rank);
+  FAN_HIP_CHECK(hipGetLastError());
+  lowrank_cholqr_apply_kernel<true><<<strips, kBlock, 0, s>>>(p, part2, nullptr, (int)rows, strips, rank);
   FAN_HIP_CHECK(hipGetLastError());
 }
 

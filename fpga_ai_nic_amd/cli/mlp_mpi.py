@@ -95,7 +95,8 @@ def run(argv=None, out=sys.stdout):
     if cfg.compress == "powersgd":  # the engine-less trainer; the reducer holds the transport
         from ..parallel.lowrank import LowRankReducer
 
-        reducer = LowRankReducer(transport if world > 1 else None, cfg.rank, seed=cfg.lowrank_seed)
+        reducer = LowRankReducer(transport if world > 1 else None, cfg.rank, seed=cfg.lowrank_seed,
+                                 orth=cfg.lowrank_orth)
     sparse = None
     if cfg.compress == "topk":  # the engine-less trainer as well
         from ..parallel.sparse import TopKReducer

@@ -33,6 +33,7 @@ class TrainConfig:
     compress: str = "bfp"          # bfp | bfp4 | sign | raw | raw_bf16 | rccl | local | powersgd | topk
     rank: int = 4                  # powersgd: the rank of the approximation, 1..16
     lowrank_seed: int = 0          # powersgd: seed of the initial Q factors (the same on every rank)
+    lowrank_orth: str = "mgs"      # powersgd: mgs (modified Gram-Schmidt) | cholqr2 (multi-workgroup CholeskyQR2)
     density: float = 0.01          # topk: the fraction of a bucket each rank sends, in (0, 1]
     rounding: str = "rne"          # rne | trunc
     algo: str = "mesh"             # mesh | ring
@@ -100,6 +101,9 @@ def add_named_flags(ap: argparse.ArgumentParser):
     ap.add_argument("--rank", type=int, default=d.rank, help="--compress powersgd: rank of the approximation, 1..16")
     ap.add_argument("--lowrank-seed", type=int, default=d.lowrank_seed,
                     help="--compress powersgd: seed of the initial Q factors")
+    ap.add_argument("--lowrank-orth", default=d.lowrank_orth, choices=["mgs", "cholqr2"],
+                    help="--compress powersgd: how P is orthogonalised: mgs = modified Gram-Schmidt in one workgroup, "
+                         "cholqr2 = CholeskyQR2 spread over 256-row strips (three launches; other bits than mgs)")
     ap.add_argument("--density", type=float, default=d.density,
                     help="--compress topk: fraction of every bucket each rank sends, in (0, 1]")
     ap.add_argument("--rounding", default=d.rounding, choices=["rne", "trunc"])
@@ -187,6 +191,11 @@ def config_from_args(a, positional_sizes=None) -> TrainConfig:
     if c.compress == "sign" and not c.error_feedback:
         raise ValueError("--compress sign: sign1 needs error feedback (--error-feedback): one bit per value converges "
                          "only with the residual carried over")
+    if c.lowrank_orth not in ("mgs", "cholqr2"):
+        raise ValueError(f"--lowrank-orth must be mgs or cholqr2, got {c.lowrank_orth!r}")
+    if c.lowrank_orth != "mgs" and c.compress != "powersgd":
+        raise ValueError(f"--lowrank-orth {c.lowrank_orth} selects PowerSGD's orthogonalisation: it needs --compress "
+                         f"powersgd")
     if c.compress == "powersgd":
         if not 1 <= c.rank <= 16:
             raise ValueError(f"--rank must lie in 1..16, got {c.rank}")

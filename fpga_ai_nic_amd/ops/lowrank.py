@@ -76,17 +76,25 @@ def backproject(g, e, ph, part, out, rows: int, cols: int):
     return out
 
 
-def orth(p, rank: int):
-    """p[rows][16] -> its orthonormalised columns 0..rank-1 in place (columns >= rank zeroed)."""
+def orth(p, rank: int, method: str = "mgs", part=None):
+    """p[rows][16] -> its orthonormalised columns 0..rank-1 in place (columns >= rank zeroed). ``method``: ``"mgs"``
+    (modified Gram-Schmidt, one workgroup) or ``"cholqr2"`` (CholeskyQR2 over strips of ``ORTH_STRIP`` rows, three
+    launches), which on the GPU needs ``part``: a partial buffer of at least ``4 * ceil(rows / ORTH_STRIP) * 256``
+    elements (two 16 x 16 fp64 Gram matrices per strip)."""
+    if method not in ("mgs", "cholqr2"):
+        raise ValueError(f"lowrank: unknown orth method {method!r}; mgs or cholqr2")
     if not (isinstance(p, torch.Tensor) and p.dim() == 2 and p.shape[1] == RANK_PAD):
         raise ValueError("lowrank: p must be a [rows][16] tensor")
     rows = p.shape[0]
     O.check_shape(rows, max(rows, RANK_PAD), rank)  # (the rank in 1..16 and <= rows; rows a multiple of 16)
     _plane(p, rows * RANK_PAD, None, "p")
-    if p.is_cuda:
+    if not p.is_cuda:
+        p.copy_(torch.from_numpy((O.orth if method == "mgs" else O.orth_cholqr2)(p.numpy(), rank)))
+    elif method == "mgs":
         _ext.require().lowrank.orth(p, rank)
     else:
-        p.copy_(torch.from_numpy(O.orth(p.numpy(), rank)))
+        _plane(part, 4 * -(-rows // O.ORTH_STRIP) * 256, p, "part", exact=False)
+        _ext.require().lowrank.orth_cholqr2(p, rank, part)
     return p
 
 

@@ -27,16 +27,19 @@ class LowRankState:
 
 
 class LowRankReducer:
-    def __init__(self, transport: Transport | None, rank: int, seed: int = 0):
+    def __init__(self, transport: Transport | None, rank: int, seed: int = 0, orth: str = "mgs"):
         """``transport=None``: one rank, no collective. ``rank``: 1..16. ``seed``: of every bucket's initial Q (bucket
-        number b, in the order of first use, draws from ``seed + b``): the same on every rank."""
+        number b, in the order of first use, draws from ``seed + b``): the same on every rank. ``orth``: ``"mgs"``
+        (modified Gram-Schmidt, one workgroup) or ``"cholqr2"`` (CholeskyQR2 spread over 256-row strips; other bits)."""
+        if orth not in ("mgs", "cholqr2"):
+            raise ValueError(f"lowrank: unknown orth method {orth!r}; mgs or cholqr2")
         if isinstance(rank, bool) or not isinstance(rank, int) or not 1 <= rank <= LR.RANK_PAD:
             raise ValueError(f"lowrank: the rank must be an int in 1..{LR.RANK_PAD}, got {rank!r}")
         if isinstance(seed, bool) or not isinstance(seed, int) or seed < 0:
             raise ValueError(f"lowrank: the seed must be a non-negative int, got {seed!r}")
         self.transport = transport
         self.world = transport.world if transport is not None else 1
-        self.rank, self.seed = rank, seed
+        self.rank, self.seed, self.orth = rank, seed, orth
         self.inv = float(np.float32(1.0) / np.float32(self.world))
         self._states: list[tuple[object, LowRankState]] = []  # (bucket, state), found by identity
 
@@ -52,10 +55,13 @@ class LowRankReducer:
             raise ValueError("lowrank: the bucket's gradient must be a contiguous float32 plane of at least n elements")
         dev = g.device
         q = torch.from_numpy(LR.O.init_q(cols, self.rank, self.seed + len(self._states))).to(dev)
+        n_part = LR.layout(rows, cols)[2]
+        if self.orth == "cholqr2":  # two 16 x 16 fp64 Gram matrices per strip: more than the products need only
+            n_part = max(n_part, 4 * -(-rows // LR.O.ORTH_STRIP) * 256)  # where a strip is mostly empty
         st = LowRankState(rows, cols, torch.zeros(rows * cols, dtype=torch.float32, device=dev), q,
                           torch.zeros(rows, LR.RANK_PAD, dtype=torch.float32, device=dev),
                           torch.zeros(cols, LR.RANK_PAD, dtype=torch.float32, device=dev),
-                          torch.zeros(LR.layout(rows, cols)[2], dtype=torch.float32, device=dev))
+                          torch.zeros(n_part, dtype=torch.float32, device=dev))
         self._states.append((bucket, st))
         return st
 
@@ -76,7 +82,7 @@ class LowRankReducer:
         rows, cols, g = st.rows, st.cols, bucket.grad
         LR.project(g, st.e, st.q, st.part, st.p, rows, cols)
         self._all_reduce(st.p)
-        LR.orth(st.p, self.rank)
+        LR.orth(st.p, self.rank, self.orth, st.part)
         LR.backproject(g, st.e, st.p, st.part, st.qn, rows, cols)
         self._all_reduce(st.qn)
         LR.reconstruct(g, st.e, st.p, st.qn, st.q, self.inv, rows, cols)

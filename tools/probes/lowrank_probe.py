@@ -6,7 +6,11 @@ alternating inside each repetition, device events around every launch, median / 
 has to move over the median; (3) the two-rank reducer's relative Frobenius error against the fp64 run of the oracle
 on the inputs of tests/test_gpu_lowrank.py::test_reducer_two_ranks. Sections 2 and 3 need the GPU and fail without it.
 
-    python tools/probes/lowrank_probe.py [--out profiles/lowrank.txt] [--reps 50] [--resources-only]
+``--orth`` writes profiles/lowrank_cholqr.txt instead: the resources, then the orthogonalisation alone by both methods
+(modified Gram-Schmidt in one workgroup; CholeskyQR2 in three launches over 256-row strips) at 4096 and 1024 rows,
+r = 1, 4 and 16, the two methods alternating inside each repetition, on fresh copies of the same P.
+
+    python tools/probes/lowrank_probe.py [--out profiles/lowrank.txt] [--reps 50] [--resources-only] [--orth]
 """
 from __future__ import annotations
 
@@ -30,9 +34,9 @@ def resources() -> list[str]:
                             "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, check=True)
     rows, cur = [], None
     for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: \S*?(lowrank_\w+_kernel)", line)
+        m = re.search(r"Function Name: \S*?(lowrank_\w+_kernel)(ILb([01])E)?", line)
         if m:
-            cur = {"name": m.group(1)}
+            cur = {"name": m.group(1) + (f"<{m.group(3)}>" if m.group(2) else "")}  # (a template's bool argument)
             rows.append(cur)
             continue
         m = re.search(r"(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)",
@@ -98,6 +102,38 @@ def timings(reps: int) -> list[str]:
     return out
 
 
+def orth_timings(reps: int) -> list[str]:
+    import torch
+
+    from fpga_ai_nic_amd.ops import lowrank as LR
+
+    if not torch.cuda.is_available():
+        raise SystemExit("lowrank_probe: the timing sections need the GPU")
+    dev = torch.device("cuda", 0)
+    out = [f"{'rows':<8}{'r':>3}  {'method':<10}{'median us':>10}{'min us':>9}{'max us':>9}{'p10 us':>9}{'p90 us':>9}"]
+    for rows in (4096, 1024):
+        for r in (1, 4, 16):
+            p0 = torch.randn(rows, 16, generator=torch.Generator().manual_seed(rows + r)).to(dev)
+            p0[:, r:] = 0
+            p, part = torch.empty_like(p0), torch.zeros(4 * -(-rows // 256) * 256, device=dev)
+            times = {"mgs": [], "cholqr2": []}
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            for rep in range(reps + 5):  # 5 warm-up repetitions
+                for method in times:
+                    p.copy_(p0)
+                    ev[0].record()
+                    LR.orth(p, r, method=method, part=part)
+                    ev[1].record()
+                    ev[1].synchronize()
+                    if rep >= 5:
+                        times[method].append(ev[0].elapsed_time(ev[1]) * 1e3)
+            for method, t in times.items():
+                dec = statistics.quantiles(t, n=10)
+                out.append(f"{rows:<8}{r:>3}  {method:<10}{statistics.median(t):>10.1f}{min(t):>9.1f}{max(t):>9.1f}"
+                           f"{dec[0]:>9.1f}{dec[-1]:>9.1f}")
+    return out
+
+
 def accuracy() -> list[str]:
     from types import SimpleNamespace
 
@@ -130,13 +166,18 @@ def accuracy() -> list[str]:
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lowrank.txt"))
+    ap.add_argument("--out", default=None, help="profiles/lowrank.txt, or profiles/lowrank_cholqr.txt with --orth")
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--resources-only", action="store_true")
+    ap.add_argument("--orth", action="store_true", help="time the orthogonalisation alone, mgs against cholqr2")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "lowrank_cholqr.txt" if a.orth else "lowrank.txt")
     lines = ["PowerSGD low-rank kernels (tools/probes/lowrank_probe.py)", "", "== resources (gfx950, compiler remarks)"]
     lines += resources()
-    if not a.resources_only:
+    if a.orth and not a.resources_only:
+        lines += ["", f"== orth alone (launch to completion, host launch cost of the three cholqr2 launches included), "
+                      f"{a.reps} alternating repetitions, device events (us)"] + orth_timings(a.reps)
+    elif not a.resources_only:
         lines += ["", f"== each kernel alone, {a.reps} alternating repetitions, device events (us)"] + timings(a.reps)
         lines += ["", "== accuracy"] + accuracy()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
