@@ -7,6 +7,7 @@
 #include "gemm/gemm_group.h"
 #include "lowrank/lowrank.h"
 #include "nn/nn.h"
+#include "sketch/sketch.h"
 #include "topk/topk.h"
 
 namespace fan {
@@ -791,6 +792,74 @@ void topk_accumulate(const at::Tensor& wires, int64_t world, at::Tensor& g, int6
                          fan_stream());
 }
 
+void topk_select_keys(const at::Tensor& plane, at::Tensor& wire, at::Tensor& scratch, int64_t n, int64_t k,
+                      int64_t max_blocks, int64_t stages) {
+  const int64_t n_pad = plane.numel();
+  tk_shape(n_pad, n, k, max_blocks);
+  const TopkLayout L = topk_layout(n_pad, k);
+  tk_plane(plane, at::kFloat, n_pad, plane, "plane");
+  tk_plane(wire, at::kByte, L.wire_bytes, plane, "wire");
+  tk_plane(scratch, at::kInt, L.scratch_words, plane, "scratch");
+  launch_topk_select_keys(plane.data_ptr<float>(), wire.data_ptr(),
+                          reinterpret_cast<uint32_t*>(scratch.data_ptr<int32_t>()), n_pad, n, k, (int)max_blocks,
+                          fan_stream(), (int)(stages & kTopkAllStages));
+}
+
+// ---- count-sketch compression (sketch/sketch.h). g and e: contiguous f32 planes of n_pad elements on one GPU; the
+// sketch, the partial buffer and the wire of exactly the length the layouts give, so nothing behind them is reachable.
+void sk_plane(const at::Tensor& t, at::ScalarType ty, int64_t n, const at::Tensor& ref, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == ty && t.device() == ref.device() &&
+                  t.numel() == n,
+              "sketch: ", what, " must be a contiguous ", ty, " tensor of ", n, " elements on the gradient's GPU");
+}
+
+void sk_shape(int64_t n_pad, int64_t n, int64_t rows, int64_t cols, int64_t max_blocks) {
+  TORCH_CHECK(n_pad > 0 && n_pad % 4 == 0 && n_pad < ((int64_t)1 << 31),
+              "sketch: n_pad must be a positive multiple of 4 below 2^31, got ", n_pad);
+  TORCH_CHECK(n >= 1 && n <= n_pad, "sketch: 1 <= n <= n_pad, got n = ", n);
+  TORCH_CHECK(rows == 1 || rows == 3 || rows == 5, "sketch: rows must be 1, 3 or 5, got ", rows);
+  TORCH_CHECK(cols >= kSketchTile && cols <= kSketchMaxCols && cols % kSketchTile == 0,
+              "sketch: cols must be a multiple of 1024 in 1024 .. 2^22, got ", cols);
+  TORCH_CHECK(max_blocks >= 0 && max_blocks <= INT32_MAX, "sketch: max_blocks >= 0");
+}
+
+void sketch_sketch(const at::Tensor& g, const at::Tensor& e, at::Tensor& part, at::Tensor& S, int64_t n, int64_t rows,
+                   int64_t cols, uint64_t seed, int64_t max_blocks, int64_t stages) {
+  const int64_t n_pad = g.numel();
+  sk_shape(n_pad, n, rows, cols, max_blocks);
+  const SketchLayout L = sketch_layout(n_pad, (int)rows, cols);
+  sk_plane(g, at::kFloat, n_pad, g, "g");
+  sk_plane(e, at::kFloat, n_pad, g, "e");
+  sk_plane(part, at::kFloat, L.part_elems, g, "part");
+  sk_plane(S, at::kFloat, L.sketch_elems, g, "S");
+  TORCH_CHECK(S.data_ptr() != part.data_ptr() && S.data_ptr() != g.data_ptr() && S.data_ptr() != e.data_ptr() &&
+                  part.data_ptr() != g.data_ptr() && part.data_ptr() != e.data_ptr(),
+              "sketch: S and part must be buffers of their own");
+  launch_sketch(g.data_ptr<float>(), e.data_ptr<float>(), part.data_ptr<float>(), S.data_ptr<float>(), n_pad, n,
+                (int)rows, cols, seed, (int)max_blocks, fan_stream(), (int)(stages & 3));
+}
+
+void sketch_estimate(at::Tensor& g, at::Tensor& e, const at::Tensor& S, int64_t n, int64_t rows, int64_t cols,
+                     uint64_t seed, int64_t max_blocks) {
+  const int64_t n_pad = g.numel();
+  sk_shape(n_pad, n, rows, cols, max_blocks);
+  sk_plane(g, at::kFloat, n_pad, g, "g");
+  sk_plane(e, at::kFloat, n_pad, g, "e");
+  sk_plane(S, at::kFloat, rows * cols, g, "S");
+  TORCH_CHECK(g.data_ptr() != e.data_ptr() && S.data_ptr() != g.data_ptr() && S.data_ptr() != e.data_ptr(),
+              "sketch: g, e and S must be buffers of their own");
+  launch_sketch_estimate(g.data_ptr<float>(), e.data_ptr<float>(), S.data_ptr<float>(), n_pad, n, (int)rows, cols,
+                         seed, (int)max_blocks, fan_stream());
+}
+
+void sketch_fetch(at::Tensor& e, at::Tensor& wire, int64_t n, int64_t k, int64_t max_blocks) {
+  const int64_t n_pad = e.numel();
+  tk_shape(n_pad, n, k, max_blocks);
+  sk_plane(e, at::kFloat, n_pad, e, "e");
+  sk_plane(wire, at::kByte, topk_layout(n_pad, k).wire_bytes, e, "wire");
+  launch_sketch_fetch(e.data_ptr<float>(), wire.data_ptr(), n_pad, n, k, (int)max_blocks, fan_stream());
+}
+
 }  // namespace
 
 void register_gemm(pybind11::module_& m) {
@@ -954,6 +1023,30 @@ void register_nn(pybind11::module_& m) {
   tk.def("accumulate", &topk_accumulate, "g[i] = (the ranks' values at i, added in rank order from +0) * inv, i < n",
          pybind11::arg("wires"), pybind11::arg("world"), pybind11::arg("g"), pybind11::arg("n"), pybind11::arg("k"),
          pybind11::arg("inv"), pybind11::arg("max_blocks") = 0);
+  tk.def("select_keys", &topk_select_keys,
+         "wire = the k largest |plane| (i < n) ascending by index, val the plane's values; the plane is read only. "
+         "Scratch and stages as for select",
+         pybind11::arg("plane"), pybind11::arg("wire"), pybind11::arg("scratch"), pybind11::arg("n"),
+         pybind11::arg("k"), pybind11::arg("max_blocks") = 0, pybind11::arg("stages") = (int64_t)kTopkAllStages);
+  pybind11::module_ sk = m.def_submodule("sketch", "count-sketch gradient compression kernels");
+  sk.def("layout", [](int64_t n_pad, int64_t rows, int64_t cols) {
+    sk_shape(n_pad, 1, rows, cols, 0);
+    const SketchLayout L = sketch_layout(n_pad, (int)rows, cols);
+    return std::vector<int64_t>{L.chunks, L.strips, L.part_elems, L.sketch_elems};
+  }, "{chunks, strips, f32 elements of the partial buffer, f32 elements of the sketch}", pybind11::arg("n_pad"),
+         pybind11::arg("rows"), pybind11::arg("cols"));
+  sk.def("sketch", &sketch_sketch,
+         "S[rows][cols] = the count sketch of (g + e)[:n]; part: the per-strip slabs. stages: bit 0 the accumulate, "
+         "bit 1 the combine",
+         pybind11::arg("g"), pybind11::arg("e"), pybind11::arg("part"), pybind11::arg("S"), pybind11::arg("n"),
+         pybind11::arg("rows"), pybind11::arg("cols"), pybind11::arg("seed"), pybind11::arg("max_blocks") = 0,
+         pybind11::arg("stages") = (int64_t)3);
+  sk.def("estimate", &sketch_estimate, "e = g + e; g = the median over the rows of the signed sketch entries (i < n)",
+         pybind11::arg("g"), pybind11::arg("e"), pybind11::arg("S"), pybind11::arg("n"), pybind11::arg("rows"),
+         pybind11::arg("cols"), pybind11::arg("seed"), pybind11::arg("max_blocks") = 0);
+  sk.def("fetch", &sketch_fetch, "val[j] = e[idx[j]], e[idx[j]] = +0 (j < k) on the top-k wire",
+         pybind11::arg("e"), pybind11::arg("wire"), pybind11::arg("n"), pybind11::arg("k"),
+         pybind11::arg("max_blocks") = 0);
 }
 
 void register_planner(pybind11::module_& m) {

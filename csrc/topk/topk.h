@@ -32,6 +32,10 @@ inline TopkLayout topk_layout(int64_t n_pad, int64_t k) {
 constexpr int kTopkAllStages = 511;
 void launch_topk_select(const float* g, float* e, void* wire, uint32_t* scratch, int64_t n_pad, int64_t n, int64_t k,
                         int max_blocks, hipStream_t s, int stages = kTopkAllStages);
+// The keys-only form: the k largest |plane[i]| (i < n) by the same keys, tie rule, wire, scratch and launches; val holds
+// the plane's values. The plane is read only: nothing is added to it and nothing in it is zeroed.
+void launch_topk_select_keys(const float* plane, void* wire, uint32_t* scratch, int64_t n_pad, int64_t n, int64_t k,
+                             int max_blocks, hipStream_t s, int stages = kTopkAllStages);
 // g[i] = (+0 + val_0[i] + val_1[i] + ...) * inv over the ranks that sent i, in rank order (i < n). wires: world wires
 // of 8 * k_pad bytes each, back to back.
 void launch_topk_accumulate(const void* wires, int world, float* g, int64_t n_pad, int64_t n, int64_t k, float inv,

@@ -99,8 +99,9 @@ __device__ __forceinline__ bool topk_digit(uint32_t key, uint32_t prefix, uint32
 // Persistent workgroups stride over tiles of 1024 elements, 16 B per lane. Pass 0 reads g and e and stores e = g + e;
 // the others read e alone. Every wave counts into its own copy of the histogram in LDS (gradients crowd into a few
 // exponent bins: four copies quarter the same-address traffic, and a lane whose consecutive elements share a digit
-// adds their count once); the copies are added and the non-zero bins flushed into the global histogram.
-template <int PASS>
+// adds their count once); the copies are added and the non-zero bins flushed into the global histogram. KEYS (pass 0
+// of the keys-only select): the keys are those of the plane e as it stands: g is not read and e is not written.
+template <int PASS, bool KEYS = false>
 __global__ void __launch_bounds__(kBlock)
     topk_hist_kernel(const float* __restrict__ g, float* __restrict__ e, const uint32_t* __restrict__ state,
                      uint32_t* __restrict__ hist, uint32_t n) {
@@ -115,7 +116,7 @@ __global__ void __launch_bounds__(kBlock)
     const uint32_t i = tile * kTopkHistTile + threadIdx.x * 4;
     if (i >= n) continue;
     v4f x = load4(e, i, n);
-    if (PASS == 0) {
+    if (PASS == 0 && !KEYS) {
       const v4f gv = load4(g, i, n);
 #pragma unroll
       for (int j = 0; j < 4; ++j) x[j] = topk_x(gv[j], x[j]);
@@ -249,7 +250,8 @@ __global__ void __launch_bounds__(kBlock)
 // slots of mbcnt(ballot); the 16 (round, wave) totals cross the workgroup through LDS. Two running prefixes, one for
 // key > T and one for key == T: an element above T lands at off + (#above before it) + min(#ties before it, take), a
 // tie whose rank q among the tile's ties is below take at off + (#above before it) + q. The selected elements are
-// zeroed in the residual plane, and only the vectors that changed are stored back.
+// zeroed in the residual plane, and only the vectors that changed are stored back (KEYS: the plane is left alone).
+template <bool KEYS>
 __global__ void __launch_bounds__(kBlock)
     topk_compact_kernel(float* __restrict__ e, const uint32_t* __restrict__ state, const uint32_t* __restrict__ off,
                         const uint32_t* __restrict__ take, uint32_t* __restrict__ idx, float* __restrict__ val,
@@ -313,7 +315,7 @@ __global__ void __launch_bounds__(kBlock)
             idx[pos] = i + j;
             val[pos] = x[r][j];
             x[r][j] = 0.0f;
-            changed = true;
+            changed = !KEYS;
           }
         }
         g_run += gt;
@@ -385,10 +387,9 @@ unsigned grid_for(int64_t tiles, int cap, int max_blocks) {
   return (unsigned)(tiles < cap ? tiles : cap);
 }
 
-}  // namespace
-
-void launch_topk_select(const float* g, float* e, void* wire, uint32_t* scratch, int64_t n_pad, int64_t n, int64_t k,
-                        int max_blocks, hipStream_t s, int stages) {
+template <bool KEYS>
+void select_launches(const float* g, float* e, void* wire, uint32_t* scratch, int64_t n_pad, int64_t n, int64_t k,
+                     int max_blocks, hipStream_t s, int stages) {
   check_plane(n_pad, n, k);
   check_aligned({g, e, wire, scratch});
   FAN_CHECK(max_blocks >= 0, "topk: max_blocks >= 0");
@@ -405,7 +406,7 @@ void launch_topk_select(const float* g, float* e, void* wire, uint32_t* scratch,
   float* val = reinterpret_cast<float*>(idx + kp);
   const unsigned hgrid = grid_for((n + kTopkHistTile - 1) / kTopkHistTile, kNumCU * 4, max_blocks);
   const unsigned tgrid = grid_for(tiles, kNumCU * 8, max_blocks);
-  if (stages & 1) topk_hist_kernel<0><<<hgrid, kBlock, 0, s>>>(g, e, state, hist, un);
+  if (stages & 1) topk_hist_kernel<0, KEYS><<<hgrid, kBlock, 0, s>>>(g, e, state, hist, un);
   if (stages & 2) topk_pick_kernel<0><<<1, kBlock, 0, s>>>(hist, state, uk);
   if (stages & 4) topk_hist_kernel<1><<<hgrid, kBlock, 0, s>>>(g, e, state, hist, un);
   if (stages & 8) topk_pick_kernel<1><<<1, kBlock, 0, s>>>(hist, state, uk);
@@ -413,8 +414,20 @@ void launch_topk_select(const float* g, float* e, void* wire, uint32_t* scratch,
   if (stages & 32) topk_pick_kernel<2><<<1, kBlock, 0, s>>>(hist, state, uk);
   if (stages & 64) topk_count_kernel<<<tgrid, kBlock, 0, s>>>(e, state, cnt_gt, cnt_eq, un, tiles);
   if (stages & 128) topk_scan_kernel<<<1, kBlock, 0, s>>>(state, cnt_gt, cnt_eq, off, take, tiles);
-  if (stages & 256) topk_compact_kernel<<<tgrid, kBlock, 0, s>>>(e, state, off, take, idx, val, un, tiles, uk, kp);
+  if (stages & 256) topk_compact_kernel<KEYS><<<tgrid, kBlock, 0, s>>>(e, state, off, take, idx, val, un, tiles, uk, kp);
   FAN_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
+void launch_topk_select(const float* g, float* e, void* wire, uint32_t* scratch, int64_t n_pad, int64_t n, int64_t k,
+                        int max_blocks, hipStream_t s, int stages) {
+  select_launches<false>(g, e, wire, scratch, n_pad, n, k, max_blocks, s, stages);
+}
+
+void launch_topk_select_keys(const float* plane, void* wire, uint32_t* scratch, int64_t n_pad, int64_t n, int64_t k,
+                             int max_blocks, hipStream_t s, int stages) {
+  select_launches<true>(plane, const_cast<float*>(plane), wire, scratch, n_pad, n, k, max_blocks, s, stages);
 }
 
 void launch_topk_accumulate(const void* wires, int world, float* g, int64_t n_pad, int64_t n, int64_t k, float inv,

@@ -4,7 +4,7 @@ Reference knobs and where they went:
   iters / MB / fuse_type / type / bn bk bc / C1..CN  -> positional CLI, kept (sw/mlp_mpi_example_f32.cpp:270-320)
   NUM_NODES=3 (sw:38)                               -> world size from the launcher (any N >= 1)
   `BFP_EN (hw/all_reduce.sv:13)                     -> compress = bfp | bfp4 | sign | raw | rccl | local | powersgd |
-                                                        topk
+                                                        topk | sketch
   NUM_FP=16, MANT_SIZE=8 (hw/bfp_adapter.sv:34-36)   -> group of 16; 8-bit mantissas (bfp; rounding = rne | trunc, the
                                                         bit-exact ref) or 4-bit (bfp4, rne only)
   BUF_SIZE=512 CL slice (hw/all_reduce.sv:102)      -> slice_elems (ring)
@@ -30,11 +30,14 @@ class TrainConfig:
     sizes: list = field(default_factory=lambda: [1024, 4096, 4096, 1024])
     dtype: str = "bf16"            # bf16 | f32
     f32_gemm: str = "mfma"         # --dtype f32: mfma (exact f32 MFMA GEMM) | bf16x3 (split precision, 3 bf16 MFMAs)
-    compress: str = "bfp"          # bfp | bfp4 | sign | raw | raw_bf16 | rccl | local | powersgd | topk
+    compress: str = "bfp"          # bfp | bfp4 | sign | raw | raw_bf16 | rccl | local | powersgd | topk | sketch
     rank: int = 4                  # powersgd: the rank of the approximation, 1..16
     lowrank_seed: int = 0          # powersgd: seed of the initial Q factors (the same on every rank)
     lowrank_orth: str = "mgs"      # powersgd: mgs (modified Gram-Schmidt) | cholqr2 (multi-workgroup CholeskyQR2)
-    density: float = 0.01          # topk: the fraction of a bucket each rank sends, in (0, 1]
+    density: float = 0.01          # topk, sketch: the fraction of a bucket that is sent / recovered, in (0, 1]
+    sketch_rows: int = 5           # sketch: rows of the count sketch, 1 | 3 | 5
+    sketch_cols: int = 65536       # sketch: columns of the count sketch, a multiple of 1024 in 1024 .. 2^22
+    sketch_seed: int = 0           # sketch: seed of the hashes (the same on every rank), an int in [0, 2^64)
     rounding: str = "rne"          # rne | trunc
     algo: str = "mesh"             # mesh | ring
     rings: int = 1
@@ -85,7 +88,7 @@ def add_named_flags(ap: argparse.ArgumentParser):
                          "f32 operands split in registers into two bf16 pieces each, three bf16 MFMAs per product "
                          "(about 2^-14.4 relative per product)")
     ap.add_argument("--compress", default=d.compress,
-                    choices=["bfp", "bfp4", "sign", "raw", "raw_bf16", "rccl", "local", "powersgd", "topk"],
+                    choices=["bfp", "bfp4", "sign", "raw", "raw_bf16", "rccl", "local", "powersgd", "topk", "sketch"],
                     help="wire format of the all-reduce: bfp = 8-bit mantissas (17 B per 16 values), bfp4 = 4-bit "
                          "mantissas (9 B per 16 values, --rounding rne only; meant for use with --error-feedback), "
                          "sign = one sign bit per value and a power-of-two scale per group (codec sign1, 3 B per 16 "
@@ -97,7 +100,11 @@ def add_named_flags(ap: argparse.ArgumentParser):
                          "sparsification with memory (each rank sends the --density largest-magnitude fraction of "
                          "every bucket as 8 B index/value pairs, one all-gather per bucket; engine-less trainer, own "
                          "residual, not checkpointed: not with --error-feedback or --stochastic-rounding; at most 16 "
-                         "ranks)")
+                         "ranks), sketch = count-sketch compression (each rank all-reduces a --sketch-rows x "
+                         "--sketch-cols f32 sketch of every bucket, every rank recovers the same --density fraction "
+                         "of indices from the sum, and a second all-reduce carries their exact values: 4 * (rows * "
+                         "cols + k) B per bucket whatever the world size; engine-less trainer, own residual, not "
+                         "checkpointed: not with --error-feedback or --stochastic-rounding)")
     ap.add_argument("--rank", type=int, default=d.rank, help="--compress powersgd: rank of the approximation, 1..16")
     ap.add_argument("--lowrank-seed", type=int, default=d.lowrank_seed,
                     help="--compress powersgd: seed of the initial Q factors")
@@ -105,7 +112,14 @@ def add_named_flags(ap: argparse.ArgumentParser):
                     help="--compress powersgd: how P is orthogonalised: mgs = modified Gram-Schmidt in one workgroup, "
                          "cholqr2 = CholeskyQR2 spread over 256-row strips (three launches; other bits than mgs)")
     ap.add_argument("--density", type=float, default=d.density,
-                    help="--compress topk: fraction of every bucket each rank sends, in (0, 1]")
+                    help="--compress topk: fraction of every bucket each rank sends, in (0, 1]; --compress sketch: "
+                         "fraction of every bucket recovered from the summed sketch")
+    ap.add_argument("--sketch-rows", type=int, default=d.sketch_rows, choices=[1, 3, 5],
+                    help="--compress sketch: rows of the count sketch (the estimate is their median)")
+    ap.add_argument("--sketch-cols", type=int, default=d.sketch_cols,
+                    help="--compress sketch: columns of the count sketch, a multiple of 1024 in 1024 .. 2^22")
+    ap.add_argument("--sketch-seed", type=int, default=d.sketch_seed,
+                    help="--compress sketch: seed of the bucket and sign hashes, an int in [0, 2^64)")
     ap.add_argument("--rounding", default=d.rounding, choices=["rne", "trunc"])
     ap.add_argument("--algo", default=d.algo, choices=["mesh", "ring"])
     ap.add_argument("--rings", type=int, default=d.rings)
@@ -201,6 +215,23 @@ def config_from_args(a, positional_sizes=None) -> TrainConfig:
             raise ValueError(f"--rank must lie in 1..16, got {c.rank}")
         if c.error_feedback or c.stochastic_rounding:
             raise ValueError("--compress powersgd keeps its own residual: not with --error-feedback or "
+                             "--stochastic-rounding")
+    d = TrainConfig()
+    if c.compress != "sketch" and (c.sketch_rows, c.sketch_cols, c.sketch_seed) != (d.sketch_rows, d.sketch_cols,
+                                                                                    d.sketch_seed):
+        raise ValueError("--sketch-rows, --sketch-cols and --sketch-seed shape the count sketch: they need --compress "
+                         "sketch")
+    if c.compress == "sketch":
+        if not 0.0 < c.density <= 1.0:
+            raise ValueError(f"--density must lie in (0, 1], got {c.density}")
+        if c.sketch_rows not in (1, 3, 5):
+            raise ValueError(f"--sketch-rows must be 1, 3 or 5, got {c.sketch_rows}")
+        if c.sketch_cols % 1024 or not 1024 <= c.sketch_cols <= 1 << 22:
+            raise ValueError(f"--sketch-cols must be a multiple of 1024 in 1024 .. 2^22, got {c.sketch_cols}")
+        if not 0 <= c.sketch_seed < 1 << 64:
+            raise ValueError(f"--sketch-seed must lie in [0, 2^64), got {c.sketch_seed}")
+        if c.error_feedback or c.stochastic_rounding:
+            raise ValueError("--compress sketch keeps its own residual: not with --error-feedback or "
                              "--stochastic-rounding")
     if c.compress == "topk":
         if not 0.0 < c.density <= 1.0:

@@ -92,8 +92,15 @@ class DataParallelTrainer:
                  betas=None, eps: float = 1e-8, trust_ratio: bool = False,
                  max_grad_norm: float | None = None, error_feedback: bool = False,
                  error_feedback_codec: str = "bfp_rne", stochastic_rounding: bool = False, sr_seed: int = 0,
-                 moment_codec: str = "f32", lowrank=None, topk=None):
-        """``topk``: a :class:`~fpga_ai_nic_amd.parallel.sparse.TopKReducer` — top-k sparsification with memory on the
+                 moment_codec: str = "f32", lowrank=None, topk=None, sketch=None):
+        """``sketch``: a :class:`~fpga_ai_nic_amd.parallel.sketch.SketchReducer` — count-sketch compression on the
+        engine-less trainer (``engine`` must be None; the reducer holds the transport). After each layer's bwd-weight
+        GEMM the reducer replaces the layer's f32 gradient by the rank mean of gradient + residual at the k indices
+        every rank recovers from the summed sketch (two synchronous all-reduces) and the local update reads it as
+        ``raw_f32`` with ``grad_scale`` 1, as with ``topk``. Not with ``lowrank``, ``topk``, ``error_feedback`` or
+        ``stochastic_rounding`` (the reducer owns its own residual: ``sketch_residuals``, not checkpointed).
+
+        ``topk``: a :class:`~fpga_ai_nic_amd.parallel.sparse.TopKReducer` — top-k sparsification with memory on the
         engine-less trainer (``engine`` must be None; the reducer holds the transport). After each layer's bwd-weight
         GEMM the reducer replaces the layer's f32 gradient by the rank mean of the ranks' k largest components of
         gradient + residual (one synchronous all-gather) and the local update reads it as ``raw_f32`` with
@@ -296,6 +303,16 @@ class DataParallelTrainer:
                                  "own residual)")
             for l in model.layers:
                 topk.state_for(l)  # (refuses a bucket the kernels do not take)
+        self.sketch = sketch
+        if sketch is not None:
+            if engine is not None:
+                raise ValueError("sketch: on the engine-less trainer only (engine=None; the reducer holds the "
+                                 "transport)")
+            if lowrank is not None or topk is not None or error_feedback or stochastic_rounding:
+                raise ValueError("sketch: not with lowrank, topk, error_feedback or stochastic_rounding (the reducer "
+                                 "owns its own residual)")
+            for l in model.layers:
+                sketch.state_for(l)  # (refuses a bucket the kernels do not take)
         self.error_feedback = bool(error_feedback)
         self.residuals = None
         self._ef_wire = None  # the engine-less trainer's one-slot wire, per layer
@@ -413,6 +430,11 @@ class DataParallelTrainer:
     def topk_residuals(self):
         """Every layer's top-k residual plane (n_pad f32), or None without ``topk``."""
         return None if self.topk is None else [self.topk.state_for(l).e for l in self.m.layers]
+
+    @property
+    def sketch_residuals(self):
+        """Every layer's count-sketch residual plane (n_pad f32), or None without ``sketch``."""
+        return None if self.sketch is None else [self.sketch.state_for(l).e for l in self.m.layers]
 
     def _opt_kw(self, l):
         """The optimizer, clip-group, error-feedback and stochastic-rounding arguments of layer l's request in the step
@@ -663,6 +685,8 @@ class DataParallelTrainer:
                             self.lowrank.reduce(l)
                         elif self.topk is not None:
                             self.topk.reduce(l)
+                        elif self.sketch is not None:
+                            self.sketch.reduce(l)
                         m.backward_data(i)
                         if h is not None:
                             clipped = self.grad_norm is not None  # (commits with its group, below)
