@@ -7,6 +7,7 @@
 #include "gemm/gemm_group.h"
 #include "lowrank/lowrank.h"
 #include "nn/nn.h"
+#include "rht/rht.h"
 #include "sketch/sketch.h"
 #include "topk/topk.h"
 
@@ -860,6 +861,57 @@ void sketch_fetch(at::Tensor& e, at::Tensor& wire, int64_t n, int64_t k, int64_t
   launch_sketch_fetch(e.data_ptr<float>(), wire.data_ptr(), n_pad, n, k, (int)max_blocks, fan_stream());
 }
 
+// ---- rotated one-bit compression (rht/rht.h). Every plane is a contiguous tensor on the gradient's GPU of exactly the
+// length the layout gives, so nothing behind it is reachable; no two arguments may be the same buffer.
+void rht_plane(const at::Tensor& t, at::ScalarType ty, int64_t n, const at::Tensor& ref, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == ty && t.device() == ref.device() &&
+                  t.numel() == n,
+              "rht: ", what, " must be a contiguous ", ty, " tensor of ", n, " elements on the gradient's GPU");
+}
+
+void rht_shape(int64_t n_pad, int64_t n, int64_t max_blocks) {
+  TORCH_CHECK(n_pad > 0 && n_pad % 4 == 0 && n_pad < ((int64_t)1 << 31),
+              "rht: n_pad must be a positive multiple of 4 below 2^31, got ", n_pad);
+  TORCH_CHECK(n >= 1 && n <= n_pad, "rht: 1 <= n <= n_pad, got n = ", n);
+  TORCH_CHECK(max_blocks >= 0 && max_blocks <= INT32_MAX, "rht: max_blocks >= 0");
+}
+
+void rht_transform(const at::Tensor& x, at::Tensor& out, int64_t n_pad, int64_t n, uint64_t seed, bool inverse,
+                   int64_t max_blocks) {
+  rht_shape(n_pad, n, max_blocks);
+  const int64_t rot = rht_layout(n).resid_elems;
+  rht_plane(x, at::kFloat, inverse ? rot : n_pad, x, "x");
+  rht_plane(out, at::kFloat, inverse ? n_pad : rot, x, "out");
+  TORCH_CHECK(x.data_ptr() != out.data_ptr(), "rht: x and out must be buffers of their own");
+  launch_rht_transform(x.data_ptr<float>(), out.data_ptr<float>(), n_pad, n, seed, inverse, (int)max_blocks,
+                       fan_stream());
+}
+
+void rht_encode(const at::Tensor& g, at::Tensor& e, at::Tensor& wire, int64_t n, uint64_t seed, int64_t max_blocks) {
+  const int64_t n_pad = g.numel();
+  rht_shape(n_pad, n, max_blocks);
+  const RhtLayout L = rht_layout(n);
+  rht_plane(g, at::kFloat, n_pad, g, "g");
+  rht_plane(e, at::kFloat, L.resid_elems, g, "e");
+  rht_plane(wire, at::kByte, L.wire_bytes, g, "wire");
+  TORCH_CHECK(g.data_ptr() != e.data_ptr() && wire.data_ptr() != g.data_ptr() && wire.data_ptr() != e.data_ptr(),
+              "rht: g, e and the wire must be buffers of their own");
+  launch_rht_encode(g.data_ptr<float>(), e.data_ptr<float>(), wire.data_ptr(), n_pad, n, seed, (int)max_blocks,
+                    fan_stream());
+}
+
+void rht_decode(const at::Tensor& wires, int64_t world, at::Tensor& g, int64_t n, uint64_t seed, double inv_world,
+                int64_t max_blocks) {
+  const int64_t n_pad = g.numel();
+  rht_shape(n_pad, n, max_blocks);
+  TORCH_CHECK(world >= 1 && world <= kRhtMaxWorld, "rht: 1 <= world <= 16, got ", world);
+  rht_plane(g, at::kFloat, n_pad, g, "g");
+  rht_plane(wires, at::kByte, world * rht_layout(n).wire_bytes, g, "wires");
+  TORCH_CHECK(wires.data_ptr() != g.data_ptr(), "rht: g and the wires must be buffers of their own");
+  launch_rht_decode(wires.data_ptr(), (int)world, g.data_ptr<float>(), n_pad, n, seed, (float)inv_world,
+                    (int)max_blocks, fan_stream());
+}
+
 }  // namespace
 
 void register_gemm(pybind11::module_& m) {
@@ -1047,6 +1099,26 @@ void register_nn(pybind11::module_& m) {
   sk.def("fetch", &sketch_fetch, "val[j] = e[idx[j]], e[idx[j]] = +0 (j < k) on the top-k wire",
          pybind11::arg("e"), pybind11::arg("wire"), pybind11::arg("n"), pybind11::arg("k"),
          pybind11::arg("max_blocks") = 0);
+  pybind11::module_ rh = m.def_submodule("rht", "rotated one-bit gradient compression kernels");
+  rh.def("layout", [](int64_t n_pad, int64_t n) {
+    rht_shape(n_pad, n, 0);
+    const RhtLayout L = rht_layout(n);
+    return std::vector<int64_t>{L.blocks, L.resid_elems, L.wire_bytes};
+  }, "{blocks of 4096, f32 elements of the residual plane, bytes of one rank's wire}", pybind11::arg("n_pad"),
+         pybind11::arg("n"));
+  rh.def("transform", &rht_transform,
+         "out = (1/64) H D x per block of 4096 (x: n_pad f32, +0 at or past n; out: blocks * 4096 f32), or with inverse "
+         "out[:n] = D (1/64) H x (x: blocks * 4096 f32; out: n_pad f32)",
+         pybind11::arg("x"), pybind11::arg("out"), pybind11::arg("n_pad"), pybind11::arg("n"), pybind11::arg("seed"),
+         pybind11::arg("inverse") = false, pybind11::arg("max_blocks") = 0);
+  rh.def("encode", &rht_encode,
+         "y = rht(g) + e; wire = [sign bits of y][mean |y| per block]; e = y - its one-bit value",
+         pybind11::arg("g"), pybind11::arg("e"), pybind11::arg("wire"), pybind11::arg("n"), pybind11::arg("seed"),
+         pybind11::arg("max_blocks") = 0);
+  rh.def("decode", &rht_decode,
+         "g[i] = inverse(the ranks' one-bit values added in rank order from +0)[i] * inv_world, i < n",
+         pybind11::arg("wires"), pybind11::arg("world"), pybind11::arg("g"), pybind11::arg("n"), pybind11::arg("seed"),
+         pybind11::arg("inv_world"), pybind11::arg("max_blocks") = 0);
 }
 
 void register_planner(pybind11::module_& m) {

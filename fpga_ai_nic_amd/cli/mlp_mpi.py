@@ -108,8 +108,13 @@ def run(argv=None, out=sys.stdout):
 
         sketch = SketchReducer(transport if world > 1 else None, cfg.density, rows=cfg.sketch_rows,
                                cols=cfg.sketch_cols, seed=cfg.sketch_seed)
+    rotated = None
+    if cfg.compress == "drive":  # the engine-less trainer as well
+        from ..parallel.rotated import RotatedSignReducer
+
+        rotated = RotatedSignReducer(transport if world > 1 else None, seed=cfg.drive_seed)
     kind = (cfg.compress if transport is not None and reducer is None and sparse is None and sketch is None
-            else "local")
+            and rotated is None else "local")
     impl = cfg.engine if device.type == "cuda" else "python"
     engine = make_engine(transport, kind, rounding=cfg.rounding, algo=cfg.algo, rings=cfg.rings,
                          max_slice_elems=cfg.slice_elems, compat_owner_fp32=cfg.compat_owner_fp32,
@@ -141,7 +146,8 @@ def run(argv=None, out=sys.stdout):
                                   error_feedback=cfg.error_feedback,
                                   error_feedback_codec=f"bfp_{cfg.rounding}",
                                   stochastic_rounding=cfg.stochastic_rounding, sr_seed=cfg.sr_seed,
-                                  moment_codec=cfg.moment_codec, lowrank=reducer, topk=sparse, sketch=sketch)
+                                  moment_codec=cfg.moment_codec, lowrank=reducer, topk=sparse, sketch=sketch,
+                                  rotated=rotated)
     trainer.opt_step = opt_step
     trainer.sr_step = sr_step
     x, y = make_data(mb, sizes[0], sizes[-1], rank, cfg.seed, device, dtype)
@@ -197,6 +203,9 @@ def run(argv=None, out=sys.stdout):
         if sketch is not None:
             print(f"ALLREDUCE: sketch {sketch.rows}x{sketch.cols} density={sketch.density:g} "
                   f"wire_bytes/step={sum(sketch.wire_bytes(l) for l in model.layers):.4g}", file=out)
+        if rotated is not None:
+            print(f"ALLREDUCE: drive seed={rotated.seed} "
+                  f"wire_bytes/step={sum(rotated.wire_bytes(l) for l in model.layers):.4g}", file=out)
     if a.dump_norms and rank == world - 1:  # the reference prints from the last rank
         for i, l in enumerate(model.layers):
             print(f"L1 of layer's {i} dweights after training : {float(l.gw.double().abs().sum()):.25g}", file=out)

@@ -4,7 +4,7 @@ Reference knobs and where they went:
   iters / MB / fuse_type / type / bn bk bc / C1..CN  -> positional CLI, kept (sw/mlp_mpi_example_f32.cpp:270-320)
   NUM_NODES=3 (sw:38)                               -> world size from the launcher (any N >= 1)
   `BFP_EN (hw/all_reduce.sv:13)                     -> compress = bfp | bfp4 | sign | raw | rccl | local | powersgd |
-                                                        topk | sketch
+                                                        topk | sketch | drive
   NUM_FP=16, MANT_SIZE=8 (hw/bfp_adapter.sv:34-36)   -> group of 16; 8-bit mantissas (bfp; rounding = rne | trunc, the
                                                         bit-exact ref) or 4-bit (bfp4, rne only)
   BUF_SIZE=512 CL slice (hw/all_reduce.sv:102)      -> slice_elems (ring)
@@ -30,7 +30,8 @@ class TrainConfig:
     sizes: list = field(default_factory=lambda: [1024, 4096, 4096, 1024])
     dtype: str = "bf16"            # bf16 | f32
     f32_gemm: str = "mfma"         # --dtype f32: mfma (exact f32 MFMA GEMM) | bf16x3 (split precision, 3 bf16 MFMAs)
-    compress: str = "bfp"          # bfp | bfp4 | sign | raw | raw_bf16 | rccl | local | powersgd | topk | sketch
+    compress: str = "bfp"          # bfp | bfp4 | sign | raw | raw_bf16 | rccl | local | powersgd | topk | sketch |
+                                   # drive
     rank: int = 4                  # powersgd: the rank of the approximation, 1..16
     lowrank_seed: int = 0          # powersgd: seed of the initial Q factors (the same on every rank)
     lowrank_orth: str = "mgs"      # powersgd: mgs (modified Gram-Schmidt) | cholqr2 (multi-workgroup CholeskyQR2)
@@ -38,6 +39,7 @@ class TrainConfig:
     sketch_rows: int = 5           # sketch: rows of the count sketch, 1 | 3 | 5
     sketch_cols: int = 65536       # sketch: columns of the count sketch, a multiple of 1024 in 1024 .. 2^22
     sketch_seed: int = 0           # sketch: seed of the hashes (the same on every rank), an int in [0, 2^64)
+    drive_seed: int = 0            # drive: seed of the rotation's signs (the same on every rank), in [0, 2^64)
     rounding: str = "rne"          # rne | trunc
     algo: str = "mesh"             # mesh | ring
     rings: int = 1
@@ -88,7 +90,8 @@ def add_named_flags(ap: argparse.ArgumentParser):
                          "f32 operands split in registers into two bf16 pieces each, three bf16 MFMAs per product "
                          "(about 2^-14.4 relative per product)")
     ap.add_argument("--compress", default=d.compress,
-                    choices=["bfp", "bfp4", "sign", "raw", "raw_bf16", "rccl", "local", "powersgd", "topk", "sketch"],
+                    choices=["bfp", "bfp4", "sign", "raw", "raw_bf16", "rccl", "local", "powersgd", "topk", "sketch",
+                             "drive"],
                     help="wire format of the all-reduce: bfp = 8-bit mantissas (17 B per 16 values), bfp4 = 4-bit "
                          "mantissas (9 B per 16 values, --rounding rne only; meant for use with --error-feedback), "
                          "sign = one sign bit per value and a power-of-two scale per group (codec sign1, 3 B per 16 "
@@ -104,7 +107,11 @@ def add_named_flags(ap: argparse.ArgumentParser):
                          "--sketch-cols f32 sketch of every bucket, every rank recovers the same --density fraction "
                          "of indices from the sum, and a second all-reduce carries their exact values: 4 * (rows * "
                          "cols + k) B per bucket whatever the world size; engine-less trainer, own residual, not "
-                         "checkpointed: not with --error-feedback or --stochastic-rounding)")
+                         "checkpointed: not with --error-feedback or --stochastic-rounding), drive = rotated "
+                         "one-bit compression (DRIVE: every block of 4096 values is rotated by a randomised Hadamard "
+                         "transform and sent as one sign bit per value and one f32 scale, 516 B per 4096 values, one "
+                         "all-gather per bucket; engine-less trainer, own residual in rotated coordinates, not "
+                         "checkpointed: not with --error-feedback or --stochastic-rounding; at most 16 ranks)")
     ap.add_argument("--rank", type=int, default=d.rank, help="--compress powersgd: rank of the approximation, 1..16")
     ap.add_argument("--lowrank-seed", type=int, default=d.lowrank_seed,
                     help="--compress powersgd: seed of the initial Q factors")
@@ -120,6 +127,8 @@ def add_named_flags(ap: argparse.ArgumentParser):
                     help="--compress sketch: columns of the count sketch, a multiple of 1024 in 1024 .. 2^22")
     ap.add_argument("--sketch-seed", type=int, default=d.sketch_seed,
                     help="--compress sketch: seed of the bucket and sign hashes, an int in [0, 2^64)")
+    ap.add_argument("--drive-seed", type=int, default=d.drive_seed,
+                    help="--compress drive: seed of the rotation's signs, an int in [0, 2^64)")
     ap.add_argument("--rounding", default=d.rounding, choices=["rne", "trunc"])
     ap.add_argument("--algo", default=d.algo, choices=["mesh", "ring"])
     ap.add_argument("--rings", type=int, default=d.rings)
@@ -232,6 +241,14 @@ def config_from_args(a, positional_sizes=None) -> TrainConfig:
             raise ValueError(f"--sketch-seed must lie in [0, 2^64), got {c.sketch_seed}")
         if c.error_feedback or c.stochastic_rounding:
             raise ValueError("--compress sketch keeps its own residual: not with --error-feedback or "
+                             "--stochastic-rounding")
+    if c.compress != "drive" and c.drive_seed != d.drive_seed:
+        raise ValueError("--drive-seed seeds the rotation of --compress drive: it needs --compress drive")
+    if c.compress == "drive":
+        if not 0 <= c.drive_seed < 1 << 64:
+            raise ValueError(f"--drive-seed must lie in [0, 2^64), got {c.drive_seed}")
+        if c.error_feedback or c.stochastic_rounding:
+            raise ValueError("--compress drive keeps its own residual: not with --error-feedback or "
                              "--stochastic-rounding")
     if c.compress == "topk":
         if not 0.0 < c.density <= 1.0:

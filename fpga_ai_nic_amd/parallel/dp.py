@@ -92,8 +92,15 @@ class DataParallelTrainer:
                  betas=None, eps: float = 1e-8, trust_ratio: bool = False,
                  max_grad_norm: float | None = None, error_feedback: bool = False,
                  error_feedback_codec: str = "bfp_rne", stochastic_rounding: bool = False, sr_seed: int = 0,
-                 moment_codec: str = "f32", lowrank=None, topk=None, sketch=None):
-        """``sketch``: a :class:`~fpga_ai_nic_amd.parallel.sketch.SketchReducer` — count-sketch compression on the
+                 moment_codec: str = "f32", lowrank=None, topk=None, sketch=None, rotated=None):
+        """``rotated``: a :class:`~fpga_ai_nic_amd.parallel.rotated.RotatedSignReducer` — rotated one-bit compression
+        (DRIVE) on the engine-less trainer (``engine`` must be None; the reducer holds the transport). After each
+        layer's bwd-weight GEMM the reducer replaces the layer's f32 gradient by the inverse rotation of the rank mean of
+        the ranks' one-bit rotated gradients (one synchronous all-gather) and the local update reads it as ``raw_f32``
+        with ``grad_scale`` 1, as with ``topk``. Not with ``lowrank``, ``topk``, ``sketch``, ``error_feedback`` or
+        ``stochastic_rounding`` (the reducer owns its own residual: ``rotated_residuals``, not checkpointed).
+
+        ``sketch``: a :class:`~fpga_ai_nic_amd.parallel.sketch.SketchReducer` — count-sketch compression on the
         engine-less trainer (``engine`` must be None; the reducer holds the transport). After each layer's bwd-weight
         GEMM the reducer replaces the layer's f32 gradient by the rank mean of gradient + residual at the k indices
         every rank recovers from the summed sketch (two synchronous all-reduces) and the local update reads it as
@@ -313,6 +320,17 @@ class DataParallelTrainer:
                                  "owns its own residual)")
             for l in model.layers:
                 sketch.state_for(l)  # (refuses a bucket the kernels do not take)
+        self.rotated = rotated
+        if rotated is not None:
+            if engine is not None:
+                raise ValueError("rotated: on the engine-less trainer only (engine=None; the reducer holds the "
+                                 "transport)")
+            if (lowrank is not None or topk is not None or sketch is not None or error_feedback
+                    or stochastic_rounding):
+                raise ValueError("rotated: not with lowrank, topk, sketch, error_feedback or stochastic_rounding (the "
+                                 "reducer owns its own residual)")
+            for l in model.layers:
+                rotated.state_for(l)  # (refuses a bucket the kernels do not take)
         self.error_feedback = bool(error_feedback)
         self.residuals = None
         self._ef_wire = None  # the engine-less trainer's one-slot wire, per layer
@@ -435,6 +453,11 @@ class DataParallelTrainer:
     def sketch_residuals(self):
         """Every layer's count-sketch residual plane (n_pad f32), or None without ``sketch``."""
         return None if self.sketch is None else [self.sketch.state_for(l).e for l in self.m.layers]
+
+    @property
+    def rotated_residuals(self):
+        """Every layer's residual plane in rotated coordinates (blocks * 4096 f32), or None without ``rotated``."""
+        return None if self.rotated is None else [self.rotated.state_for(l).e for l in self.m.layers]
 
     def _opt_kw(self, l):
         """The optimizer, clip-group, error-feedback and stochastic-rounding arguments of layer l's request in the step
@@ -687,6 +710,8 @@ class DataParallelTrainer:
                             self.topk.reduce(l)
                         elif self.sketch is not None:
                             self.sketch.reduce(l)
+                        elif self.rotated is not None:
+                            self.rotated.reduce(l)
                         m.backward_data(i)
                         if h is not None:
                             clipped = self.grad_norm is not None  # (commits with its group, below)
